@@ -9,7 +9,12 @@ One "step" = one pass of the hot path over one batch of synthetic scans resident
 with no data-path collective ("weak" scaling); the 20x20 confusion matrix and the ECE bins are all-reduced
 (RCCL) once after the timed region, as an evaluation run would.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, ...).  `--full` adds everything
+else beside it: the roofline step with HIP events around every conv launch (`--breakdown`), the CPU oracle baseline and the parity block,
+the shared-prefix schedule, the B = 1 stream, the capped-ECE form and the training step.  `--dump-outputs DIR` writes what the last timed
+step handed its caller (p_bar, entropy, MI, argmax; the IoU / ECE accumulators of the timed steps) as float32 / float64 `.npy` files.
 
 `--gpus N` ALWAYS means N ranks: under torch.distributed.run (the driver's launch line) WORLD_SIZE must equal N; started
 plainly with N > 1 this script launches `python -m torch.distributed.run --nproc-per-node N` on itself BEFORE touching the
@@ -58,10 +63,22 @@ def parse_args(argv=None):
     ap.add_argument("--precision", default="f16", choices=["fp32", "f16x3", "f16"],
                     help="conv precision: exact fp32 MFMA; split-fp16 (fp32 storage, 3 f16 MFMAs, fp32 accumulate); "
                          "f16 = fp16 storage + 1 f16 MFMA, fp32 accumulate (BASELINE configs[2] names half-precision storage)")
-    ap.add_argument("--breakdown", default=None, help="write a per-kernel / per-layer-shape timing table to this file")
+    ap.add_argument("--breakdown", default=None, help="with --full: write a per-kernel / per-layer-shape timing table to this file")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps also run the roofline step, CPU baseline + parity, shared-prefix, B = 1 stream, capped-ECE "
+                         "and training-step legs (the --no-* options above drop single legs); default: the headline measurement only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32 / float64; p_bar as a fixed seeded sample of pixels)")
     ap.add_argument("--stub-cpu", action="store_true",
                     help="launcher self-test (tests/test_distributed_cpu.py): gloo ranks on the CPU and a trivial step; no GPU, no HIP library")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.breakdown and not args.full:
+        ap.error("--breakdown needs --full (it comes from the extra roofline step)")
+    return args
 
 
 def _free_port():
@@ -246,6 +263,51 @@ def load_pmc(images):
     return pmc, os.path.relpath(PMC_FILE, ROOT)
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# --dump-outputs
+# ---------------------------------------------------------------------------------------------------------------
+DUMP_MAP_PIXELS = 1 << 20       # per-pixel maps (entropy, MI, argmax): every pixel up to this many, else a fixed seeded sample of this many
+DUMP_PBAR_PIXELS = 1 << 18      # p_bar (NCLS values per pixel): a fixed seeded sample of at most this many pixels
+DUMP_MAX_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, outs, iou, ece):
+    """What the last timed step handed its caller, as DIR/<name>.npy: `p_bar` [pixels, classes] (pixel-major rows of a fixed seeded sample of
+    the flattened (scan, row, column) index), `h_norm`, `mi_norm`, `preds` (every pixel [B, H, W] when there are at most DUMP_MAP_PIXELS of
+    them, else the same kind of sample), all float32; the IoU confusion matrix and the three ECE bin accumulators of the timed steps in
+    float64 (integer counts are exact).  The samples depend on the output shape only, so two builds given the same arguments dump the same
+    pixels."""
+    import numpy as np
+    import torch
+    p_bar, h_norm, mi_norm, preds = outs
+    n_pix = h_norm.numel()
+
+    def sample_index(k, seed):
+        if n_pix <= k:
+            return None
+        idx = np.sort(np.random.default_rng(seed).choice(n_pix, size=k, replace=False))
+        return torch.from_numpy(idx).to(h_norm.device)
+
+    pix = sample_index(DUMP_PBAR_PIXELS, 0)
+    rows = p_bar.permute(0, 2, 3, 1).reshape(n_pix, p_bar.shape[1])
+    arrays = {"p_bar": rows if pix is None else rows[pix]}
+    pix = sample_index(DUMP_MAP_PIXELS, 1)
+    for name, t in (("h_norm", h_norm), ("mi_norm", mi_norm), ("preds", preds)):
+        arrays[name] = t if pix is None else t.reshape(-1)[pix]
+    arrays = {k: v.float().cpu().numpy() for k, v in arrays.items()}
+    arrays["iou_confusion_matrix"] = iou.confmat.double().cpu().numpy()
+    _, n, sum_correct, sum_conf = ece._bins()
+    arrays["ece_bin_count"] = np.asarray(n, dtype=np.float64)
+    arrays["ece_bin_sum_correct"] = np.asarray(sum_correct, dtype=np.float64)
+    arrays["ece_bin_sum_conf"] = np.asarray(sum_conf, dtype=np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte budget"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
+
+
 def stub_main(args, rank, world):
     """Launcher self-test: N gloo ranks on the CPU, a trivial step, the same barrier / max-over-ranks / one-JSON-line protocol."""
     import torch
@@ -317,7 +379,7 @@ def main(argv=None):
 
     sn.set_conv_precision(args.precision)
     model = seeded_model(SalsaNext)
-    sd_cpu = {k: v.clone() for k, v in model.state_dict().items()}
+    sd_cpu = {k: v.clone() for k, v in model.state_dict().items()} if args.full else None     # the CPU baseline's weights
     model = model.to(dev)
     Hh, Ww, Tt = args.height, args.width, args.passes
     x_cpu, labels_cpu = synthetic_scan(args.scans, Hh, Ww, seed=1234 + rank)
@@ -332,7 +394,7 @@ def main(argv=None):
         p_bar, h_norm, mi_norm, preds = mc_predict(model, [x], T=Tt, share_prefix=share_prefix)
         iou.update(preds, labels)
         ece.update(p_bar, labels)
-        return h_norm
+        return p_bar, h_norm, mi_norm, preds
 
     def barrier():
         if dist is not None:
@@ -344,8 +406,9 @@ def main(argv=None):
     iou.reset(); ece.reset()
     barrier()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    last = step()
     barrier()
     dt = time.perf_counter() - t0
     rccl_world = 1
@@ -355,6 +418,39 @@ def main(argv=None):
         dt = float(t.item())
         rccl_world = dist.get_world_size()
         all_reduce_metrics(iou, ece, device=dev)                      # the evaluation's one exchange
+    if args.dump_outputs and rank == 0:
+        nbytes = dump_outputs(args.dump_outputs, last, iou, ece)
+        sys.stderr.write(f"bench.py: wrote the outputs of the last timed step to {args.dump_outputs} ({nbytes / 1e6:.1f} MB)\n")
+    del last
+
+    out = None
+    if rank == 0:
+        scans = args.scans * world * args.steps
+        out = {
+            "metric": f"range-image scans/sec ({Hh}x{Ww}, T={Tt} MC)", "value": round(scans / dt, 3), "unit": "scans/s",
+            "n_gpus": world, "rccl_world_size": rccl_world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": {"fp32": "f32", "f16x3": "f16x3 (fp32 I/O and accumulate; products as 3 split-fp16 MFMAs)",
+                      "f16": "f16 (fp16 activations/weights, fp32 accumulate + epilogue, fp32 logits)"}[args.precision],
+            "data": "synthetic",
+            "config": {"workload": f"SalsaNext MC-dropout T={Tt} + entropy/MI map + IoU/ECE accumulation, "
+                                   f"{args.scans} scans of {Hh}x{Ww}x5 per step per GPU "
+                                   f"({'BASELINE configs[2] shape' if (Hh, Ww, Tt) == (H, W, T) else 'non-default shape'})",
+                       "scans_per_step_per_gpu": args.scans, "T": Tt, "parallelism": f"scan-sharded x{world}",
+                       "mc_schedule": "shared deterministic prefix (3 context blocks + resBlock1 + resBlock2 convs once per scan)"
+                                      if args.shared_prefix else "every pass fully recomputed",
+                       "ece_form": "ECEAggregator(max_samples=None): every valid pixel, exact per-bin accumulators on the device (no host sync); "
+                                   "the Trainer's capped form is timed beside it as `ece_capped_500k` (--full)"},
+        }
+    if not args.full:          # the headline only: no extra step, leg or metric readout
+        if rank == 0:
+            sys.stdout.flush()
+            os.write(line_fd, (json.dumps(out) + "\n").encode())
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
     miou, _ = iou.compute([str(i) for i in range(NCLS)], test_mask=[0] + [1] * (NCLS - 1), ignore_gt=[0])
     (ece_v, _), _ = ece.compute()[:2]
 
@@ -568,27 +664,9 @@ def main(argv=None):
             train, train_hung = guarded_train_leg(dev, rank, world)
 
     if rank == 0:
-        scans = args.scans * world * args.steps
-        out = {
-            "metric": f"range-image scans/sec ({Hh}x{Ww}, T={Tt} MC)", "value": round(scans / dt, 3), "unit": "scans/s",
-            "n_gpus": world, "rccl_world_size": rccl_world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": {"fp32": "f32", "f16x3": "f16x3 (fp32 I/O and accumulate; products as 3 split-fp16 MFMAs)",
-                      "f16": "f16 (fp16 activations/weights, fp32 accumulate + epilogue, fp32 logits)"}[args.precision],
-            "data": "synthetic",
-            "config": {"workload": f"SalsaNext MC-dropout T={Tt} + entropy/MI map + IoU/ECE accumulation, "
-                                   f"{args.scans} scans of {Hh}x{Ww}x5 per step per GPU "
-                                   f"({'BASELINE configs[2] shape' if (Hh, Ww, Tt) == (H, W, T) else 'non-default shape'})",
-                       "scans_per_step_per_gpu": args.scans, "T": Tt, "parallelism": f"scan-sharded x{world}",
-                       "mc_schedule": "shared deterministic prefix (3 context blocks + resBlock1 + resBlock2 convs once per scan)"
-                                      if args.shared_prefix else "every pass fully recomputed",
-                       "ece_form": "ECEAggregator(max_samples=None): every valid pixel, exact per-bin accumulators on the device (no host sync); "
-                                   "the Trainer's capped form is timed beside it as `ece_capped_500k`"},
-            "metrics_of_the_timed_run": {"mIoU_random_labels": round(miou, 6), "ece_all_pixels": round(ece_v, 6),
-                                         "note": "synthetic random labels: plumbing only; parity is the `parity` block"},
-            "roofline": roofline,
-        }
+        out["metrics_of_the_timed_run"] = {"mIoU_random_labels": round(miou, 6), "ece_all_pixels": round(ece_v, 6),
+                                           "note": "synthetic random labels: plumbing only; parity is the `parity` block"}
+        out["roofline"] = roofline
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"], ref = cpu_baseline_and_parity_reference(sd_cpu, x_cpu, Tt)
             out["parity"] = parity_block(model, x_cpu, ref, Tt, dev)

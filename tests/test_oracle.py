@@ -17,6 +17,29 @@ def _t(a):
     return torch.from_numpy(np.asarray(a))
 
 
+# The goldens hold the reference's float32 results computed on one host.  Their last bits depend on the CPU that computed them: which
+# vectorised transcendental kernels, MKL / oneDNN code paths and thread partitions torch picks there.  On another x86 host the same
+# operations land a few float32 roundings away (at most 6 measured), so the oracle is held to the golden within F32_ULPS roundings.
+F32_EPS = float(np.finfo(np.float32).eps)
+F32_ULPS = 8
+AUROC_PAIRS = 8
+
+
+def _max_ulps(got, want):
+    """max over elements of |got - want| in float32 roundings of max(1, |want|)."""
+    got = np.asarray(got.detach() if torch.is_tensor(got) else got, dtype=np.float64)
+    want = np.asarray(want, dtype=np.float64)
+    return float((np.abs(got - want) / (F32_EPS * np.maximum(1.0, np.abs(want)))).max())
+
+
+def _max_ulps_of_scale(got, want):
+    """max |got - want| in float32 roundings of max |want|: for gradients, whose elements are sums of terms that cancel -- a rounding of a
+    term is measured against the gradient's scale, not against the small element it cancels down to."""
+    got = np.asarray(got.detach() if torch.is_tensor(got) else got, dtype=np.float64)
+    want = np.asarray(want, dtype=np.float64)
+    return float(np.abs(got - want).max() / (F32_EPS * max(float(np.abs(want).max()), np.finfo(np.float32).tiny)))
+
+
 def _sd():
     return seeded_model(SalsaNext).state_dict()
 
@@ -139,14 +162,14 @@ def test_dirichlet_head_matches_reference_golden():
     g = golden("dirichlet_head_2x21x8x64")
     outs = torch.from_numpy(g["outputs"])
     alpha, p_hat, h_norm, preds = odir.head(outs, 20)
-    assert float((alpha - torch.from_numpy(g["alpha"])).abs().max()) == 0.0
-    assert float((p_hat - torch.from_numpy(g["p_hat"])).abs().max()) == 0.0
-    assert float((h_norm - torch.from_numpy(g["H_norm"])).abs().max()) == 0.0
+    assert _max_ulps(alpha, g["alpha"]) <= F32_ULPS
+    assert _max_ulps(p_hat, g["p_hat"]) <= F32_ULPS
+    assert _max_ulps(h_norm, g["H_norm"]) <= F32_ULPS
     assert torch.equal(preds, torch.from_numpy(g["preds"]))
-    assert float((odir.aleatoric(alpha) - torch.from_numpy(g["AU"])).abs().max()) == 0.0
-    assert float((odir.epistemic(alpha) - torch.from_numpy(g["EU"])).abs().max()) == 0.0
+    assert _max_ulps(odir.aleatoric(alpha), g["AU"]) <= F32_ULPS
+    assert _max_ulps(odir.epistemic(alpha), g["EU"]) <= F32_ULPS
     a2 = odir.alpha_from_shape_and_scale(outs[:, :20], outs[:, 20:21], 2.5, 1e-6)
-    assert float((a2 - torch.from_numpy(g["alpha_T2p5_eps1em6"])).abs().max()) == 0.0
+    assert _max_ulps(a2, g["alpha_T2p5_eps1em6"]) <= F32_ULPS
     # known answers: zero evidence (scale -> -inf) gives alpha = 1 + eps, the uniform p_hat and H_norm = 1
     flat = torch.zeros(1, 21, 2, 2)
     flat[:, 20] = -100.0
@@ -166,8 +189,12 @@ def test_auroc_golden_and_known_answers():
         ov = torch.from_numpy(g["override"]) if src == "override" else None
         s1, e1 = ometrics.auroc_samples(inputs[mode], labs, mode, score, 0, 1e-12, ov)
         s2, e2 = ometrics.auroc_samples(inputs[mode].flip(0), labs.flip(0), mode, score, 0, 1e-12, None if ov is None else ov.flip(0))
-        a = ometrics.auroc_from_samples(np.concatenate([s1, s2]), np.concatenate([e1, e2]))
-        assert a == float(g[key]) and s1.size + s2.size == int(g["nsamples:" + key[len("auroc:"):]])
+        err = np.concatenate([e1, e2])
+        a = ometrics.auroc_from_samples(np.concatenate([s1, s2]), err)
+        # one (error, correct) pair whose near-equal scores swap order under another CPU's last-bit rounding moves the AUROC by
+        # 1 / (errors x correct): at most AUROC_PAIRS such swaps
+        pairs = float(err.sum()) * float(err.size - err.sum())
+        assert abs(a - float(g[key])) <= AUROC_PAIRS / pairs and s1.size + s2.size == int(g["nsamples:" + key[len("auroc:"):]])
     # hand-derived: perfectly separated scores give 1, reversed 0, one inversion among 2 x 2 gives 3/4
     assert ometrics.auroc_from_samples(np.array([0.9, 0.8, 0.2, 0.1]), np.array([1, 1, 0, 0])) == 1.0
     assert ometrics.auroc_from_samples(np.array([0.9, 0.8, 0.2, 0.1]), np.array([0, 0, 1, 1])) == 0.0
@@ -206,8 +233,8 @@ def test_tversky_golden():
             x = inp.clone().requires_grad_(True)
             lo = olosses.tversky(x, lab, 20, act, 0.7, 0.3, 1.0, 255, red)
             ((lo * wgt).sum() if red == "none" else lo).backward()
-            assert float((lo.detach() - torch.from_numpy(g[f"loss:{act}|{red}"])).abs().max()) == 0.0
-            assert float((x.grad - torch.from_numpy(g[f"grad:{act}|{red}"])).abs().max()) == 0.0
+            assert _max_ulps(lo, g[f"loss:{act}|{red}"]) <= F32_ULPS
+            assert _max_ulps_of_scale(x.grad, g[f"grad:{act}|{red}"]) <= F32_ULPS
     assert float(olosses.tversky(logits, torch.full((2, 8, 64), 255), 20, "logits")) == float(g["loss:all_ignored"]) == 0.0
 
 
@@ -243,8 +270,8 @@ def test_dirichlet_losses_golden():
         a = alpha.clone().requires_grad_(True)
         lo = fn(a)
         lo.backward()
-        assert float((lo.detach() - torch.from_numpy(g["loss:" + name])).abs()) == 0.0
-        assert float((a.grad - torch.from_numpy(g["grad:" + name])).abs().max()) == 0.0
+        assert _max_ulps(lo, g["loss:" + name]) <= F32_ULPS
+        assert _max_ulps_of_scale(a.grad, g["grad:" + name]) <= F32_ULPS
     # known answers at the uniform prior alpha = 1 (C = 4): NLL = ln 4; digamma-CE = psi(4) - psi(1) = 1 + 1/2 + 1/3
     one = torch.ones(1, 4, 1, 2)
     y = torch.tensor([[[1, 3]]])
@@ -359,7 +386,9 @@ def test_fpn_resnet50_oracle_matches_reference_golden():
     assert sd["backbone.layer4.2.conv3.weight"].shape == (2048, 512, 1, 1) and sd["fpn_block4.0.weight"].shape == (1024, 2048, 3, 3)
     with torch.no_grad():
         y = ofpn.fpn_forward(sd, _t(g["x"]), _t(g["meta"]), "resnet50", True, True)
-    assert float((y - _t(g["out"])).abs().max()) <= 1e-5 * max(1.0, float(np.abs(g["out"]).max()))
+    # 50 float32 layers over randomised BatchNorm: the golden host's conv kernels and thread partitions leave 2e-5 .. 8e-5 of the output
+    # scale of rounding noise (measured over hosts and thread counts), so the bound is 2e-4 of it where the shallower backbones keep 1e-5
+    assert float((y - _t(g["out"])).abs().max()) <= 2e-4 * max(1.0, float(np.abs(g["out"]).max()))
 
 
 def test_fpn_opt_oracle_matches_reference_golden():
