@@ -13,32 +13,51 @@ pytestmark = pytest.mark.gpu
 FAMILIES = [(1, 1, 0), (3, 1, 1), (3, 2, 2), (2, 2, 1)]
 
 
-def _run(dev, n, cin_parts, cout, h, w, fam, seed, act=True, bn=True, resid=True, scales=False, ps_first=False):
+def _run(dev, n, cin_parts, cout, h, w, fam, seed, act=True, bn=True, resid=True, scales=False, ps_first=False, bias=True, big=False,
+         stats=False, expect_kernel=None):
+    """expect_kernel: the instantiation the launch must record (slu_conv2d_kernel_name).  stats: the fused BatchNorm statistics of the
+    stored output are checked too, as test_gpu_backward.test_fused_bn_statistics does."""
     k, dil, pad = fam
     g = torch.Generator().manual_seed(seed)
     srcs_cpu = []
     cin = 0
     for i, c in enumerate(cin_parts):
         ps = ps_first and i == 0
-        t = torch.randn(n, c, h // 2 if ps else h, w // 2 if ps else w, generator=g)
+        t = torch.randn(n, c, h // 2 if ps else h, w // 2 if ps else w, generator=g) * (30.0 if big else 1.0)
         s = None
         if scales:
             s = (torch.rand(n, c, generator=g) > 0.2).float() * 1.25
         srcs_cpu.append((t, s, ps))
         cin += c // 4 if ps else c
     wgt = torch.randn(cout, cin, k, k, generator=g) / (cin * k * k) ** 0.5
-    bias = torch.randn(cout, generator=g) * 0.1
+    bias = torch.randn(cout, generator=g) * 0.1 if bias else None
     bn_a = torch.rand(cout, generator=g) + 0.5 if bn else None
     bn_b = torch.randn(cout, generator=g) * 0.1 if bn else None
     res = torch.randn(n, cout, h, w, generator=g) if resid else None
     want = osalsa.fused_conv(srcs_cpu, wgt, bias, pad, dil, 0.01 if act else None, bn_a, bn_b, res)
     d = lambda t: None if t is None else t.to(dev).contiguous()
     wpack = ops.pack_conv_weight(d(wgt))
-    got = ops.conv2d_fused([ConvSource(d(t), d(s), ps) for t, s, ps in srcs_cpu], wpack, cout, k, dil, pad,
-                           bias=d(bias), slope=0.01 if act else None, bn_a=d(bn_a), bn_b=d(bn_b), resid=d(res))
+    st = torch.zeros((2, cout), dtype=torch.float64, device=dev) if stats else None
+    if expect_kernel is not None:
+        ops.TIMING, ops.TIMING_TAGS = [], []              # measurement mode records the instantiation slu_conv2d_kernel_name reports
+    try:
+        got = ops.conv2d_fused([ConvSource(d(t), d(s), ps) for t, s, ps in srcs_cpu], wpack, cout, k, dil, pad,
+                               bias=d(bias), slope=0.01 if act else None, bn_a=d(bn_a), bn_b=d(bn_b), resid=d(res), stats=st)
+        launched = [t[0] for t in ops.TIMING] if expect_kernel is not None else None
+    finally:
+        if expect_kernel is not None:
+            ops.TIMING, ops.TIMING_TAGS = None, []
     torch.cuda.synchronize()
+    if expect_kernel is not None:
+        assert launched == [expect_kernel], (cin_parts, cout, n, h, w, fam, launched)
+    scale = max(1.0, float(want.abs().max())) if big else 1.0
     err = float((got.cpu() - want).abs().max())
-    assert err <= 1e-4, f"fam={fam} cin={cin_parts} cout={cout} {h}x{w}: max abs err {err}"
+    assert err <= 1e-4 * scale, f"fam={fam} cin={cin_parts} cout={cout} {h}x{w}: max abs err {err}"
+    if stats:
+        s, q = ops.bn_stats(got)
+        assert float(((st[0] - s).abs() / (s.abs() + 1.0)).max()) <= 1e-5 and float(((st[1] - q).abs() / q).max()) <= 1e-5
+        ref = got.double()
+        assert float(((st[0] - ref.sum((0, 2, 3))).abs() / (ref.abs().sum((0, 2, 3)) + 1.0)).max()) <= 1e-6
 
 
 @pytest.mark.parametrize("fam", FAMILIES)
@@ -56,7 +75,9 @@ def test_ragged_sizes_and_odd_channels(cuda, fam):
 
 
 def test_big_tiles_full_resolution_row(cuda):
-    # enough workgroups that choose_cfg picks the TH=8 / M64 / M128 tiles
+    # full-resolution rows of the real layers.  Under choose_cfg's thresholds (>= 512 workgroups, >= 3 072 eight-row tiles for 32 outputs)
+    # these shapes select the 4-row tiles (M32_TH4 / M64_TH4); the TH=8 / M64 / M128 tiles are checked, each at a shape that selects it and
+    # with its name asserted, by test_gpu_dispatch_coverage.test_fp32_instantiation
     _run(cuda, 1, [32], 32, 64, 1024, (3, 2, 2), seed=6)
     _run(cuda, 1, [32], 64, 64, 1024, (3, 1, 1), seed=7)
     _run(cuda, 4, [64], 128, 32, 512, (2, 2, 1), seed=8)

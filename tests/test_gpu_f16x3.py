@@ -18,7 +18,8 @@ def _t(a):
     return torch.from_numpy(np.asarray(a))
 
 
-def _run(dev, n, cin_parts, cout, h, w, fam, seed, scales=False, ps_first=False, big=False):
+def _run(dev, n, cin_parts, cout, h, w, fam, seed, scales=False, ps_first=False, big=False, resid=True, expect_kernel=None):
+    """expect_kernel: the instantiation the split-fp16 launch must record (slu_conv2d_kernel_name)."""
     k, dil, pad = fam
     g = torch.Generator().manual_seed(seed)
     srcs, cin = [], 0
@@ -30,12 +31,22 @@ def _run(dev, n, cin_parts, cout, h, w, fam, seed, scales=False, ps_first=False,
         cin += c // 4 if ps else c
     wgt = torch.randn(cout, cin, k, k, generator=g) / (cin * k * k) ** 0.5
     bias, bn_a, bn_b = torch.randn(cout, generator=g) * 0.1, torch.rand(cout, generator=g) + 0.5, torch.randn(cout, generator=g) * 0.1
-    res = torch.randn(n, cout, h, w, generator=g)
+    res = torch.randn(n, cout, h, w, generator=g) if resid else None
     want = osalsa.fused_conv(srcs, wgt, bias, pad, dil, 0.01, bn_a, bn_b, res)
     d = lambda t: None if t is None else t.to(dev).contiguous()
     dsrc = [ConvSource(d(t), d(s), ps) for t, s, ps in srcs]
-    got = ops.conv2d_fused(dsrc, ops.pack_conv_weight_f16x3(d(wgt)), cout, k, dil, pad, bias=d(bias), slope=0.01, bn_a=d(bn_a),
-                           bn_b=d(bn_b), resid=d(res), precision="f16x3")
+    wpack16 = ops.pack_conv_weight_f16x3(d(wgt))
+    if expect_kernel is not None:
+        ops.TIMING, ops.TIMING_TAGS = [], []              # measurement mode records the instantiation slu_conv2d_kernel_name reports
+    try:
+        got = ops.conv2d_fused(dsrc, wpack16, cout, k, dil, pad, bias=d(bias), slope=0.01, bn_a=d(bn_a), bn_b=d(bn_b), resid=d(res),
+                               precision="f16x3")
+        launched = [t[0] for t in ops.TIMING] if expect_kernel is not None else None
+    finally:
+        if expect_kernel is not None:
+            ops.TIMING, ops.TIMING_TAGS = None, []
+    if expect_kernel is not None:
+        assert launched == [expect_kernel], (cin_parts, cout, n, h, w, fam, launched)
     exact = ops.conv2d_fused(dsrc, ops.pack_conv_weight(d(wgt)), cout, k, dil, pad, bias=d(bias), slope=0.01, bn_a=d(bn_a),
                              bn_b=d(bn_b), resid=d(res))
     scale = max(1.0, float(want.abs().max()))
@@ -57,6 +68,9 @@ def test_ragged_sizes_odd_channels_and_large_values(cuda, fam):
 
 
 def test_big_tiles_concat_and_pixel_shuffle(cuda):
+    # full-resolution rows, concat and PixelShuffle sources.  These shapes stay under choose_cfg's thresholds (M32_TH4 / M64_TH4 and the
+    # streaming 1x1 kernel); M128_TH4 and the other forms the headline launches are checked, names asserted, by
+    # test_gpu_dispatch_coverage.test_f16x3_instantiation
     _run(cuda, 1, [32], 32, 64, 1024, (3, 2, 2), seed=6)
     _run(cuda, 1, [32], 64, 64, 1024, (3, 1, 1), seed=7)
     _run(cuda, 4, [64], 128, 32, 512, (2, 2, 1), seed=8)

@@ -52,8 +52,10 @@ def test_layout_round_trip_and_padding(cuda):
         h8.from_h8(torch.zeros(1, 1, 4, 4, 8, device=cuda))   # wrong dtype
 
 
-def _conv_case(dev, n, parts, cout, h, w, fam, seed, scales=False, resid=True, out_f32=False, nbatch_last=0, big=False):
-    """parts: real channel counts per source (multiples of 8 except the last)."""
+def _conv_case(dev, n, parts, cout, h, w, fam, seed, scales=False, resid=True, out_f32=False, nbatch_last=0, big=False, bias=True, bn=True,
+               act=True, expect_kernel=None):
+    """parts: real channel counts per source (multiples of 8 except the last).  expect_kernel: the instantiation the launch must
+    record (slu_conv2d_h8_kernel_name), checked before the numbers."""
     k, dil, pad = fam
     g = torch.Generator().manual_seed(seed)
     srcs, osrcs, cin = [], [], 0
@@ -67,12 +69,24 @@ def _conv_case(dev, n, parts, cout, h, w, fam, seed, scales=False, resid=True, o
         osrcs.append((_r16(tt * s[:, :c, None, None]) if s is not None else tt, None, False))
         cin += c
     wgt = _r16(torch.randn(cout, cin, k, k, generator=g) / (cin * k * k) ** 0.5)
-    bias, bn_a, bn_b = torch.randn(cout, generator=g) * 0.1, torch.rand(cout, generator=g) + 0.5, torch.randn(cout, generator=g) * 0.1
+    use_bias, bias, bn_a, bn_b = bias, torch.randn(cout, generator=g) * 0.1, torch.rand(cout, generator=g) + 0.5, torch.randn(cout, generator=g) * 0.1
+    bias, bn_a, bn_b = bias if use_bias else None, bn_a if bn else None, bn_b if bn else None
+    slope = 0.01 if act else None
     res = _r16(torch.randn(n, cout, h, w, generator=g)) if (resid and not out_f32) else None
-    want = osalsa.fused_conv(osrcs, wgt, bias, pad, dil, 0.01, bn_a, bn_b, res)
+    want = osalsa.fused_conv(osrcs, wgt, bias, pad, dil, slope, bn_a, bn_b, res)
     d = lambda t: None if t is None else t.to(dev).contiguous()
-    got = h8.conv2d_h8(srcs, h8.pack_conv_weight_h8(d(wgt)), cin, cout, k, dil, pad, bias=d(bias), slope=0.01, bn_a=d(bn_a), bn_b=d(bn_b),
-                       resid=None if res is None else h8.to_h8(d(res)), out_f32_nchw=out_f32)
+    wpack, dres = h8.pack_conv_weight_h8(d(wgt)), None if res is None else h8.to_h8(d(res))
+    if expect_kernel is not None:
+        ops.TIMING, ops.TIMING_TAGS = [], []              # measurement mode records the instantiation slu_conv2d_h8_kernel_name reports
+    try:
+        got = h8.conv2d_h8(srcs, wpack, cin, cout, k, dil, pad, bias=d(bias), slope=slope, bn_a=d(bn_a), bn_b=d(bn_b), resid=dres,
+                           out_f32_nchw=out_f32)
+        launched = [t[0] for t in ops.TIMING] if expect_kernel is not None else None
+    finally:
+        if expect_kernel is not None:
+            ops.TIMING, ops.TIMING_TAGS = None, []
+    if expect_kernel is not None:
+        assert launched == [expect_kernel], (parts, cout, n, h, w, fam, launched)
     if out_f32:
         assert got.dtype == torch.float32 and got.shape == (n, cout, h, w)
         y = got.cpu()
@@ -308,5 +322,30 @@ def test_ouster_shape_128x4096_T16(cuda):
             fp, fh, fm, fa = model.mc_predict_fused(x.to(cuda), t, share_prefix=share, scales=oscales)
             assert float((fp - p_bar).abs().max()) <= 2e-6 and float((fh - h_norm).abs().max()) <= 2e-5
             assert float((fm - mi_norm).abs().max()) <= 2e-5 and int((fa != preds).sum()) <= 4
+    finally:
+        sn.set_conv_precision("fp32")
+
+
+def test_batch_beyond_2_31_elements(cuda):
+    """bench.py --height 128 --width 4096 --passes 16 (8 scans x 16 passes = 128 images of 128x4096): every 32-channel fp16 tensor holds
+    exactly 2^31 values and the 64-channel ones 2^32, so any 32-bit element offset in the full-resolution kernels (ctx_h8, ring3_h8,
+    tail2_h8, conv1x1_h8, head / from_h8, to_h8) wraps.  The logits of the first and the last image against the oracle on that one image
+    with its own multipliers, at test_ouster_shape_128x4096_T16's bars."""
+    model = seeded_model(sn.SalsaNext).to(cuda)
+    sn.set_conv_precision("f16")
+    try:
+        scans, t, h, w = 8, 16, 128, 4096
+        x, _ = synthetic_scan(scans, h, w, seed=23)
+        oscales = osalsa.draw_dropout_scales(t * scans, 0.2, torch.Generator().manual_seed(29))
+        with torch.no_grad():
+            got = model.forward_with_dropout_scales(x.to(cuda).repeat(t, 1, 1, 1), {k: v.to(cuda) for k, v in oscales.items()})
+            assert got.shape == (t * scans, 20, h, w)
+            sel = {i: got[i].cpu() for i in (0, t * scans - 1)}
+        del got
+        sd = {k: v.cpu() for k, v in model.state_dict().items()}
+        for i, y in sel.items():
+            want = osalsa.salsanext_forward(sd, x[i % scans:i % scans + 1], {k: v[i:i + 1] for k, v in oscales.items()})[0]
+            assert float((y - want).abs().max()) <= 1e-3, (i, float((y - want).abs().max()))
+            assert float((_entropy(y[None]) - _entropy(want[None])).abs().max()) <= 1e-3
     finally:
         sn.set_conv_precision("fp32")
