@@ -9,7 +9,9 @@
 // no LDS.  One wave accumulates a 32 x 32 x (KS*KS taps) block of dW over a strided set of pixel runs; the
 // tap-shifted B operands of neighbouring K-steps overlap and are served by L1/L2.  Partial blocks are added
 // to a tap-major image dWp[co][tap][ci] with float atomics (contiguous 128-byte segments per instruction;
-// summation order is not reproducible bit for bit), then unpacked to OIHW.
+// summation order is not reproducible bit for bit), then unpacked to OIHW.  Any W: a pixel pair may straddle two
+// rows (odd W), so each lane half tracks the row and column of its own pixel; an odd total pixel count leaves the
+// second half of the last pair empty.
 #include "slu_common.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -26,7 +28,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const float* __restrict__
   const int hh = lane >> 5, jj = lane & 31;
   const int cob = blockIdx.y, cib = blockIdx.z;
   const long long HW = (long long)H * W;
-  const long long npairs = (long long)N * HW / 2;
+  const long long npix = (long long)N * HW;
+  const long long npairs = (npix + 1) / 2;
   const long long nruns = (npairs + kRun - 1) / kRun;
   const long long worker = (long long)blockIdx.x * 4 + wave, nworkers = (long long)gridDim.x * 4;
 
@@ -48,13 +51,13 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const float* __restrict__
   for (long long run = worker; run < nruns; run += nworkers) {
     const long long q0 = run * kRun;
     const long long q1 = (q0 + kRun < npairs) ? q0 + kRun : npairs;
-    // position of the first pixel of the run (wave-uniform; kept in scalar registers and advanced incrementally)
-    const long long pix0 = 2 * q0;
+    // position of this lane's pixel of the run's first pair (per lane half: with W odd, the two pixels of a pair may lie on two rows)
+    const long long pix0 = 2 * q0 + hh;
     const long long n0 = pix0 / HW;
     const int rem0 = (int)(pix0 - n0 * HW);
     int y = rem0 / W, x = rem0 - y * W;
-    const float* pa = abase + (size_t)(pix0 + hh) * Cop;
-    const float* pb = bbase + (size_t)(pix0 + hh) * Cip;
+    const float* pa = abase + (size_t)pix0 * Cop;
+    const float* pb = bbase + (size_t)pix0 * Cip;
     // four K-steps (pixel pairs) per iteration: all 4 * (1 + T) loads are issued before the first MFMA, so the
     // L2/HBM latency of one batch hides behind the 4 * T MFMAs of the previous one across the 2 waves per SIMD
     constexpr int U = (T >= 9) ? 2 : 4;           // 3x3: 144 accumulator registers leave room for two batches of operands
@@ -63,17 +66,18 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const float* __restrict__
       int yu = y, xu = x;
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        const bool live = q + u < q1;
+        const bool live = q + u < q1 && 2 * (q + u) + hh < npix;      // the second pixel of the last pair exists only if npix is even
         a[u] = live ? pa[(size_t)u * 2 * Cop] : 0.0f;
 #pragma unroll
         for (int t = 0; t < T; ++t) {
-          const int yy = yu - PAD + (t / KS) * DIL, xx = xu + hh - PAD + (t % KS) * DIL;
+          const int yy = yu - PAD + (t / KS) * DIL, xx = xu - PAD + (t % KS) * DIL;
           const bool ok = live && yy >= 0 && yy < H && xx >= 0 && xx < W;
-          const float v = pb[ok ? (long long)u * 2 * Cip + tapoff[t] : 0];
+          // masked-off lanes read the first pixel of the pair (pixel 2 q always exists)
+          const float v = pb[ok ? (long long)u * 2 * Cip + tapoff[t] : -(long long)hh * Cip];
           b[u][t] = ok ? v : 0.0f;
         }
         xu += 2;
-        if (xu >= W) { xu = 0; ++yu; if (yu >= H) yu = 0; }      // W is even: a pair never straddles a row
+        while (xu >= W) { xu -= W; if (++yu >= H) yu = 0; }
       }
 #pragma unroll
       for (int u = 0; u < U; ++u)
@@ -118,7 +122,7 @@ __global__ __launch_bounds__(256, 2) void wgrad1x1_kernel(const float* __restric
   const int hh = lane >> 5, jj = lane & 31;
   const int cob0 = blockIdx.y * MT, cib0 = blockIdx.z * NT;
   const int ncob = Cop / 32, ncib = Cip / 32;
-  const long long npairs = npix / 2;
+  const long long npairs = (npix + 1) / 2;                  // an odd pixel count leaves the second half of the last pair empty
   const long long nruns = (npairs + kRun - 1) / kRun;
   const long long worker = (long long)blockIdx.x * 4 + wave, nworkers = (long long)gridDim.x * 4;
 
@@ -144,8 +148,8 @@ __global__ __launch_bounds__(256, 2) void wgrad1x1_kernel(const float* __restric
       float a[U][MT], b[U][NT];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        const bool live = q + u < q1;
-        const size_t pix = (size_t)(2 * (live ? q + u : q0) + hh);
+        const bool live = q + u < q1 && 2 * (q + u) + hh < npix;
+        const size_t pix = (size_t)(live ? 2 * (q + u) + hh : 2 * q0);
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
           const float v = abase[i][pix * Cop];
@@ -615,7 +619,6 @@ extern "C" size_t slu_wgrad_packed_floats(int cout, int cin, int ksize) {
 extern "C" int slu_conv2d_wgrad(const float* da_t, const float* in_t, int N, int H, int W, int Cout, int Cin, int ksize, int dil, int pad,
                                 float* dWp, float* dW, slu_stream_t stream) {
   if (!da_t || !in_t || !dWp || !dW || N <= 0 || H <= 0 || W <= 0 || Cout <= 0 || Cin <= 0) return SLU_EINVAL;
-  if (W & 1) return SLU_EUNSUPPORTED;
   if (Cout > 65535 * 32 || Cin > 65535 * 32) return SLU_EUNSUPPORTED;
   const int Cop = (Cout + 31) / 32 * 32, Cip = (Cin + 31) / 32 * 32;
   hipStream_t st = slu_stream(stream);

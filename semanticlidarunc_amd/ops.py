@@ -741,8 +741,6 @@ def conv2d_wgrad(da_t, in_t, n, h, w, cout, cin, ksize, dil, pad):
     cop, cip = (cout + 31) // 32 * 32, (cin + 31) // 32 * 32
     if tuple(da_t.shape) != (n, h * w, cop) or tuple(in_t.shape) != (n, h * w, cip):
         raise RuntimeError("conv2d_wgrad: operand shapes do not match")
-    if w % 2:
-        raise RuntimeError("conv2d_wgrad: W must be even")
     lib = _lib.load()
     scratch = torch.empty(lib.slu_wgrad_packed_floats(cout, cin, ksize), dtype=torch.float32, device=da_t.device)
     dw = torch.empty((cout, cin, ksize, ksize), dtype=torch.float32, device=da_t.device)

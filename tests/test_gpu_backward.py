@@ -92,6 +92,23 @@ def test_wgrad_and_dgrad_match_torch_autograd(cuda, fam, cin, cout):
     assert _rel(dx, x.grad) <= 1e-4
 
 
+@pytest.mark.parametrize("fam", FAMILIES)
+@pytest.mark.parametrize("n,h,w", [(1, 3, 5), (3, 3, 65), (2, 7, 33), (1, 1, 1), (3, 5, 2)])
+def test_channel_last_wgrad_odd_width(cuda, fam, n, h, w):
+    """The channel-last weight gradient (the fallback for W % 16 != 0 or H W % 32 != 0, e.g. SalsaNext's lowest level at W = 16 * odd) at
+    odd W, where a pixel pair straddles two rows, and at an odd pixel count, where the last pair has one pixel (1e-4 of the gradient's
+    scale, as test_wgrad_and_dgrad_match_torch_autograd); a dropped last pixel moves dW by ~1 / (N H W) of its scale."""
+    k, dil, pad = fam
+    g = torch.Generator().manual_seed(n * 100 + h * 10 + w + k)
+    cin, cout = 48, 40
+    x = torch.randn(n, cin, h, w, generator=g)
+    wt = (torch.randn(cout, cin, k, k, generator=g) / (cin * k * k) ** 0.5).requires_grad_(True)
+    da = torch.randn(n, cout, h, w, generator=g)
+    F.conv2d(x, wt, None, padding=pad, dilation=dil).backward(da)
+    dw = ops.conv2d_wgrad(ops.nchw_to_nhwc(da.to(cuda)), ops.nchw_to_nhwc(x.to(cuda)), n, h, w, cout, cin, k, dil, pad).cpu()
+    assert _rel(dw, wt.grad) <= 1e-4
+
+
 @pytest.mark.parametrize("chans,cout,n,h,w", [((5,), 32, 2, 8, 40), ((32, 32, 32), 32, 3, 16, 64), ((64, 64, 72), 80, 2, 8, 28),
                                                ((256, 256, 256), 256, 2, 4, 128), ((48,), 40, 1, 4, 8)])
 def test_wgrad_1x1_from_nchw(cuda, chans, cout, n, h, w):
