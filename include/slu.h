@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SLU_ABI_VERSION 31
+#define SLU_ABI_VERSION 32
 
 #define SLU_OK            0
 #define SLU_EINVAL       -1   /* null pointer / non-positive size / inconsistent descriptor   */
@@ -115,7 +115,9 @@ int slu_conv2d_fwd(const slu_conv_desc* desc, slu_stream_t stream);
 /* split-fp16 weight image (bytes) and its packer (w: [cout,cin,k,k] fp32 OIHW) */
 size_t slu_packed_weight_bytes_f16x3(int cout, int cin, int ksize);
 int slu_pack_conv_weight_f16x3(const float* w, int cout, int cin, int ksize, void* out, slu_stream_t stream);
-/* name of the kernel instantiation slu_conv2d_fwd launches for `desc` (as rocprofv3 prints it); HOST buf >= 64 bytes */
+/* Name of the kernel instantiation slu_conv2d_fwd launches for `desc` (as rocprofv3 prints it), into HOST buf (64 bytes hold every name).
+ * The launch's own dispatch with a leaf that prints instead of launching: no HIP call, and the status is the one slu_conv2d_fwd returns
+ * for `desc` (a refused descriptor gets that error, not a name); SLU_EINVAL for a null or too short buf. */
 int slu_conv2d_kernel_name(const slu_conv_desc* desc, char* buf, size_t buflen);
 
 /* a = gamma / sqrt(var + eps), b = beta - mean * a   (eval-mode nn.BatchNorm2d, SalsaNext.py:32,36,...) */
@@ -328,7 +330,8 @@ int slu_pack_conv_weight_h8(const float* w, int cout, int cin, int ksize, void* 
 /* out = [resid +] bn_a * act(conv(cat(src * scale)) + bias) + bn_b, rounded to fp16 once.
  * Families: (k,dil,pad) = (1,1,0), (3,1,1), (3,2,2), (2,2,1) as in slu_conv2d_fwd. */
 int slu_conv2d_h8_fwd(const slu_conv_h8_desc* desc, slu_stream_t stream);
-/* name of the kernel instantiation the call above launches (as rocprofv3 prints it); host only, no launch */
+/* name of the kernel instantiation the call above launches (as rocprofv3 prints it), by the same rules as slu_conv2d_kernel_name
+ * (96 bytes hold every name) */
 int slu_conv2d_h8_kernel_name(const slu_conv_h8_desc* desc, char* buf, size_t n);
 /* fp32 NCHW <-> h8 (set_model_inputs' tensor on the way in, utils/inputs.py:4-34; scale [N][C] optional) */
 int slu_nchw_to_h8(const float* x, const float* scale, void* y, int N, int C, int H, int W, slu_stream_t stream);
@@ -368,6 +371,8 @@ typedef struct slu_conv_tail_h8_desc {   /* HOST struct */
 int slu_conv_tail_h8_supported(int C, int H, int W);
 int slu_conv_tail_h8_shortcut_supported(int C, int sc_cin);
 int slu_conv_tail_h8_fwd(const slu_conv_tail_h8_desc* desc, slu_stream_t stream);
+/* name of the kernel instantiation the call above launches, by the same rules as slu_conv2d_kernel_name */
+int slu_conv_tail_h8_kernel_name(const slu_conv_tail_h8_desc* desc, char* buf, size_t n);
 
 /* Fused ResContextBlock on the h8 path (SalsaNext.py:10-39: conv1 1x1 + act -> shortcut; conv2 3x3 + act + bn1; conv3 3x3 dil 2 +
  * act + bn2; + shortcut), the three full-resolution blocks at the head of the network:

@@ -347,33 +347,49 @@ __global__ void pack_weight_multi_kernel(const slu_pack_job* __restrict__ jobs, 
 // dispatch
 // ---------------------------------------------------------------------------------------------
 template <int KS, int DIL, int PAD, int CK, int MB, int WM, int WN, int RPW, bool GEN>
-int launch_cfg(ConvArgs& a, hipStream_t st) {
+int launch_cfg(ConvArgs& a, const SluEmit& e) {
   constexpr int TH = WN * RPW, MBLK = WM * MB;
   a.tiles_x = (a.W + 63) / 64;
   a.tiles_y = (a.H + TH - 1) / TH;
   const long long gx = (long long)a.tiles_x * a.tiles_y * a.N;
   const int gy = (a.nmblk + MBLK - 1) / MBLK;
   if (gx <= 0 || gx > 0x7fffffffLL || gy > 65535) return SLU_EUNSUPPORTED;
+  if (e.name) return slu_emit_name(e, "conv_fwd_kernel<%d, %d, %d, %d, %d, %d, %d, %d, %s>", KS, DIL, PAD, CK, MB, WM, WN, RPW, slu_tf(GEN));
   hipLaunchKernelGGL((conv_fwd_kernel<KS, DIL, PAD, CK, MB, WM, WN, RPW, GEN>), dim3((unsigned)gx, (unsigned)gy), dim3(64 * WM * WN),
-                     0, st, a, a.resid, a.out);
+                     0, e.st, a, a.resid, a.out);
   SLU_CHECK_LAUNCH();
 }
 
 template <int KS, int DIL, int PAD, int CK, bool GEN>
-int launch_tiles(ConvArgs& a, int cfg, hipStream_t st) {
+int launch_tiles(ConvArgs& a, int cfg, const SluEmit& e) {
   switch (cfg) {
-    case M32_TH8:  return launch_cfg<KS, DIL, PAD, CK, 1, 1, 4, 2, GEN>(a, st);
-    case M64_TH8:  return launch_cfg<KS, DIL, PAD, CK, 2, 1, 4, 2, GEN>(a, st);
-    case M128_TH4: return launch_cfg<KS, DIL, PAD, CK, 2, 2, 2, 2, GEN>(a, st);
-    case M32_TH4:  return launch_cfg<KS, DIL, PAD, CK, 1, 1, 4, 1, GEN>(a, st);
-    case M64_TH4:  return launch_cfg<KS, DIL, PAD, CK, 2, 1, 4, 1, GEN>(a, st);
+    case M32_TH8:  return launch_cfg<KS, DIL, PAD, CK, 1, 1, 4, 2, GEN>(a, e);
+    case M64_TH8:  return launch_cfg<KS, DIL, PAD, CK, 2, 1, 4, 2, GEN>(a, e);
+    case M128_TH4: return launch_cfg<KS, DIL, PAD, CK, 2, 2, 2, 2, GEN>(a, e);
+    case M32_TH4:  return launch_cfg<KS, DIL, PAD, CK, 1, 1, 4, 1, GEN>(a, e);
+    case M64_TH4:  return launch_cfg<KS, DIL, PAD, CK, 2, 1, 4, 1, GEN>(a, e);
   }
   return SLU_EUNSUPPORTED;
 }
 
 template <int KS, int DIL, int PAD, int CK>
-int launch_family(ConvArgs& a, int cfg, hipStream_t st) {
-  return a.gen ? launch_tiles<KS, DIL, PAD, CK, true>(a, cfg, st) : launch_tiles<KS, DIL, PAD, CK, false>(a, cfg, st);
+int launch_family(ConvArgs& a, int cfg, const SluEmit& e) {
+  return a.gen ? launch_tiles<KS, DIL, PAD, CK, true>(a, cfg, e) : launch_tiles<KS, DIL, PAD, CK, false>(a, cfg, e);
+}
+
+// the one traversal of the forward dispatch: slu_conv2d_fwd launches at its leaf, slu_conv2d_kernel_name has the leaf name itself
+int conv_dispatch(const slu_conv_desc* d, const SluEmit& e) {
+  if (d && d->precision == SLU_CONV_F16X3) return slu_conv2d_f16x3_dispatch(d, e);
+  ConvArgs a{};
+  const int rc = fill_args(d, a);
+  if (rc != SLU_OK) return rc;
+  const int cfg = choose_cfg(a);
+  if (d->ksize == 1 && d->dil == 1 && d->pad == 0) return launch_family<1, 1, 0, 16>(a, cfg, e);
+  if (d->ksize == 3 && d->dil == 1 && d->pad == 1) return launch_family<3, 1, 1, 8>(a, cfg, e);
+  if (d->ksize == 3 && d->dil == 2 && d->pad == 2) return launch_family<3, 2, 2, 8>(a, cfg, e);
+  if (d->ksize == 2 && d->dil == 2 && d->pad == 1) return launch_family<2, 2, 1, 8>(a, cfg, e);
+  if (d->ksize == 2 && d->dil == 1 && d->pad == 1) return launch_family<2, 1, 1, 8>(a, cfg, e);
+  return SLU_EUNSUPPORTED;
 }
 
 }  // namespace
@@ -411,44 +427,9 @@ extern "C" int slu_conv_prof_read(unsigned long long* out8) {      // copies and
 }
 #endif
 
-int slu_conv2d_fwd_f16x3_impl(const slu_conv_desc* d, hipStream_t st);   // conv2d_f16x3.hip
+extern "C" int slu_conv2d_fwd(const slu_conv_desc* d, slu_stream_t stream) { return conv_dispatch(d, SluEmit{slu_stream(stream), nullptr, 0}); }
 
-extern "C" int slu_conv2d_fwd(const slu_conv_desc* d, slu_stream_t stream) {
-  if (d && d->precision == SLU_CONV_F16X3) return slu_conv2d_fwd_f16x3_impl(d, slu_stream(stream));
-  ConvArgs a{};
-  const int rc = fill_args(d, a);
-  if (rc != SLU_OK) return rc;
-  const int cfg = choose_cfg(a);
-  hipStream_t st = slu_stream(stream);
-  if (d->ksize == 1 && d->dil == 1 && d->pad == 0) return launch_family<1, 1, 0, 16>(a, cfg, st);
-  if (d->ksize == 3 && d->dil == 1 && d->pad == 1) return launch_family<3, 1, 1, 8>(a, cfg, st);
-  if (d->ksize == 3 && d->dil == 2 && d->pad == 2) return launch_family<3, 2, 2, 8>(a, cfg, st);
-  if (d->ksize == 2 && d->dil == 2 && d->pad == 1) return launch_family<2, 2, 1, 8>(a, cfg, st);
-  if (d->ksize == 2 && d->dil == 1 && d->pad == 1) return launch_family<2, 1, 1, 8>(a, cfg, st);
-  return SLU_EUNSUPPORTED;
-}
-
-// Template arguments of the instantiation slu_conv2d_fwd would launch for this descriptor, in the
-// order rocprofv3 prints them: "conv_fwd_kernel<KS, DIL, PAD, CK, MB, WM, WN, RPW>".
+// name of the kernel instantiation slu_conv2d_fwd launches for `d` (as rocprofv3 prints it), or the status with which it refuses `d`
 extern "C" int slu_conv2d_kernel_name(const slu_conv_desc* d, char* buf, size_t buflen) {
-  if (!buf || buflen < 64) return SLU_EINVAL;
-  ConvArgs a{};
-  const int rc = fill_args(d, a);
-  if (rc != SLU_OK) return rc;
-  static const int kTile[5][4] = {{1, 1, 4, 2}, {2, 1, 4, 2}, {2, 2, 2, 2}, {1, 1, 4, 1}, {2, 1, 4, 1}};
-  int cfg = choose_cfg(a);
-  if (d->precision == SLU_CONV_F16X3 && cfg == M32_TH8) cfg = M32_TH4;
-  if (d->precision == SLU_CONV_F16X3 && cfg == M64_TH8) cfg = M64_TH4;
-  const int* t = kTile[cfg];
-  if (d->precision == SLU_CONV_F16X3 && d->ksize == 1 && !a.gen && a.nmblk <= 8 && ((long long)a.H * a.W) % 32 == 0 &&
-      (a.nsrc < 2 || a.src[0].ccount % 16 == 0) && (a.nsrc < 3 || a.src[1].ccount % 16 == 0)) {
-    const int mb = a.nmblk == 1 ? 1 : (a.nmblk == 2 ? 2 : (a.nmblk <= 4 ? 4 : 8));
-    snprintf(buf, buflen, "conv1x1_f16x3_kernel<%d, %d>", mb, 1);
-    return SLU_OK;
-  }
-  if (d->precision == SLU_CONV_F16X3)
-    snprintf(buf, buflen, "conv_f16x3_kernel<%d, %d, %d, %d, %d, %d, %d, %s>", d->ksize, d->dil, d->pad, t[0], t[1], t[2], t[3], a.gen ? "true" : "false");
-  else
-    snprintf(buf, buflen, "conv_fwd_kernel<%d, %d, %d, %d, %d, %d, %d, %d, %s>", d->ksize, d->dil, d->pad, d->ck, t[0], t[1], t[2], t[3], a.gen ? "true" : "false");
-  return SLU_OK;
+  return buf ? conv_dispatch(d, SluEmit{nullptr, buf, buflen}) : SLU_EINVAL;
 }

@@ -451,15 +451,16 @@ __global__ __launch_bounds__(256, (MB * NBW >= 8) ? 2 : ((MB * NBW >= 4) ? 3 : 4
 }
 
 template <int MB, int NBW>
-int launch_1x1(ConvArgs& a, hipStream_t st) {
+int launch_1x1(ConvArgs& a, const SluEmit& e) {
   constexpr size_t lds = (size_t)2 * MB * 4 * 64 * 16 + (size_t)3 * MB * 32 * 4;
   const long long nblocks = (long long)a.N * a.H * a.W / 32;
   const long long gx = (nblocks + 4 * NBW - 1) / (4 * NBW);
   if (gx <= 0 || gx > 0x7fffffffLL) return SLU_EUNSUPPORTED;
+  if (e.name) return slu_emit_name(e, "conv1x1_f16x3_kernel<%d, %d>", MB, NBW);
   auto kern = conv1x1_f16x3_kernel<MB, NBW>;
   static SluLdsGrant grant;
   if (slu_grant_dynamic_lds(reinterpret_cast<const void*>(kern), lds, grant) != SLU_OK) return SLU_ELAUNCH;
-  hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(256), lds, st, a, a.resid, a.out);
+  hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(256), lds, e.st, a, a.resid, a.out);
   SLU_CHECK_LAUNCH();
 }
 
@@ -472,11 +473,11 @@ bool stream_1x1_ok(const slu_conv_desc* d, const ConvArgs& a) {
   return true;
 }
 
-int launch_1x1_any(ConvArgs& a, hipStream_t st) {
-  if (a.nmblk == 1) return launch_1x1<1, 1>(a, st);
-  if (a.nmblk == 2) return launch_1x1<2, 1>(a, st);
-  if (a.nmblk <= 4) return launch_1x1<4, 1>(a, st);
-  return launch_1x1<8, 1>(a, st);
+int launch_1x1_any(ConvArgs& a, const SluEmit& e) {
+  if (a.nmblk == 1) return launch_1x1<1, 1>(a, e);
+  if (a.nmblk == 2) return launch_1x1<2, 1>(a, e);
+  if (a.nmblk <= 4) return launch_1x1<4, 1>(a, e);
+  return launch_1x1<8, 1>(a, e);
 }
 
 // wpack16[mblk][chunk][tap][hi|lo][lane][8]: lane (r, h) holds W[co = 32 mblk + r][ci = 16 chunk + 8 h + j][tap], j = 0..7
@@ -506,7 +507,7 @@ __global__ void pack_f16x3_kernel(const float* __restrict__ w, int cout, int cin
 }
 
 template <int KS, int DIL, int PAD, int MB, int WM, int WN, int RPW, bool GEN>
-int launch_cfg16(ConvArgs& a, hipStream_t st) {
+int launch_cfg16(ConvArgs& a, const SluEmit& e) {
   constexpr int TH = WN * RPW, MBLK = WM * MB, T = KS * KS, XO = PAD ? 4 : 0;
   constexpr int REC = (TH + 2 * PAD) * ((64 + 2 * XO) + (64 + 2 * XO) / 8);
   constexpr size_t lds = (size_t)4 * REC * 16 + (size_t)2 * MBLK * T * 64 * 16 + (size_t)3 * MBLK * 32 * 4;
@@ -516,28 +517,29 @@ int launch_cfg16(ConvArgs& a, hipStream_t st) {
   const long long gx = (long long)a.tiles_x * a.tiles_y * a.N;
   const int gy = (a.nmblk + MBLK - 1) / MBLK;
   if (gx <= 0 || gx > 0x7fffffffLL || gy > 65535) return SLU_EUNSUPPORTED;
+  if (e.name) return slu_emit_name(e, "conv_f16x3_kernel<%d, %d, %d, %d, %d, %d, %d, %s>", KS, DIL, PAD, MB, WM, WN, RPW, slu_tf(GEN));
   auto kern = conv_f16x3_kernel<KS, DIL, PAD, MB, WM, WN, RPW, GEN>;
   static SluLdsGrant grant;
   if (slu_grant_dynamic_lds(reinterpret_cast<const void*>(kern), lds, grant) != SLU_OK) return SLU_ELAUNCH;
-  hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)gy), dim3(64 * WM * WN), lds, st, a, a.resid, a.out);
+  hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)gy), dim3(64 * WM * WN), lds, e.st, a, a.resid, a.out);
   SLU_CHECK_LAUNCH();
 }
 
 template <int KS, int DIL, int PAD, bool GEN>
-int launch_tiles16(ConvArgs& a, int cfg, hipStream_t st) {
+int launch_tiles16(ConvArgs& a, int cfg, const SluEmit& e) {
   switch (cfg) {
-    case M32_TH8:  return launch_cfg16<KS, DIL, PAD, 1, 1, 4, 2, GEN>(a, st);
-    case M64_TH8:  return launch_cfg16<KS, DIL, PAD, 2, 1, 4, 2, GEN>(a, st);
-    case M128_TH4: return launch_cfg16<KS, DIL, PAD, 2, 2, 2, 2, GEN>(a, st);
-    case M32_TH4:  return launch_cfg16<KS, DIL, PAD, 1, 1, 4, 1, GEN>(a, st);
-    case M64_TH4:  return launch_cfg16<KS, DIL, PAD, 2, 1, 4, 1, GEN>(a, st);
+    case M32_TH8:  return launch_cfg16<KS, DIL, PAD, 1, 1, 4, 2, GEN>(a, e);
+    case M64_TH8:  return launch_cfg16<KS, DIL, PAD, 2, 1, 4, 2, GEN>(a, e);
+    case M128_TH4: return launch_cfg16<KS, DIL, PAD, 2, 2, 2, 2, GEN>(a, e);
+    case M32_TH4:  return launch_cfg16<KS, DIL, PAD, 1, 1, 4, 1, GEN>(a, e);
+    case M64_TH4:  return launch_cfg16<KS, DIL, PAD, 2, 1, 4, 1, GEN>(a, e);
   }
   return SLU_EUNSUPPORTED;
 }
 
 template <int KS, int DIL, int PAD>
-int launch_family16(ConvArgs& a, int cfg, hipStream_t st) {
-  return a.gen ? launch_tiles16<KS, DIL, PAD, true>(a, cfg, st) : launch_tiles16<KS, DIL, PAD, false>(a, cfg, st);
+int launch_family16(ConvArgs& a, int cfg, const SluEmit& e) {
+  return a.gen ? launch_tiles16<KS, DIL, PAD, true>(a, cfg, e) : launch_tiles16<KS, DIL, PAD, false>(a, cfg, e);
 }
 
 }  // namespace
@@ -560,20 +562,20 @@ extern "C" int slu_pack_conv_weight_f16x3(const float* w, int cout, int cin, int
   SLU_CHECK_LAUNCH();
 }
 
-// called by slu_conv2d_fwd (conv2d.hip) when desc->precision == SLU_CONV_F16X3
-int slu_conv2d_fwd_f16x3_impl(const slu_conv_desc* d, hipStream_t st) {
+// the split-fp16 branch of conv2d.hip's conv_dispatch (desc->precision == SLU_CONV_F16X3)
+int slu_conv2d_f16x3_dispatch(const slu_conv_desc* d, const SluEmit& e) {
   ConvArgs a{};
   const int rc = fill_args(d, a);
   if (rc != SLU_OK) return rc;
-  if (stream_1x1_ok(d, a)) return launch_1x1_any(a, st);
+  if (stream_1x1_ok(d, a)) return launch_1x1_any(a, e);
   int cfg = choose_cfg(a);
   // 4-row tiles only: the (hi, lo) input tile of an 8-row tile leaves room for a single workgroup per CU
   if (cfg == M32_TH8) cfg = M32_TH4;
   if (cfg == M64_TH8) cfg = M64_TH4;
-  if (d->ksize == 1 && d->dil == 1 && d->pad == 0) return launch_family16<1, 1, 0>(a, cfg, st);
-  if (d->ksize == 3 && d->dil == 1 && d->pad == 1) return launch_family16<3, 1, 1>(a, cfg, st);
-  if (d->ksize == 3 && d->dil == 2 && d->pad == 2) return launch_family16<3, 2, 2>(a, cfg, st);
-  if (d->ksize == 2 && d->dil == 2 && d->pad == 1) return launch_family16<2, 2, 1>(a, cfg, st);
-  if (d->ksize == 2 && d->dil == 1 && d->pad == 1) return launch_family16<2, 1, 1>(a, cfg, st);
+  if (d->ksize == 1 && d->dil == 1 && d->pad == 0) return launch_family16<1, 1, 0>(a, cfg, e);
+  if (d->ksize == 3 && d->dil == 1 && d->pad == 1) return launch_family16<3, 1, 1>(a, cfg, e);
+  if (d->ksize == 3 && d->dil == 2 && d->pad == 2) return launch_family16<3, 2, 2>(a, cfg, e);
+  if (d->ksize == 2 && d->dil == 2 && d->pad == 1) return launch_family16<2, 2, 1>(a, cfg, e);
+  if (d->ksize == 2 && d->dil == 1 && d->pad == 1) return launch_family16<2, 1, 1>(a, cfg, e);
   return SLU_EUNSUPPORTED;
 }

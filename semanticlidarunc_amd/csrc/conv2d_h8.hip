@@ -56,7 +56,9 @@ struct H8Args {
   int out_f32;         // 1: `out` is fp32 NCHW [N][Cout][H][W] (the logits head); 0: h8
   int tiles_x, tiles_y;
   int order;                 // 0: each workgroup walks a contiguous run of tiles; 1: tiles interleaved across workgroups
-  int dbg;                   // development switches of gemm1x1_h8_kernel (SLU_GEMM_DBG): 1 no input DMA, 2 no weight DMA, 4 no MFMA
+#ifdef SLU_H8_AB
+  int dbg;                   // ablation switches of gemm1x1_h8_kernel (SLU_GEMM_DBG, -DSLU_H8_AB builds only): 1 no input DMA, 2 no weight DMA, 4 no MFMA
+#endif
 };
 
 struct SrcSel {
@@ -247,8 +249,11 @@ __device__ unsigned long long g_h8_prof[8];
 // wait + barrier instead of after; 8 = whole 16-byte records per lane on the way out (v_permlane32_swap).
 // ONE: the layer has ONE plain source (no concatenation, no batch broadcast): the staging set-up of a chunk is one 64-bit multiply-add on
 // the scalar unit instead of the source-selection chains of the general form.
+// waves per SIMD the registers allow: the kernel's __launch_bounds__ and launch_h8_k's persistent grid
+constexpr int h8_waves_per_simd(int mb, int nwave, int rpw) { return (mb * rpw >= 8) ? 1 : ((nwave >= 8 || mb >= 2 || rpw >= 2) ? 2 : 3); }
+
 template <int KS, int DIL, int PAD, int MB, int WM, int WN, int RPW, bool SCALED, bool WRES, bool F32OUT, int KPC = 1, int OPT = 0, bool ONE = false>
-__global__ __launch_bounds__(64 * WM * WN, (MB * RPW >= 8) ? 1 : ((WM * WN >= 8 || MB >= 2 || RPW >= 2) ? 2 : 3)) void conv_h8_kernel(const H8Args a, const void* __restrict__ resid,
+__global__ __launch_bounds__(64 * WM * WN, h8_waves_per_simd(MB, WM * WN, RPW)) void conv_h8_kernel(const H8Args a, const void* __restrict__ resid,
                                                                                                        void* __restrict__ out) {
   constexpr int NWAVE = WM * WN;
   constexpr int T = KS * KS, TS = KPC * T;          // taps per K-step, tap-steps per chunk
@@ -542,14 +547,6 @@ __global__ __launch_bounds__(64 * WM * WN, (MB * RPW >= 8) ? 1 : ((WM * WN >= 8 
           auto read_frags = [&](int set, int ts) __attribute__((always_inline)) {
             const int j = ts / T, tap = ts % T;          // K-step of the chunk, tap
             const int dy = (tap / KS) * DIL, dx = (tap % KS) * DIL;
-#ifdef SLU_H8_FAKE_LDS      // experiment (WRONG results): a quarter of the fragment reads, the same MFMAs -- does LDS traffic limit these layers?
-            af[set][0] = __builtin_bit_cast(half8, sa[ts * 64]);
-            bf[set][0] = __builtin_bit_cast(half8, sb[j * 2 * REC + dy * LW + dx]);
-#pragma unroll
-            for (int i = 1; i < MB; ++i) af[set][i] = af[set][0];
-#pragma unroll
-            for (int b = 1; b < NB; ++b) bf[set][b] = bf[set][0];
-#else
 #pragma unroll
             for (int i = 0; i < MB; ++i) af[set][i] = __builtin_bit_cast(half8, sa[i * a_stride + ts * 64]);
 #pragma unroll
@@ -557,7 +554,6 @@ __global__ __launch_bounds__(64 * WM * WN, (MB * RPW >= 8) ? 1 : ((WM * WN >= 8 
               bf[set][b] = __builtin_bit_cast(half8, sb[j * 2 * REC + ((b >> 1) + dy) * LW + (b & 1) * 32 + dx]);
               if constexpr (SCALED) bf[set][b] *= sc;
             }
-#endif
           };
           read_frags(0, 0);
 #pragma unroll
@@ -803,8 +799,11 @@ __global__ __launch_bounds__(256, (MB * NBW >= 8) ? 2 : ((MB * NBW >= 4) ? 3 : 4
 // 512-byte runs per wave) and the residual loads at once, and multiplies as they arrive.  Memory-level parallelism
 // comes from occupancy (4-5 waves per SIMD, up to NKS KB in flight per wave); LDS only serves the A fragments.
 // -----------------------------------------------------------------------------------------------------------
+// 4-wave workgroups per CU (= waves per SIMD) the registers allow: the kernel's __launch_bounds__ and launch_h8_1x1_res's grid
+constexpr int h8_1x1_res_waves_per_simd(int mb, int nks) { return (mb * nks >= 12) ? 2 : ((mb * nks >= 2) ? 3 : 4); }
+
 template <int MB, int NKS>
-__global__ __launch_bounds__(256, (MB * NKS >= 12) ? 2 : ((MB * NKS >= 2) ? 3 : 4)) void conv1x1_h8_res_kernel(const H8Args a, const void* __restrict__ resid, void* __restrict__ out) {
+__global__ __launch_bounds__(256, h8_1x1_res_waves_per_simd(MB, NKS)) void conv1x1_h8_res_kernel(const H8Args a, const void* __restrict__ resid, void* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* s_epi = reinterpret_cast<float*>(smem);                 // bias | bn_a | bn_b
   uint4* s_a = reinterpret_cast<uint4*>(s_epi + 3 * MB * 32);    // [MB][NKS][64]
@@ -906,7 +905,7 @@ __global__ __launch_bounds__(256, (MB * NKS >= 12) ? 2 : ((MB * NKS >= 2) ? 3 : 
 // pixels (the streaming conv1x1_h8_kernel re-reads them per 128 and stages them through registers + two barriers per 64 channels).
 // Measured (N = 64, tools/h8_1x1_bench.py): 768 -> 256 at 16x512 504 -> 459 us, 128 -> 256 at 16x512 117 -> 96, 256 -> 256 at 8x256 46 -> 38; the
 // 128-output instantiation is 17 % SLOWER than the streaming kernel (544 -> 634 us at 32x1024) and is not dispatched.  What the ablation
-// switches (H8Args.dbg / SLU_GEMM_DBG) showed on 768 -> 256: no input DMA 399 us, no weight DMA 413, no MFMA 354, none of the three STILL 306 of
+// switches (SLU_GEMM_DBG in -DSLU_H8_AB builds) showed on 768 -> 256: no input DMA 399 us, no weight DMA 413, no MFMA 354, none of the three STILL 306 of
 // 481 -- the time is in the per-chunk skeleton (32 DMA instructions per CU and chunk, barrier, fragment reads) and the epilogue, not in HBM,
 // L2 or the matrix cores; a deeper ring of smaller chunks (KC 2, D 4) was slower (484) than two 64-channel chunks (459).
 // With a residual the epilogue's loads drain the ring once per tile (the compiler's vmcnt(0)); without, the stores stay in flight.
@@ -966,14 +965,14 @@ __global__ __launch_bounds__(512, 2) void gemm1x1_h8_kernel(const H8Args a, cons
 #pragma unroll
     for (int i = 0; i < NIB; ++i) {
       const int p = i * NWAVE + wv;                                      // block = p / 4, pixel quarter = p % 4
-      const uintptr_t src = (valid && !(a.dbg & 1)) ? base + 16 * ((size_t)(p >> 2) * HW + (size_t)((p & 3) * 64 + lane)) : zero_addr;
+      const uintptr_t src = (valid && !SLU_ABLATE(a, 1)) ? base + 16 * ((size_t)(p >> 2) * HW + (size_t)((p & 3) * 64 + lane)) : zero_addr;
       SLU_GLDS16(reinterpret_cast<const uint4*>(src), db + p * 64);
     }
 #pragma unroll
     for (int i = 0; i < NIA; ++i) {
       const int p = i * NWAVE + wv;                                      // = m * KC + ks
       const int m = p / KC, ks = p - m * KC;
-      const uint4* src = (valid && !(a.dbg & 2)) ? a.wpack + ((size_t)m * a.nks + KC * s_q + ks) * 64 + lane : reinterpret_cast<const uint4*>(zero_addr);
+      const uint4* src = (valid && !SLU_ABLATE(a, 2)) ? a.wpack + ((size_t)m * a.nks + KC * s_q + ks) * 64 + lane : reinterpret_cast<const uint4*>(zero_addr);
       SLU_GLDS16(src, da + p * 64);
     }
     asm volatile("" ::: "memory");
@@ -1020,7 +1019,7 @@ __global__ __launch_bounds__(512, 2) void gemm1x1_h8_kernel(const H8Args a, cons
       for (int ks = 0; ks < KC; ++ks) {
         if (ks + 1 < KC) read_frags((ks + 1) & 1, ks + 1);
         __builtin_amdgcn_sched_barrier(0);
-        if (!(a.dbg & 4)) {
+        if (!SLU_ABLATE(a, 4)) {
 #pragma unroll
           for (int b = 0; b < NB; ++b)
 #pragma unroll
@@ -1228,14 +1227,16 @@ int fill_h8(const slu_conv_h8_desc* d, H8Args& a) {
   a.has_act = d->has_act; a.slope = d->slope;
   a.out_f32 = d->out_f32_nchw ? 1 : 0;
   a.tiles_x = a.tiles_y = 0;
-  a.dbg = [] { const char* e = getenv("SLU_GEMM_DBG"); return e ? atoi(e) : 0; }();
+#ifdef SLU_H8_AB
+  static const int dbg = [] { const char* e = getenv("SLU_GEMM_DBG"); return e ? atoi(e) : 0; }();
+  a.dbg = dbg;
+#endif
   return SLU_OK;
 }
 
 template <int KS, int DIL, int PAD, int MB, int WM, int WN, int RPW, bool SCALED, bool WRES, bool F32OUT = false, int KPC = 1, int OPT = 0, bool ONE = false>
-int launch_h8_k(H8Args& a, const slu_conv_h8_desc* d, hipStream_t st) {
+int launch_h8_k(H8Args& a, const slu_conv_h8_desc* d, const SluEmit& e) {
   constexpr int TH = WN * RPW, MBLK = WM * MB, T = KS * KS, NWAVE = WM * WN;
-  constexpr int WAVES_PER_SIMD = (MB * RPW >= 8) ? 1 : ((NWAVE >= 8 || MB >= 2 || RPW >= 2) ? 2 : 3);       // the kernel's __launch_bounds__
   constexpr size_t nb_alloc = (size_t)((KPC * 2 * (TH + 2 * PAD) * (64 + 2 * PAD) + 63) / 64) * 64;
   const size_t lds = (size_t)3 * MBLK * 32 * 4 + (SCALED ? 2048 : 0) + 2 * nb_alloc * 16 + (size_t)MBLK * (WRES ? a.nks : 2 * KPC) * T * 64 * 16;
   if (lds > 160 * 1024) return SLU_EUNSUPPORTED;
@@ -1247,8 +1248,11 @@ int launch_h8_k(H8Args& a, const slu_conv_h8_desc* d, hipStream_t st) {
   const long long nt = (long long)a.tiles_x * a.tiles_y * a.N;
   const int gy = (a.nmblk + MBLK - 1) / MBLK;
   if (nt <= 0 || nt > 0x7fffffffLL || gy > 65535) return SLU_EUNSUPPORTED;
+  if (e.name)
+    return slu_emit_name(e, "conv_h8_kernel<%d, %d, %d, %d, %d, %d, %d, %s, %s, %s, %d, %d, %s>", KS, DIL, PAD, MB, WM, WN, RPW, slu_tf(SCALED),
+                         slu_tf(WRES), slu_tf(F32OUT), KPC, OPT, slu_tf(ONE));
   // persistent grid: as many workgroups as fit on the 256 CUs at once (registers / LDS), never more than tiles
-  long long per_cu = WAVES_PER_SIMD * 4 / NWAVE;
+  long long per_cu = h8_waves_per_simd(MB, NWAVE, RPW) * 4 / NWAVE;
   const long long by_lds = (long long)(160 * 1024 / lds);
   if (by_lds < per_cu) per_cu = by_lds;
   if (per_cu < 1) per_cu = 1;
@@ -1258,7 +1262,7 @@ int launch_h8_k(H8Args& a, const slu_conv_h8_desc* d, hipStream_t st) {
   auto kern = conv_h8_kernel<KS, DIL, PAD, MB, WM, WN, RPW, SCALED, WRES, F32OUT, KPC, OPT, ONE>;
   static SluLdsGrant grant;
   if (slu_grant_dynamic_lds(reinterpret_cast<const void*>(kern), lds, grant) != SLU_OK) return SLU_ELAUNCH;
-  hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)gy), dim3(64 * NWAVE), lds, st, a, d->resid, d->out);
+  hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)gy), dim3(64 * NWAVE), lds, e.st, a, d->resid, d->out);
   SLU_CHECK_LAUNCH();
 }
 
@@ -1478,7 +1482,7 @@ __global__ __launch_bounds__(512, 2) void ring3_h8_kernel(const RingArgs a) {
 }
 
 template <int DIL, int MB, int NKS, int RPW, int D>
-int launch_ring3(const H8Args& h, const slu_conv_h8_desc* d, hipStream_t st) {
+int launch_ring3(const H8Args& h, const slu_conv_h8_desc* d, const SluEmit& e) {
   constexpr int TH = 8 * RPW, PAD = DIL;
   constexpr size_t nblk_b = (size_t)(2 * (TH + 2 * PAD) * (64 + 2 * PAD) + 63) / 64;
   constexpr size_t lds = ((size_t)MB * NKS * 9 * 64 + (size_t)D * nblk_b * 64 + 64) * 16;      // + 3 * 32 MB floats static
@@ -1493,54 +1497,49 @@ int launch_ring3(const H8Args& h, const slu_conv_h8_desc* d, hipStream_t st) {
   a.tiles_x = (a.W + 63) / 64;
   a.tiles_y = (a.H + TH - 1) / TH;
   const long long nt = (long long)a.tiles_x * a.tiles_y * a.N;
-  if (nt <= 0 || nt > 0x7fffffffLL) return SLU_EUNSUPPORTED;
-  long long gx = 256;
-  if (gx > nt) gx = nt;
+  if (nt < 256) return -1;      // too few tiles to fill the chip: the tiled kernel
+  if (nt > 0x7fffffffLL) return SLU_EUNSUPPORTED;
+  if (e.name) return slu_emit_name(e, "ring3_h8_kernel<%d, %d, %d, %d, %d>", DIL, MB, NKS, RPW, D);
   auto kern = ring3_h8_kernel<DIL, MB, NKS, RPW, D>;
   static SluLdsGrant grant;
   if (slu_grant_dynamic_lds(reinterpret_cast<const void*>(kern), lds, grant) != SLU_OK) return SLU_ELAUNCH;
-  hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(512), lds, st, a);
+  hipLaunchKernelGGL(kern, dim3(256), dim3(512), lds, e.st, a);
   SLU_CHECK_LAUNCH();
 }
 
-// the layers ring3_h8_kernel covers: 3x3 (dil 1 / 2), one plain source of exactly 32 / 64 channels, 32 / 64 output channels, h8 output,
-// no residual, activation before BN only, and enough tiles to fill the chip.  Returns the instantiation's name, or nullptr.
-const char* ring3_name(const slu_conv_h8_desc* d, const H8Args& a, char* buf, size_t n) {
+// the layers ring3_h8_kernel covers: 3x3 (dil 1 / 2), one or two plain sources of 32 / 64 (80 -> 32: dil 1) channels in all, 32 / 64 output
+// channels, h8 output, no residual, activation before BN only
+bool ring3_ok(const slu_conv_h8_desc* d, const H8Args& a) {
   static const bool off = [] { const char* e = getenv("SLU_H8_RING3"); return e && e[0] == '0'; }();      // A/B switch
-  if (off || d->ksize != 3 || d->pad != d->dil || (d->dil != 1 && d->dil != 2) || a.nsrc < 1 || a.nsrc > 2) return nullptr;
+  if (off || d->ksize != 3 || d->pad != d->dil || (d->dil != 1 && d->dil != 2) || a.nsrc < 1 || a.nsrc > 2) return false;
   int gsum = 0;
   for (int s = 0; s < a.nsrc; ++s) {
-    if (a.src[s].scale || a.src[s].nb) return nullptr;
+    if (a.src[s].scale || a.src[s].nb) return false;
     gsum += a.src[s].G;
   }
-  if (gsum != a.Gin || (a.nsrc == 2 && (a.src[0].G & 1)) || a.out_f32 || d->resid || (a.has_act & ~1)) return nullptr;
-  if ((a.has_act & 1) && !(a.slope >= 0.0f && a.slope <= 1.0f)) return nullptr;      // LeakyReLU as max(t, slope t)
-  const int mb = a.Cout / 32, nks = a.Gin / 2;
-  const bool shape = (a.Cout == 32 || a.Cout == 64) && ((a.Gin == 4 || a.Gin == 8) || (a.Gin == 10 && a.Cout == 32 && d->dil == 1));
-  if (!shape) return nullptr;
-  const int rpw = (mb * nks >= 5 || (d->dil == 2 && mb * nks == 4)) ? 1 : 2;      // 16-row tiles where weights + the ring fit in LDS
-  if ((long long)a.N * ((a.H + 8 * rpw - 1) / (8 * rpw)) * ((a.W + 63) / 64) < 256) return nullptr;
-  snprintf(buf, n, "ring3_h8_kernel<%d, %d, %d, %d, %d>", d->dil, mb, nks, rpw, nks == 5 ? 4 : 3);
-  return buf;
+  if (gsum != a.Gin || (a.nsrc == 2 && (a.src[0].G & 1)) || a.out_f32 || d->resid || (a.has_act & ~1)) return false;
+  if ((a.has_act & 1) && !(a.slope >= 0.0f && a.slope <= 1.0f)) return false;      // LeakyReLU as max(t, slope t)
+  return (a.Cout == 32 || a.Cout == 64) && ((a.Gin == 4 || a.Gin == 8) || (a.Gin == 10 && a.Cout == 32 && d->dil == 1));
 }
 
-int launch_ring3_any(const H8Args& a, const slu_conv_h8_desc* d, hipStream_t st) {
+// <DIL, MB, NKS, RPW, D>: 16-row tiles (RPW 2) where the weights and the ring fit in LDS; -1 when the layer has fewer than 256 tiles of that height
+int launch_ring3_any(const H8Args& a, const slu_conv_h8_desc* d, const SluEmit& e) {
   const int mb = a.Cout / 32, nks = a.Gin / 2;
-  if (nks == 5) return launch_ring3<1, 1, 5, 1, 4>(a, d, st);                       // 80 -> 32: PixelShuffle output | skip (UpBlock.conv1, full resolution)
-  if (mb == 2 && nks == 4) return d->dil == 1 ? launch_ring3<1, 2, 4, 1, 3>(a, d, st) : launch_ring3<2, 2, 4, 1, 3>(a, d, st);
-  if (mb == 2 && nks == 2) return d->dil == 1 ? launch_ring3<1, 2, 2, 2, 3>(a, d, st) : launch_ring3<2, 2, 2, 1, 3>(a, d, st);
-  if (mb == 1 && nks == 4) return d->dil == 1 ? launch_ring3<1, 1, 4, 2, 3>(a, d, st) : launch_ring3<2, 1, 4, 1, 3>(a, d, st);
-  return d->dil == 1 ? launch_ring3<1, 1, 2, 2, 3>(a, d, st) : launch_ring3<2, 1, 2, 2, 3>(a, d, st);
+  if (nks == 5) return launch_ring3<1, 1, 5, 1, 4>(a, d, e);                       // 80 -> 32: PixelShuffle output | skip (UpBlock.conv1, full resolution)
+  if (mb == 2 && nks == 4) return d->dil == 1 ? launch_ring3<1, 2, 4, 1, 3>(a, d, e) : launch_ring3<2, 2, 4, 1, 3>(a, d, e);
+  if (mb == 2 && nks == 2) return d->dil == 1 ? launch_ring3<1, 2, 2, 2, 3>(a, d, e) : launch_ring3<2, 2, 2, 1, 3>(a, d, e);
+  if (mb == 1 && nks == 4) return d->dil == 1 ? launch_ring3<1, 1, 4, 2, 3>(a, d, e) : launch_ring3<2, 1, 4, 1, 3>(a, d, e);
+  return d->dil == 1 ? launch_ring3<1, 1, 2, 2, 3>(a, d, e) : launch_ring3<2, 1, 2, 2, 3>(a, d, e);
 }
 
 constexpr size_t WRES_MAX_BYTES = 24 * 1024;
 
 // weights of all K-steps stay resident in LDS when they are small (full-resolution 32-channel layers)
 template <int KS, int DIL, int PAD, int MB, int WM, int WN, int RPW, bool SCALED>
-int launch_h8(H8Args& a, const slu_conv_h8_desc* d, hipStream_t st) {
+int launch_h8(H8Args& a, const slu_conv_h8_desc* d, const SluEmit& e) {
   const size_t wbytes = (size_t)WM * MB * a.nks * KS * KS * 64 * 16;
-  if (wbytes <= WRES_MAX_BYTES) return launch_h8_k<KS, DIL, PAD, MB, WM, WN, RPW, SCALED, true>(a, d, st);
-  return launch_h8_k<KS, DIL, PAD, MB, WM, WN, RPW, SCALED, false>(a, d, st);
+  if (wbytes <= WRES_MAX_BYTES) return launch_h8_k<KS, DIL, PAD, MB, WM, WN, RPW, SCALED, true>(a, d, e);
+  return launch_h8_k<KS, DIL, PAD, MB, WM, WN, RPW, SCALED, false>(a, d, e);
 }
 
 inline long long wg_count(const H8Args& a, int th, int mblk) {
@@ -1550,7 +1549,6 @@ inline long long wg_count(const H8Args& a, int th, int mblk) {
 // tile configurations {MB, WM, WN, RPW}: 8-wave workgroups (16 or 8 rows) when the layer has enough tiles for
 // every CU, 4-wave ones with 8 / 4 rows for the small feature maps at the bottom of the U-Net
 enum { CFG_M32_TH16 = 0, CFG_M64_TH16, CFG_M128_TH8, CFG_M32_TH8, CFG_M64_TH8, CFG_M128_TH4, CFG_M32_TH4, CFG_M64_TH4, CFG_COUNT };
-const int CFG_TABLE[CFG_COUNT][4] = {{1, 1, 8, 2}, {2, 1, 8, 2}, {2, 2, 4, 2}, {1, 1, 4, 2}, {2, 1, 4, 2}, {2, 2, 2, 2}, {1, 1, 4, 1}, {2, 1, 4, 1}};
 
 int choose_h8(const H8Args& a) {
   const long long want = 256;
@@ -1584,91 +1582,86 @@ constexpr size_t h8_m128_weight_bytes(int nks, int T) { return (size_t)4 * nks *
 inline bool h8_one_plain_source(const H8Args& a) { return a.nsrc == 1 && a.src[0].nb == 0 && !a.src[0].scale; }
 
 template <int KS, int DIL, int PAD, bool SCALED>
-int launch_h8_m128(H8Args& a, const slu_conv_h8_desc* d, hipStream_t st) {
-  if (h8_m128_weight_bytes(a.nks, KS * KS) <= WRES_MAX_BYTES) return launch_h8_k<KS, DIL, PAD, 2, 2, 4, 2, SCALED, true>(a, d, st);
+int launch_h8_m128(H8Args& a, const slu_conv_h8_desc* d, const SluEmit& e) {
+  if (h8_m128_weight_bytes(a.nks, KS * KS) <= WRES_MAX_BYTES) return launch_h8_k<KS, DIL, PAD, 2, 2, 4, 2, SCALED, true>(a, d, e);
   if constexpr (!SCALED) {
     if (h8_one_plain_source(a)) {
       if constexpr (KS == 2) {
         if (g_h8_kpc2 && a.nks >= 2) {
 #ifdef SLU_H8_AB
-          if (g_h8_opt == 0) return launch_h8_k<KS, DIL, PAD, 2, 2, 4, 2, false, false, false, 2, 0, true>(a, d, st);
+          if (g_h8_opt == 0) return launch_h8_k<KS, DIL, PAD, 2, 2, 4, 2, false, false, false, 2, 0, true>(a, d, e);
 #endif
-          return launch_h8_k<KS, DIL, PAD, 2, 2, 4, 2, false, false, false, 2, H8_M128_OPT_2X2, true>(a, d, st);
+          return launch_h8_k<KS, DIL, PAD, 2, 2, 4, 2, false, false, false, 2, H8_M128_OPT_2X2, true>(a, d, e);
         }
       }
 #ifdef SLU_H8_AB
       switch (g_h8_opt) {
-        case 0: return launch_h8_k<KS, DIL, PAD, 2, 2, 4, 2, false, false, false, 1, 0, true>(a, d, st);
-        case 8: return launch_h8_k<KS, DIL, PAD, 2, 2, 4, 2, false, false, false, 1, 8, true>(a, d, st);
-        case 15: return launch_h8_k<KS, DIL, PAD, 2, 2, 4, 2, false, false, false, 1, 15, true>(a, d, st);
-        case 100: return launch_h8_k<KS, DIL, PAD, 2, 2, 4, 2, false, false, false, 1, 0, false>(a, d, st);      // the general form, for comparison
+        case 0: return launch_h8_k<KS, DIL, PAD, 2, 2, 4, 2, false, false, false, 1, 0, true>(a, d, e);
+        case 8: return launch_h8_k<KS, DIL, PAD, 2, 2, 4, 2, false, false, false, 1, 8, true>(a, d, e);
+        case 15: return launch_h8_k<KS, DIL, PAD, 2, 2, 4, 2, false, false, false, 1, 15, true>(a, d, e);
+        case 100: return launch_h8_k<KS, DIL, PAD, 2, 2, 4, 2, false, false, false, 1, 0, false>(a, d, e);      // the general form, for comparison
       }
 #endif
-      return launch_h8_k<KS, DIL, PAD, 2, 2, 4, 2, false, false, false, 1, KS == 2 ? H8_M128_OPT_2X2 : H8_M128_OPT_3X3, true>(a, d, st);
+      return launch_h8_k<KS, DIL, PAD, 2, 2, 4, 2, false, false, false, 1, KS == 2 ? H8_M128_OPT_2X2 : H8_M128_OPT_3X3, true>(a, d, e);
     }
   }
-  return launch_h8_k<KS, DIL, PAD, 2, 2, 4, 2, SCALED, false>(a, d, st);
+  return launch_h8_k<KS, DIL, PAD, 2, 2, 4, 2, SCALED, false>(a, d, e);
 }
 
 template <int KS, int DIL, int PAD, bool SCALED>
-int launch_h8_tiles(H8Args& a, const slu_conv_h8_desc* d, int cfg, hipStream_t st) {
+int launch_h8_tiles(H8Args& a, const slu_conv_h8_desc* d, int cfg, const SluEmit& e) {
   switch (cfg) {
-    case CFG_M32_TH16: return launch_h8<KS, DIL, PAD, 1, 1, 8, 2, SCALED>(a, d, st);
-    case CFG_M64_TH16: return launch_h8<KS, DIL, PAD, 2, 1, 8, 2, SCALED>(a, d, st);
-    case CFG_M128_TH8: return launch_h8_m128<KS, DIL, PAD, SCALED>(a, d, st);
-    case CFG_M32_TH8:  return launch_h8<KS, DIL, PAD, 1, 1, 4, 2, SCALED>(a, d, st);
-    case CFG_M64_TH8:  return launch_h8<KS, DIL, PAD, 2, 1, 4, 2, SCALED>(a, d, st);
-    case CFG_M128_TH4: return launch_h8<KS, DIL, PAD, 2, 2, 2, 2, SCALED>(a, d, st);
-    case CFG_M32_TH4:  return launch_h8<KS, DIL, PAD, 1, 1, 4, 1, SCALED>(a, d, st);
-    case CFG_M64_TH4:  return launch_h8<KS, DIL, PAD, 2, 1, 4, 1, SCALED>(a, d, st);
+    case CFG_M32_TH16: return launch_h8<KS, DIL, PAD, 1, 1, 8, 2, SCALED>(a, d, e);
+    case CFG_M64_TH16: return launch_h8<KS, DIL, PAD, 2, 1, 8, 2, SCALED>(a, d, e);
+    case CFG_M128_TH8: return launch_h8_m128<KS, DIL, PAD, SCALED>(a, d, e);
+    case CFG_M32_TH8:  return launch_h8<KS, DIL, PAD, 1, 1, 4, 2, SCALED>(a, d, e);
+    case CFG_M64_TH8:  return launch_h8<KS, DIL, PAD, 2, 1, 4, 2, SCALED>(a, d, e);
+    case CFG_M128_TH4: return launch_h8<KS, DIL, PAD, 2, 2, 2, 2, SCALED>(a, d, e);
+    case CFG_M32_TH4:  return launch_h8<KS, DIL, PAD, 1, 1, 4, 1, SCALED>(a, d, e);
+    case CFG_M64_TH4:  return launch_h8<KS, DIL, PAD, 2, 1, 4, 1, SCALED>(a, d, e);
   }
   return SLU_EUNSUPPORTED;
 }
 
 template <int KS, int DIL, int PAD>
-int launch_h8_family(H8Args& a, const slu_conv_h8_desc* d, int cfg, bool scaled, hipStream_t st) {
-  return scaled ? launch_h8_tiles<KS, DIL, PAD, true>(a, d, cfg, st) : launch_h8_tiles<KS, DIL, PAD, false>(a, d, cfg, st);
+int launch_h8_family(H8Args& a, const slu_conv_h8_desc* d, int cfg, bool scaled, const SluEmit& e) {
+  return scaled ? launch_h8_tiles<KS, DIL, PAD, true>(a, d, cfg, e) : launch_h8_tiles<KS, DIL, PAD, false>(a, d, cfg, e);
 }
 
 template <int MB, int NBW>
-int launch_h8_1x1(H8Args& a, const slu_conv_h8_desc* d, hipStream_t st) {
+int launch_h8_1x1(H8Args& a, const slu_conv_h8_desc* d, const SluEmit& e) {
   constexpr size_t lds = (size_t)MB * 4 * 64 * 16 + (size_t)3 * MB * 32 * 4;
   const long long nblocks = (long long)a.N * a.H * a.W / 32;
   const long long gx = (nblocks + 4 * NBW - 1) / (4 * NBW);
   if (gx <= 0 || gx > 0x7fffffffLL) return SLU_EUNSUPPORTED;
-  hipLaunchKernelGGL((conv1x1_h8_kernel<MB, NBW>), dim3((unsigned)gx), dim3(256), lds, st, a, d->resid, d->out);
+  if (e.name) return slu_emit_name(e, "conv1x1_h8_kernel<%d, %d>", MB, NBW);
+  hipLaunchKernelGGL((conv1x1_h8_kernel<MB, NBW>), dim3((unsigned)gx), dim3(256), lds, e.st, a, d->resid, d->out);
   SLU_CHECK_LAUNCH();
 }
 
 template <int MB, int NKS>
-int launch_h8_1x1_res(H8Args& a, const slu_conv_h8_desc* d, hipStream_t st) {
+int launch_h8_1x1_res(H8Args& a, const slu_conv_h8_desc* d, const SluEmit& e) {
   constexpr size_t lds = (size_t)MB * NKS * 64 * 16 + (size_t)3 * MB * 32 * 4;
   const long long nblocks = (long long)a.N * a.H * a.W / 32;
-  long long gx = 256 * ((MB * NKS >= 12) ? 2 : ((MB * NKS >= 2) ? 3 : 4));      // as many 4-wave workgroups per CU as the registers allow
+  long long gx = 256 * h8_1x1_res_waves_per_simd(MB, NKS);      // as many 4-wave workgroups per CU as the registers allow
   if (gx * 4 > nblocks) gx = (nblocks + 3) / 4;
   if (gx <= 0) return SLU_EUNSUPPORTED;
-  hipLaunchKernelGGL((conv1x1_h8_res_kernel<MB, NKS>), dim3((unsigned)gx), dim3(256), lds, st, a, d->resid, d->out);
+  if (e.name) return slu_emit_name(e, "conv1x1_h8_res_kernel<%d, %d>", MB, NKS);
+  hipLaunchKernelGGL((conv1x1_h8_res_kernel<MB, NKS>), dim3((unsigned)gx), dim3(256), lds, e.st, a, d->resid, d->out);
   SLU_CHECK_LAUNCH();
 }
 
 // resident-weight streaming form: <= 64 output channels and 1 / 2 / 6 / 12 K-steps (the 1x1 convs of the full- and
 // half-resolution blocks); returns -1 when the shape is not covered
 template <int MB>
-int launch_h8_1x1_res_nks(H8Args& a, const slu_conv_h8_desc* d, hipStream_t st) {
+int launch_h8_1x1_res_nks(H8Args& a, const slu_conv_h8_desc* d, const SluEmit& e) {
   switch (a.nks) {
-    case 1:  return launch_h8_1x1_res<MB, 1>(a, d, st);
-    case 2:  return launch_h8_1x1_res<MB, 2>(a, d, st);
-    case 5: case 6:   return launch_h8_1x1_res<MB, 6>(a, d, st);
-    case 10: case 12: return launch_h8_1x1_res<MB, 12>(a, d, st);
+    case 1:  return launch_h8_1x1_res<MB, 1>(a, d, e);
+    case 2:  return launch_h8_1x1_res<MB, 2>(a, d, e);
+    case 5: case 6:   return launch_h8_1x1_res<MB, 6>(a, d, e);
+    case 10: case 12: return launch_h8_1x1_res<MB, 12>(a, d, e);
   }
   return -1;
-}
-
-const char* res_1x1_name(const H8Args& a, char* buf, size_t n) {
-  const int nks = a.nks <= 2 ? a.nks : (a.nks == 5 || a.nks == 6 ? 6 : ((a.nks == 10 || a.nks == 12) ? 12 : 0));
-  if (a.nmblk > 2 || nks == 0) return nullptr;
-  snprintf(buf, n, "conv1x1_h8_res_kernel<%d, %d>", a.nmblk, nks);
-  return buf;
 }
 
 // the layers gemm1x1_h8_kernel covers; SLU_H8_GEMM1X1=0 is the A/B switch back to the streaming kernels
@@ -1687,16 +1680,17 @@ bool gemm1x1_ok(const slu_conv_h8_desc* d, const H8Args& a) {
 }
 
 template <int MB, int D>
-int launch_gemm1x1(H8Args& a, const slu_conv_h8_desc* d, hipStream_t st) {
+int launch_gemm1x1(H8Args& a, const slu_conv_h8_desc* d, const SluEmit& e) {
   constexpr int KC = GEMM1X1_KC, MBLK = 2 * MB;
   constexpr size_t lds = (size_t)3 * MBLK * 32 * 4 + (size_t)D * (2 * KC * 256) * 16 + (size_t)D * (MBLK * KC * 64) * 16;
   static_assert(lds <= 160 * 1024, "gemm1x1 LDS");
   const long long nt = (long long)a.N * a.H * a.W / 256;
   const long long gx = nt < 256 ? nt : 256;
+  if (e.name) return slu_emit_name(e, "gemm1x1_h8_kernel<%d, %d, %d>", MB, KC, D);
   auto kern = gemm1x1_h8_kernel<MB, KC, D>;
   static SluLdsGrant grant;
   if (slu_grant_dynamic_lds(reinterpret_cast<const void*>(kern), lds, grant) != SLU_OK) return SLU_ELAUNCH;
-  hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(512), lds, st, a, d->resid, d->out);
+  hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(512), lds, e.st, a, d->resid, d->out);
   SLU_CHECK_LAUNCH();
 }
 
@@ -1708,6 +1702,39 @@ bool any_scale(const slu_conv_h8_desc* d) {
 
 bool stream_ok(const slu_conv_h8_desc* d, const H8Args& a) {
   return d->ksize == 1 && d->pad == 0 && a.nmblk <= 8 && ((long long)a.H * a.W) % 32 == 0 && !any_scale(d);
+}
+
+// the one traversal of the h8 forward dispatch: slu_conv2d_h8_fwd launches at its leaf, slu_conv2d_h8_kernel_name has the leaf name itself
+int conv_h8_dispatch(const slu_conv_h8_desc* d, const SluEmit& e) {
+  H8Args a{};
+  const int rc = fill_h8(d, a);
+  if (rc != SLU_OK) return rc;
+  if (gemm1x1_ok(d, a)) return a.Cout == 128 ? launch_gemm1x1<2, GEMM1X1_D128>(a, d, e) : launch_gemm1x1<4, GEMM1X1_D256>(a, d, e);
+  if (stream_ok(d, a)) {
+    if (a.nmblk <= 2) {
+      const int rc2 = a.nmblk == 1 ? launch_h8_1x1_res_nks<1>(a, d, e) : launch_h8_1x1_res_nks<2>(a, d, e);
+      if (rc2 != -1) return rc2;
+    }
+    if (a.nmblk == 1) return launch_h8_1x1<1, 2>(a, d, e);
+    if (a.nmblk == 2) return launch_h8_1x1<2, 2>(a, d, e);
+    if (a.nmblk <= 4) return launch_h8_1x1<4, 1>(a, d, e);
+    return launch_h8_1x1<8, 1>(a, d, e);
+  }
+  if (ring3_ok(d, a)) {
+    const int rc2 = launch_ring3_any(a, d, e);
+    if (rc2 != -1) return rc2;
+  }
+  const bool sc = any_scale(d);
+  if (a.out_f32) {      // fp32 NCHW output outside the streaming kernel's reach (odd H*W): 1x1 head only
+    if (d->ksize != 1 || d->dil != 1 || d->pad != 0 || sc) return SLU_EUNSUPPORTED;
+    return launch_h8_k<1, 1, 0, 1, 1, 4, 1, false, false, true>(a, d, e);
+  }
+  const int cfg = choose_h8(a);
+  if (d->ksize == 1 && d->dil == 1 && d->pad == 0) return launch_h8_family<1, 1, 0>(a, d, cfg, sc, e);
+  if (d->ksize == 3 && d->dil == 1 && d->pad == 1) return launch_h8_family<3, 1, 1>(a, d, cfg, sc, e);
+  if (d->ksize == 3 && d->dil == 2 && d->pad == 2) return launch_h8_family<3, 2, 2>(a, d, cfg, sc, e);
+  if (d->ksize == 2 && d->dil == 2 && d->pad == 1) return launch_h8_family<2, 2, 1>(a, d, cfg, sc, e);
+  return SLU_EUNSUPPORTED;
 }
 
 }  // namespace
@@ -1728,76 +1755,11 @@ extern "C" int slu_pack_conv_weight_h8(const float* w, int cout, int cin, int ks
   SLU_CHECK_LAUNCH();
 }
 
-extern "C" int slu_conv2d_h8_fwd(const slu_conv_h8_desc* d, slu_stream_t stream) {
-  H8Args a{};
-  const int rc = fill_h8(d, a);
-  if (rc != SLU_OK) return rc;
-  hipStream_t st = slu_stream(stream);
-  if (gemm1x1_ok(d, a)) return a.Cout == 128 ? launch_gemm1x1<2, GEMM1X1_D128>(a, d, st) : launch_gemm1x1<4, GEMM1X1_D256>(a, d, st);
-  if (stream_ok(d, a)) {
-    if (a.nmblk <= 2) {
-      const int rc2 = a.nmblk == 1 ? launch_h8_1x1_res_nks<1>(a, d, st) : launch_h8_1x1_res_nks<2>(a, d, st);
-      if (rc2 != -1) return rc2;
-    }
-    if (a.nmblk == 1) return launch_h8_1x1<1, 2>(a, d, st);
-    if (a.nmblk == 2) return launch_h8_1x1<2, 2>(a, d, st);
-    if (a.nmblk <= 4) return launch_h8_1x1<4, 1>(a, d, st);
-    return launch_h8_1x1<8, 1>(a, d, st);
-  }
-  {
-    char nm[96];
-    if (ring3_name(d, a, nm, sizeof nm)) return launch_ring3_any(a, d, st);
-  }
-  const bool sc = any_scale(d);
-  if (a.out_f32) {      // fp32 NCHW output outside the streaming kernel's reach (odd H*W): 1x1 head only
-    if (d->ksize != 1 || d->dil != 1 || d->pad != 0 || sc) return SLU_EUNSUPPORTED;
-    return launch_h8_k<1, 1, 0, 1, 1, 4, 1, false, false, true>(a, d, st);
-  }
-  const int cfg = choose_h8(a);
-  if (d->ksize == 1 && d->dil == 1 && d->pad == 0) return launch_h8_family<1, 1, 0>(a, d, cfg, sc, st);
-  if (d->ksize == 3 && d->dil == 1 && d->pad == 1) return launch_h8_family<3, 1, 1>(a, d, cfg, sc, st);
-  if (d->ksize == 3 && d->dil == 2 && d->pad == 2) return launch_h8_family<3, 2, 2>(a, d, cfg, sc, st);
-  if (d->ksize == 2 && d->dil == 2 && d->pad == 1) return launch_h8_family<2, 2, 1>(a, d, cfg, sc, st);
-  return SLU_EUNSUPPORTED;
-}
+extern "C" int slu_conv2d_h8_fwd(const slu_conv_h8_desc* d, slu_stream_t stream) { return conv_h8_dispatch(d, SluEmit{slu_stream(stream), nullptr, 0}); }
 
-// name of the kernel instantiation slu_conv2d_h8_fwd launches for `d` (as rocprofv3 prints it), for per-kernel accounting
+// name of the kernel instantiation slu_conv2d_h8_fwd launches for `d` (as rocprofv3 prints it), or the status with which it refuses `d`
 extern "C" int slu_conv2d_h8_kernel_name(const slu_conv_h8_desc* d, char* buf, size_t n) {
-  H8Args a{};
-  const int rc = fill_h8(d, a);
-  if (rc != SLU_OK || !buf || n == 0) return rc != SLU_OK ? rc : SLU_EINVAL;
-  if (gemm1x1_ok(d, a)) {
-    snprintf(buf, n, "gemm1x1_h8_kernel<%d, %d, %d>", a.Cout / 64, GEMM1X1_KC, a.Cout == 128 ? GEMM1X1_D128 : GEMM1X1_D256);
-    return SLU_OK;
-  }
-  if (stream_ok(d, a)) {
-    if (res_1x1_name(a, buf, n)) return SLU_OK;
-    const int mb = a.nmblk == 1 ? 1 : (a.nmblk == 2 ? 2 : (a.nmblk <= 4 ? 4 : 8));
-    snprintf(buf, n, "conv1x1_h8_kernel<%d, %d>", mb, mb <= 2 ? 2 : 1);
-    return SLU_OK;
-  }
-  if (ring3_name(d, a, buf, n)) return SLU_OK;
-  if (a.out_f32) {
-    snprintf(buf, n, "conv_h8_kernel<1, 1, 0, 1, 1, 4, 1, false, false, true, 1, 0, false>");
-    return SLU_OK;
-  }
-  const int cfg = choose_h8(a);
-  const int* c = CFG_TABLE[cfg];
-  const bool wres = (size_t)c[0] * c[1] * a.nks * d->ksize * d->ksize * 64 * 16 <= WRES_MAX_BYTES;
-  int kpc = 1, opt = 0;
-  bool one = false;
-  if (cfg == CFG_M128_TH8 && !wres && !any_scale(d) && h8_one_plain_source(a)) {      // launch_h8_m128's choice
-    one = true;
-    kpc = (d->ksize == 2 && g_h8_kpc2 && a.nks >= 2) ? 2 : 1;
-    opt = d->ksize == 2 ? H8_M128_OPT_2X2 : H8_M128_OPT_3X3;
-#ifdef SLU_H8_AB
-    if (kpc == 2 ? g_h8_opt == 0 : (g_h8_opt == 0 || g_h8_opt == 8 || g_h8_opt == 15)) opt = g_h8_opt;
-    if (kpc == 1 && g_h8_opt == 100) opt = 0, one = false;
-#endif
-  }
-  snprintf(buf, n, "conv_h8_kernel<%d, %d, %d, %d, %d, %d, %d, %s, %s, false, %d, %d, %s>", d->ksize, d->dil, d->pad, c[0], c[1], c[2], c[3],
-           any_scale(d) ? "true" : "false", wres ? "true" : "false", kpc, opt, one ? "true" : "false");
-  return SLU_OK;
+  return buf ? conv_h8_dispatch(d, SluEmit{nullptr, buf, n}) : SLU_EINVAL;
 }
 
 #ifdef SLU_H8_AB

@@ -329,5 +329,7 @@ inline int fill_args(const slu_conv_desc* d, ConvArgs& a) {
   return SLU_OK;
 }
 
-
 }  // namespace slu_conv
+
+// the split-fp16 branch of slu_conv2d_fwd / slu_conv2d_kernel_name (conv2d_f16x3.hip), entered from conv2d.hip's dispatch
+int slu_conv2d_f16x3_dispatch(const slu_conv_desc* d, const SluEmit& e);

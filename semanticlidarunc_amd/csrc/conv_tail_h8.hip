@@ -48,7 +48,9 @@ struct TailArgs {
   uint2* out;
   int N, H, W, G;              // G = C / 8 channel blocks
   int tiles_x, tiles_y;
-  int dbg;                     // development: 1 = ring DMAs copy the zero record (no input traffic), 2 = no MFMA work
+#ifdef SLU_H8_AB
+  int dbg;                     // ablation switches (SLU_TAIL_DBG, -DSLU_H8_AB builds only): 1 = ring DMAs copy the zero record (no input traffic), 2 = no MFMA work
+#endif
 };
 
 template <int MB, int WM, int WN, int RPW, bool W3RES>
@@ -443,7 +445,7 @@ __global__ __launch_bounds__(512, 2) void tail2_h8_kernel(const TailArgs a) {
   bool has_next = t_beg + t_step < t_end;
   if (has_next) nxt = decode(t_beg + t_step);
 #pragma unroll
-  for (int c = 0; c < P; ++c) stage(cur, c, c, !(a.dbg & 1));
+  for (int c = 0; c < P; ++c) stage(cur, c, c, !SLU_ABLATE(a, 1));
   int rslot = 0, wslot = P % D;
   bool first = true;
   const float2v slA = {a.slopeA, a.slopeA}, slB = {a.slopeB, a.slopeB}, slS = {a.slopeS, a.slopeS};
@@ -481,8 +483,8 @@ __global__ __launch_bounds__(512, 2) void tail2_h8_kernel(const TailArgs a) {
       asm volatile("" ::: "memory");
       {
         constexpr int cn = (c + P) % NKS;
-        if (c + P < NKS) stage(cur, cn, wslot, !(a.dbg & 1));
-        else stage(nxt, cn, wslot, has_next && !(a.dbg & 1));
+        if (c + P < NKS) stage(cur, cn, wslot, !SLU_ABLATE(a, 1));
+        else stage(nxt, cn, wslot, has_next && !SLU_ABLATE(a, 1));
         wslot = wslot + 1 == D ? 0 : wslot + 1;
       }
       if constexpr (c == 0) {       // a1: K-step k of pixel block b = the record of channel block 2 k + hh
@@ -500,7 +502,7 @@ __global__ __launch_bounds__(512, 2) void tail2_h8_kernel(const TailArgs a) {
                      : "+v"(a1r[0][0]), "+v"(a1r[0][1]), "+v"(a1r[(2 / NB) % NKS][2 % NB]), "+v"(a1r[(3 / NB) % NKS][3 % NB]),
                        "+v"(a1r[(4 / NB) % NKS][4 % NB]), "+v"(a1r[(5 / NB) % NKS][5 % NB]), "+v"(a1r[(6 / NB) % NKS][6 % NB]), "+v"(a1r[(7 / NB) % NKS][7 % NB])
                      : "n"(A1WAIT));
-        if (!(a.dbg & 2)) {
+        if (!SLU_ABLATE(a, 2)) {
 #pragma unroll
           for (int k = 0; k < NKS; ++k) {
             half8 af[MB];
@@ -537,7 +539,7 @@ __global__ __launch_bounds__(512, 2) void tail2_h8_kernel(const TailArgs a) {
       }
       const uint4* sb = s_ring + rslot * BUFREC + bbase2;
       rslot = rslot + 1 == D ? 0 : rslot + 1;
-      if (!(a.dbg & 2)) {
+      if (!SLU_ABLATE(a, 2)) {
         // 5 steps (4 dilated taps -> acc3, the centre tap = the 1x1 over a2 -> acc_out), fragments double-buffered: the reads of step
         // s + 1 are issued before the MFMAs of step s, in THIS order (the compiler's own schedule is read, wait, MFMA, read, wait, ...)
         half8 fa[2][MB], fb[2][NB];
@@ -684,7 +686,7 @@ __global__ __launch_bounds__(512, 2) void tail2_h8_kernel(const TailArgs a) {
 }
 
 template <int MB, int RPW, int D, int RES>
-int launch_tail2(TailArgs& a, hipStream_t st) {
+int launch_tail2(TailArgs& a, const SluEmit& e) {
   constexpr int TH = 8 * RPW, C = 32 * MB, NKS = 2 * MB;
   constexpr size_t nblk_b = (size_t)(2 * (TH + 2) * 66 + 63) / 64;
   constexpr size_t lds = ((size_t)MB * NKS * 4 * 64 + (size_t)MB * 3 * NKS * 64 + (RES == 2 ? (size_t)MB * 2 * 64 : 0) + (size_t)D * nblk_b * 64 + 64) * 16;      // + 7 C floats static
@@ -695,15 +697,16 @@ int launch_tail2(TailArgs& a, hipStream_t st) {
   if (nt <= 0 || nt > 0x7fffffffLL) return SLU_EUNSUPPORTED;
   long long gx = 256;
   if (gx > nt) gx = nt;
+  if (e.name) return slu_emit_name(e, "tail2_h8_kernel<%d, %d, %d, %d>", MB, RPW, D, RES);
   auto kern = tail2_h8_kernel<MB, RPW, D, RES>;
   static SluLdsGrant grant;
   if (slu_grant_dynamic_lds(reinterpret_cast<const void*>(kern), lds, grant) != SLU_OK) return SLU_ELAUNCH;
-  hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(512), lds, st, a);
+  hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(512), lds, e.st, a);
   SLU_CHECK_LAUNCH();
 }
 
 template <int MB, int WM, int WN, int RPW, bool W3RES>
-int launch_tail(TailArgs& a, hipStream_t st) {
+int launch_tail(TailArgs& a, const SluEmit& e) {
   constexpr int TH = WN * RPW, MBLK = MB * WM, C = 32 * MBLK, NKS = 2 * MBLK;
   constexpr size_t nb_alloc = (size_t)((2 * (TH + 2) * 66 + 63) / 64) * 64;
   constexpr size_t lds = (size_t)6 * C * 4 + 2 * nb_alloc * 16 + (size_t)2 * MBLK * 5 * 64 * 16 + (W3RES ? (size_t)MBLK * NKS * 64 * 16 : 0) +
@@ -715,10 +718,11 @@ int launch_tail(TailArgs& a, hipStream_t st) {
   if (nt <= 0 || nt > 0x7fffffffLL) return SLU_EUNSUPPORTED;
   long long gx = 256;                                                 // one 8-wave workgroup per CU (LDS)
   if (gx > nt) gx = nt;
+  if (e.name) return slu_emit_name(e, "tail_h8_kernel<%d, %d, %d, %d, %s>", MB, WM, WN, RPW, slu_tf(W3RES));
   auto kern = tail_h8_kernel<MB, WM, WN, RPW, W3RES>;
   static SluLdsGrant grant;
   if (slu_grant_dynamic_lds(reinterpret_cast<const void*>(kern), lds, grant) != SLU_OK) return SLU_ELAUNCH;
-  hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(64 * WM * WN), lds, st, a);
+  hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(64 * WM * WN), lds, e.st, a);
   SLU_CHECK_LAUNCH();
 }
 
@@ -728,7 +732,8 @@ extern "C" int slu_conv_tail_h8_shortcut_supported(int C, int sc_cin) { return C
 
 extern "C" int slu_conv_tail_h8_supported(int C, int H, int W) { return (C == 32 || C == 64 || C == 128) && H > 0 && W > 0 ? 1 : 0; }
 
-extern "C" int slu_conv_tail_h8_fwd(const slu_conv_tail_h8_desc* d, slu_stream_t stream) {
+// the one traversal of the tail dispatch: slu_conv_tail_h8_fwd launches at its leaf, slu_conv_tail_h8_kernel_name has the leaf name itself
+static int conv_tail_dispatch(const slu_conv_tail_h8_desc* d, const SluEmit& e) {
   if (!d || !d->a1 || !d->a2 || !d->w2x2 || !d->w1x1 || !d->out || d->N <= 0 || d->H <= 0 || d->W <= 0) return SLU_EINVAL;
   if (((uintptr_t)d->a1 | (uintptr_t)d->a2 | (uintptr_t)d->out | (uintptr_t)d->resid | (uintptr_t)d->w2x2 | (uintptr_t)d->w1x1) & 15) return SLU_EINVAL;
   if ((d->bnA_a == nullptr) != (d->bnA_b == nullptr) || (d->bnB_a == nullptr) != (d->bnB_b == nullptr)) return SLU_EINVAL;
@@ -747,10 +752,11 @@ extern "C" int slu_conv_tail_h8_fwd(const slu_conv_tail_h8_desc* d, slu_stream_t
   a.resid = reinterpret_cast<const uint2*>(d->resid);
   a.out = reinterpret_cast<uint2*>(d->out);
   a.N = d->N; a.H = d->H; a.W = d->W; a.G = d->C / 8;
-  static const int dbg = [] { const char* e = getenv("SLU_TAIL_DBG"); return e ? atoi(e) : 0; }();
+#ifdef SLU_H8_AB
+  static const int dbg = [] { const char* v = getenv("SLU_TAIL_DBG"); return v ? atoi(v) : 0; }();
   a.dbg = dbg;
-  hipStream_t st = slu_stream(stream);
-  static const bool v1 = [] { const char* e = getenv("SLU_TAIL_V1"); return e && e[0] == '1'; }();     // A/B switch: the round-1 kernel
+#endif
+  static const bool v1 = [] { const char* v = getenv("SLU_TAIL_V1"); return v && v[0] == '1'; }();     // A/B switch: the round-1 kernel
   if (d->sc_x) {      // shortcut mode
     if (d->resid || !d->sc_w || !slu_conv_tail_h8_shortcut_supported(d->C, d->sc_cin) || (((uintptr_t)d->sc_x | (uintptr_t)d->sc_w) & 15)) return SLU_EINVAL;
     if (d->sc_hasact && !(d->sc_slope >= 0.0f && d->sc_slope <= 1.0f)) return SLU_EINVAL;
@@ -758,11 +764,17 @@ extern "C" int slu_conv_tail_h8_fwd(const slu_conv_tail_h8_desc* d, slu_stream_t
     a.sc_w = reinterpret_cast<const uint4*>(d->sc_w);
     a.sc_bias = d->sc_bias;
     a.slopeS = d->sc_hasact ? d->sc_slope : 1.0f;
-    return launch_tail2<2, 1, 4, 2>(a, st);
+    return launch_tail2<2, 1, 4, 2>(a, e);
   }
-  if (!v1 && d->C == 32) return a.resid ? launch_tail2<1, 2, 3, 1>(a, st) : launch_tail2<1, 2, 3, 0>(a, st);
-  if (!v1 && d->C == 64) return a.resid ? launch_tail2<2, 1, 4, 1>(a, st) : launch_tail2<2, 1, 4, 0>(a, st);
-  if (d->C == 32) return launch_tail<1, 1, 8, 2, true>(a, st);
-  if (d->C == 64) return launch_tail<2, 1, 8, 1, true>(a, st);
-  return launch_tail<2, 2, 4, 1, false>(a, st);
+  if (!v1 && d->C == 32) return a.resid ? launch_tail2<1, 2, 3, 1>(a, e) : launch_tail2<1, 2, 3, 0>(a, e);
+  if (!v1 && d->C == 64) return a.resid ? launch_tail2<2, 1, 4, 1>(a, e) : launch_tail2<2, 1, 4, 0>(a, e);
+  if (d->C == 32) return launch_tail<1, 1, 8, 2, true>(a, e);
+  if (d->C == 64) return launch_tail<2, 1, 8, 1, true>(a, e);
+  return launch_tail<2, 2, 4, 1, false>(a, e);
+}
+
+extern "C" int slu_conv_tail_h8_fwd(const slu_conv_tail_h8_desc* d, slu_stream_t stream) { return conv_tail_dispatch(d, SluEmit{slu_stream(stream), nullptr, 0}); }
+
+extern "C" int slu_conv_tail_h8_kernel_name(const slu_conv_tail_h8_desc* d, char* buf, size_t n) {
+  return buf ? conv_tail_dispatch(d, SluEmit{nullptr, buf, n}) : SLU_EINVAL;
 }

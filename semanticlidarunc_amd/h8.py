@@ -6,7 +6,6 @@ kernels (fp16 operands, fp32 accumulate / epilogue); torch only owns the memory.
 """
 from __future__ import annotations
 
-import os
 
 import ctypes as C
 from typing import NamedTuple, Optional, Sequence
@@ -220,6 +219,8 @@ def conv_tail_h8(a1: torch.Tensor, a2: torch.Tensor, w2x2: torch.Tensor, w1x1: t
     if ops.TIMING is None:
         check(lib.slu_conv_tail_h8_fwd(C.byref(d), _stream()), "slu_conv_tail_h8_fwd")
         return out
+    buf = C.create_string_buffer(96)
+    check(lib.slu_conv_tail_h8_kernel_name(C.byref(d), buf, 96), "slu_conv_tail_h8_kernel_name")
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     check(lib.slu_conv_tail_h8_fwd(C.byref(d), _stream()), "slu_conv_tail_h8_fwd")
@@ -231,12 +232,7 @@ def conv_tail_h8(a1: torch.Tensor, a2: torch.Tensor, w2x2: torch.Tensor, w1x1: t
     nbytes = n * h * w * 2.0 * (c + c + 3 * c + c + (scin + c if shortcut is not None else 0)) + 2.0 * c * (c * (4 + 3) + scin)
     # what the fused kernel must move: a1, a2 (+ the residual, or the shortcut's input) in, out once, weights
     min_bytes = n * h * w * 2.0 * (c * 3 + (c if resid is not None else 0) + scin) + 2.0 * c * (c * (4 + 3) + scin)
-    res = 2 if shortcut is not None else (1 if resid is not None else 0)      # the instantiation slu_conv_tail_h8_fwd launches (rocprofv3 reports the same name)
-    if os.environ.get("SLU_TAIL_V1") == "1" and shortcut is None:
-        name = {32: "tail_h8_kernel<1, 1, 8, 2, true>", 64: "tail_h8_kernel<2, 1, 8, 1, true>", 128: "tail_h8_kernel<2, 2, 4, 1, false>"}[c]
-    else:
-        name = {32: f"tail2_h8_kernel<1, 2, 3, {res}>", 64: f"tail2_h8_kernel<2, 1, 4, {res}>", 128: "tail_h8_kernel<2, 2, 4, 1, false>"}[c]
-    ops.TIMING.append((name, flops, nbytes, e0, e1, min_bytes))
+    ops.TIMING.append((buf.value.decode(), flops, nbytes, e0, e1, min_bytes))
     ops.TIMING_TAGS.append(f"N{n} {c}->{c} k2d2 + {3 * c}->{c} k1" + (f" + {scin}->{c} k1 shortcut" if shortcut is not None else "") + f" fused {h}x{w}")
     return out
 

@@ -4,8 +4,9 @@ selects it, and a coverage test that keeps that true as the dispatch rules chang
 The dispatchers (choose_h8 in csrc/conv2d_h8.hip, choose_cfg in csrc/conv_common.h, launch_h8_m128) choose the tile from the
 launch size, so the configurations of the full-size runs (>= 256 / 512 / 3 072 workgroups) are never reached by the small shapes of
 test_gpu_h8.py / test_gpu_conv.py / test_gpu_f16x3.py.  Each row of the tables below names the instantiation its shape must select
-(read back from ops.TIMING, i.e. slu_conv2d_h8_kernel_name / slu_conv2d_kernel_name) and checks every output element at the bar
-of its precision:
+(read back from ops.TIMING, i.e. slu_conv2d_h8_kernel_name / slu_conv2d_kernel_name: the launch's own dispatch with a leaf that
+prints its template arguments instead of launching, so the name is the launched one by construction; test_dispatch_names_cpu.py asks
+the same rows for their names without a GPU) and checks every output element at the bar of its precision:
   h8     2^-10 |y| + 1e-4 max(1, max|y| / 30) against the oracle fed the same fp16-rounded operands; pad channels exactly 0
   fp32   1e-4 abs on O(1) outputs (fused BatchNorm statistics: as test_gpu_backward.test_fused_bn_statistics)
   f16x3  1e-4 scale against the oracle, 2e-5 scale against the fp32 kernel
