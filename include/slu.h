@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SLU_ABI_VERSION 32
+#define SLU_ABI_VERSION 33
 
 #define SLU_OK            0
 #define SLU_EINVAL       -1   /* null pointer / non-positive size / inconsistent descriptor   */
@@ -307,6 +307,23 @@ typedef struct slu_h8_src {
   const float* scale;  /* [N][8 G] fp32 multiplier per (output image, channel) (Dropout2d), or NULL; 16-byte aligned  */
   int32_t G;           /* channel blocks                                                                             */
   int32_t nbatch;      /* 0: nimg = N; k > 0: the tensor holds k images, output image n reads image n % k            */
+  int32_t shuffle;     /* 1 (first source only): the source is nn.PixelShuffle(2) of ptr, read in place.  ptr is h8
+                          [N][G][H/2][W/2][8] whose channels are STORED IN SHUFFLE ORDER -- stored block 4 go + sub, slot k
+                          holds channel 32 go + 4 k + sub of the tensor PixelShuffle is applied to (sub = 2 i + j), so that
+                          the record of shuffled block go at output pixel (y, x) is the stored record of block
+                          4 go + 2 (y & 1) + (x & 1) at (y >> 1, x >> 1).  The source contributes G / 4 blocks; G a multiple
+                          of 8 (SLU_EINVAL otherwise), H and W even; scale is [N][8 G] per STORED channel in stored order.
+                          COVERED: (a) G == 8 (64 stored channels = one shuffled K-step) as the first of two sources of
+                          the 80 -> 32 3x3 layer that ring3_h8_kernel<1, 1, 5, 1, 4> runs (second source plain: no
+                          scale, no nbatch; at least 256 tiles of 8 x 64; N <= 237 with a scale); (b) any 3x3 / dil 1 /
+                          pad 1 layer with h8 output in which SOME source carries a scale (the SCALED conv_h8_kernel
+                          instantiations), with 3 G / 4 + input blocks <= 64 (one multiplier record per stored block).
+                          Anything else is SLU_EUNSUPPORTED: materialise the shuffle with slu_pixel_shuffle_h8.
+                          Each multiplier is rounded to fp16 and the fp16 product rounds once; slu_pixel_shuffle_h8
+                          multiplies by the fp32 value and rounds once.  The two agree bit for bit when the multipliers
+                          are exact in fp16 (0 and products of 1 / (1 - p) for p = 0.2: powers of 1.25); for other
+                          values they may differ in the last fp16 bit of the scaled input                              */
+  int32_t reserved;
 } slu_h8_src;
 
 typedef struct slu_conv_h8_desc {   /* HOST struct */
@@ -379,7 +396,9 @@ int slu_conv_tail_h8_kernel_name(const slu_conv_tail_h8_desc* desc, char* buf, s
  *   s = act(conv1x1(x) + bias1);  a1 = bn1(act(conv3x3_pad1(s) + bias2));  out = s + bn2(act(conv3x3_dil2_pad2(a1) + bias3))
  * s and a1 stay on chip (rounded to fp16 exactly where the three separate slu_conv2d_h8_fwd launches would store them).
  * x: h8 [N][ceil(Cin/8)][H][W][8]; out: h8 [N][4][H][W][8]; w1 / w2 / w3 = slu_pack_conv_weight_h8 of [32][Cin][1][1] / [32][32][3][3] /
- * [32][32][3][3]; act = LeakyReLU(slope), 0 <= slope <= 1.  Cin <= 32, C == 32 (slu_ctx_block_h8_supported). */
+ * [32][32][3][3]; act = LeakyReLU(slope), 0 <= slope <= 1.  Cin <= 32, C == 32 (slu_ctx_block_h8_supported).
+ * nbatch > 0: x holds nbatch images and output image n is the block of x[n % nbatch] (N a multiple of nbatch): the T stacked passes of an
+ * MC-dropout evaluation read the B distinct input images in place instead of T copies of them. */
 typedef struct slu_ctx_block_h8_desc {   /* HOST struct */
   const void* x;
   int32_t N, H, W, Cin, C;
@@ -389,6 +408,7 @@ typedef struct slu_ctx_block_h8_desc {   /* HOST struct */
   const float *bias3, *bn2_a, *bn2_b;
   float slope;
   void* out;
+  int32_t nbatch;                        /* 0: x holds N images */
 } slu_ctx_block_h8_desc;
 int slu_ctx_block_h8_supported(int Cin, int C, int H, int W);
 int slu_ctx_block_h8_fwd(const slu_ctx_block_h8_desc* desc, slu_stream_t stream);
@@ -566,7 +586,9 @@ int slu_spatial_softmax_gate_bwd(const float* x, const float* score, const float
  * the offset by ceil(total draws / 4).  An output is an [N][C] table buf[begin ...] = product over its <= 3 sites:
  *   site_a[n][off_a + c] * site_b[n][off_b + c'] * site_c[n][off_c + c'],  c' = shuffled ? c / 4 : c  (stored channel c of a tensor read
  *   through PixelShuffle(2) feeds shuffled channel c / 4: UpBlock's dropout1 / dropout2 act on the shuffled tensor, SalsaNext.py:141-149);
- * a site index of -1 drops the factor.  `sites`, `outs`: DEVICE arrays; outs sorted by `begin`; total = sum of N * C over the outputs. */
+ * a site index of -1 drops the factor.  shuffled == 2: the same values, written in the stored order of slu_h8_src.shuffle -- position
+ * 8 (4 go + sub) + k holds the multiplier of channel c = 32 go + 4 k + sub (C a multiple of 32).
+ * `sites`, `outs`: DEVICE arrays; outs sorted by `begin`; total = sum of N * C over the outputs. */
 typedef struct slu_dropout_site {
   long long begin;
   int C, active;

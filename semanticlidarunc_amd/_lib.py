@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-ABI_VERSION = 32
+ABI_VERSION = 33
 MAX_SRC = 3
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libslu_hip.so")
@@ -43,7 +43,8 @@ class ConvDesc(C.Structure):
 
 
 class H8Src(C.Structure):
-    _fields_ = [("ptr", C.c_void_p), ("scale", C.c_void_p), ("G", C.c_int32), ("nbatch", C.c_int32)]
+    _fields_ = [("ptr", C.c_void_p), ("scale", C.c_void_p), ("G", C.c_int32), ("nbatch", C.c_int32), ("shuffle", C.c_int32),
+                ("reserved", C.c_int32)]
 
 
 class ConvH8Desc(C.Structure):
@@ -90,6 +91,7 @@ class CtxBlockH8Desc(C.Structure):
         ("bias3", C.c_void_p), ("bn2_a", C.c_void_p), ("bn2_b", C.c_void_p),
         ("slope", C.c_float),
         ("out", C.c_void_p),
+        ("nbatch", C.c_int32),
     ]
 
 

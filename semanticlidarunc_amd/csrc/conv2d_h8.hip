@@ -43,6 +43,7 @@ struct H8Src {
   int G;               // channel blocks of the stored tensor
   int gbeg;            // first block of this source in the concatenated input
   int nb;              // 0: holds N images; k > 0: holds k images, output image n reads n % k
+  int shuf;            // 1: read through PixelShuffle(2) in place: ptr is [nimg][4 G][H/2][W/2] with its channels stored in shuffle order (slu.h)
 };
 
 struct H8Args {
@@ -269,6 +270,12 @@ __global__ __launch_bounds__(64 * WM * WN, h8_waves_per_simd(MB, WM * WN, RPW)) 
   static_assert(OPT == 0 || (MB == 2 && WM == 2 && WN == 4 && !F32OUT), "OPT: the 8-wave 128-channel configuration only");
   static_assert(KPC <= 2, "pc_rc carries 2 bits of channel block");
   static_assert(KPC == 1 || ONE, "multi-K-step chunks: single-source layers only");
+  // SHUF: the instantiations that can read source 0 through PixelShuffle(2) in place (H8Src.shuf, a runtime property: UpBlock.conv1 with
+  // multipliers).  The K-steps of source 0 fetch, for tile-image pixel (gy, gx) of contributed block g, the stored record of plane
+  // 4 g + 2 (gy & 1) + (gx & 1) at (gy >> 1, gx >> 1) -- a block's four stored planes span H W records like a plain block, so only the
+  // per-lane offset differs -- and their multiplier is the one of that STORED block: selected by the parity of the pixel a B fragment reads.
+  constexpr bool SHUF = SCALED && KS == 3 && DIL == 1 && PAD == 1 && !ONE && KPC == 1;
+  static_assert(!SHUF || (WN * RPW) % 2 == 0, "tile rows start on even image rows");
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* s_epi = reinterpret_cast<float*>(smem);                        // bias | bn_a | bn_b
@@ -382,14 +389,20 @@ __global__ __launch_bounds__(64 * WM * WN, h8_waves_per_simd(MB, WM * WN, RPW)) 
   // st_b0: byte address of the record at tile-image position (0, 0) of the chunk's first block; st_b1: the same for its second block
   // MINUS one plane (pc_off carries the plane offset of the block), which equals st_b0 unless the K-step straddles two sources
   uintptr_t st_b0 = 0, st_b1 = 0;
+  bool st_sh = false;                                  // SHUF: the chunk belongs to the shuffled source 0 (an even number of blocks: never straddles)
+  const int hw4 = (a.H >> 1) * (a.W >> 1), w2 = a.W >> 1;
   int st_g0 = 0;                                       // first channel block of the chunk (a block g is live while st_g0 + g < Gin)
   bool st_on = false;
   int st_x0 = 0, st_y0 = 0, st_q = 0, st_wave = wave;
   uint4 *st_db = s_b, *st_da = s_a;
   auto stage_begin = [&](const TilePos& tp, int q, int buf) __attribute__((always_inline)) {
     const int img[SLU_MAX_SRC] = {tp.i0, tp.i1, tp.i2};
-    const long long org = (long long)(tp.y0 - PAD) * a.W + (tp.x0 - PAD);
+    long long org = (long long)(tp.y0 - PAD) * a.W + (tp.x0 - PAD);
     st_g0 = 2 * KPC * q;
+    if constexpr (SHUF) {
+      st_sh = a.src[0].shuf && st_g0 < a.src[0].G;
+      if (st_sh) org = 0;                              // the pieces carry the whole in-image offset
+    }
     if constexpr (ONE) {
       st_b0 = reinterpret_cast<uintptr_t>(a.src[0].ptr) + 16 * ((long long)(((size_t)tp.n * a.src[0].G + st_g0) * HW) + org);
       st_b1 = st_b0;
@@ -418,7 +431,11 @@ __global__ __launch_bounds__(64 * WM * WN, h8_waves_per_simd(MB, WM * WN, RPW)) 
         const int gsel = (rc >> 16) & 3;
         const uintptr_t gb = (!ONE && gsel == 1) ? st_b1 : st_b0;
         const bool ok = (rc >> 20) && st_g0 + gsel < a.Gin && (unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W;
-        const uintptr_t src = ok ? gb + 16 * (long long)pc_off[i] : zero_addr;
+        int off = pc_off[i];                           // records; one image's blocks of a chunk stay far below 2^31 / 16
+        if constexpr (SHUF) {
+          if (st_sh) off = gsel * (int)HW + (2 * (gy & 1) + (gx & 1)) * hw4 + (gy >> 1) * w2 + (gx >> 1);
+        }
+        const uintptr_t src = ok ? gb + 16 * (long long)off : zero_addr;
         SLU_GLDS16(reinterpret_cast<const uint4*>(src), st_db + blk * 64);
       }
     } else if constexpr (!WRES) {
@@ -445,9 +462,26 @@ __global__ __launch_bounds__(64 * WM * WN, h8_waves_per_simd(MB, WM * WN, RPW)) 
       half8 h;
 #pragma unroll
       for (int k = 0; k < 8; ++k) h[k] = (_Float16)1.0f;
-      if (tid < a.Gin) {
+      // table position -> block: plain, position g = block g of the concatenated input; with a shuffled source 0 of G0 contributed
+      // blocks, positions [0, 4 G0) = its STORED blocks and position 3 G0 + g = block g >= G0 of the other sources
+      int g = tid;
+      bool stored0 = false;
+      if constexpr (SHUF) {
+        if (a.src[0].shuf) {
+          stored0 = tid < 4 * a.src[0].G;
+          g = stored0 ? 0 : tid - 3 * a.src[0].G;
+        }
+      }
+      if (stored0) {
+        if (a.src[0].scale) {
+          const float* sp = a.src[0].scale + ((size_t)n * 4 * a.src[0].G + tid) * 8;
+          const float4 s0 = *reinterpret_cast<const float4*>(sp), s1 = *reinterpret_cast<const float4*>(sp + 4);
+          h[0] = (_Float16)s0.x; h[1] = (_Float16)s0.y; h[2] = (_Float16)s0.z; h[3] = (_Float16)s0.w;
+          h[4] = (_Float16)s1.x; h[5] = (_Float16)s1.y; h[6] = (_Float16)s1.z; h[7] = (_Float16)s1.w;
+        }
+      } else if (g < a.Gin) {
         int img[SLU_MAX_SRC] = {0, 0, 0};
-        const SrcSel p = select_src(a, img, tid);
+        const SrcSel p = select_src(a, img, g);
         if (p.scale) {
           const float* sp = p.scale + ((size_t)n * p.G + p.gl) * 8;
           const float4 s0 = *reinterpret_cast<const float4*>(sp), s1 = *reinterpret_cast<const float4*>(sp + 4);
@@ -536,8 +570,26 @@ __global__ __launch_bounds__(64 * WM * WN, h8_waves_per_simd(MB, WM * WN, RPW)) 
       H8_PROF_MARK(2)                                    // issuing the next chunk's DMA (+ residual prefetch)
       const uint4* sb = s_b + buf * NB_ALLOC + bbase;
       const uint4* sa = s_a + abase + (WRES ? q * T * 64 : buf * NREC_A);
-      half8 sc;
-      if constexpr (SCALED) sc = __builtin_bit_cast(half8, s_scale[spar * 64 + 2 * q + hh]);
+      // scm[yr][xr]: the multiplier of the B fragment of accumulator block b at tap (dy, dx), yr = ((b >> 1) + dy) & 1, xr = dx & 1.  A plain
+      // chunk has one record for all four; a shuffled one the stored block 4 g + 2 (row parity) + (column parity) of the pixel read: row
+      // y0 + wn RPW + (b >> 1) + dy - 1 with y0 even, column x0 + 32 (b & 1) + jj + dx - 1 with x0 a multiple of 64
+      half8 scm[SHUF ? 2 : 1][SHUF ? 2 : 1];
+      if constexpr (SHUF) {
+        const int g0s = a.src[0].shuf ? a.src[0].G : 0;
+        if (2 * q < g0s) {
+#pragma unroll
+          for (int yr = 0; yr < 2; ++yr)
+#pragma unroll
+            for (int xr = 0; xr < 2; ++xr)
+              scm[yr][xr] = __builtin_bit_cast(half8, s_scale[spar * 64 + 4 * (2 * q + hh) + 2 * ((yr + wn * RPW + 1) & 1) + ((jj + xr + 1) & 1)]);
+        } else {
+          scm[0][0] = __builtin_bit_cast(half8, s_scale[spar * 64 + 3 * g0s + 2 * q + hh]);
+          scm[0][1] = scm[1][0] = scm[1][1] = scm[0][0];
+        }
+      } else if constexpr (SCALED) {
+        scm[0][0] = __builtin_bit_cast(half8, s_scale[spar * 64 + 2 * q + hh]);
+      }
+      auto sc_of = [&](int b, int dy, int dx) __attribute__((always_inline)) -> half8 { return SHUF ? scm[((b >> 1) + dy) & 1][dx & 1] : scm[0][0]; };
       {
         if constexpr (MB == 2 && WM == 2 && WN == 4) {
           // the 8-wave 128-channel configuration (MFMA-bound layers): fragments of tap-step t+1 are read before the MFMAs of tap-step t
@@ -552,7 +604,7 @@ __global__ __launch_bounds__(64 * WM * WN, h8_waves_per_simd(MB, WM * WN, RPW)) 
 #pragma unroll
             for (int b = 0; b < NB; ++b) {
               bf[set][b] = __builtin_bit_cast(half8, sb[j * 2 * REC + ((b >> 1) + dy) * LW + (b & 1) * 32 + dx]);
-              if constexpr (SCALED) bf[set][b] *= sc;
+              if constexpr (SCALED) bf[set][b] *= sc_of(b, dy, dx);
             }
           };
           read_frags(0, 0);
@@ -588,7 +640,7 @@ __global__ __launch_bounds__(64 * WM * WN, h8_waves_per_simd(MB, WM * WN, RPW)) 
 #pragma unroll
             for (int b = 0; b < NB; ++b) {
               bf[set][b] = __builtin_bit_cast(half8, sb[((b >> 1) + dy) * LW + (b & 1) * 32 + dx]);
-              if constexpr (SCALED) bf[set][b] *= sc;
+              if constexpr (SCALED) bf[set][b] *= sc_of(b, dy, dx);
             }
           };
           read_frags(0, 0);
@@ -618,7 +670,7 @@ __global__ __launch_bounds__(64 * WM * WN, h8_waves_per_simd(MB, WM * WN, RPW)) 
 #pragma unroll
             for (int b = 0; b < NB; ++b) {
               half8 bf = __builtin_bit_cast(half8, sb[((b >> 1) + dy) * LW + (b & 1) * 32 + dx]);
-              if constexpr (SCALED) bf *= sc;
+              if constexpr (SCALED) bf *= sc_of(b, dy, dx);
 #pragma unroll
               for (int i = 0; i < MB; ++i) acc[i][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[i], bf, acc[i][b], 0, 0, 0);
             }
@@ -1207,12 +1259,15 @@ int fill_h8(const slu_conv_h8_desc* d, H8Args& a) {
   int g = 0;
   for (int s = 0; s < d->nsrc; ++s) {
     const slu_h8_src& S = d->src[s];
-    if (!S.ptr || S.G <= 0 || S.nbatch < 0) return SLU_EINVAL;
+    if (!S.ptr || S.G <= 0 || S.nbatch < 0 || (S.shuffle != 0 && S.shuffle != 1)) return SLU_EINVAL;
     if (((uintptr_t)S.ptr & 15) || ((uintptr_t)S.scale & 15)) return SLU_EINVAL;
-    a.src[s] = H8Src{reinterpret_cast<const uint4*>(S.ptr), S.scale, S.G, g, S.nbatch};
-    g += S.G;
+    // a shuffled source: the first one, whole groups of 64 stored channels (an even number of contributed blocks), even output size
+    if (S.shuffle && (s != 0 || S.G % 8 || (d->H & 1) || (d->W & 1) || S.nbatch)) return SLU_EINVAL;
+    const int gc = S.shuffle ? S.G / 4 : S.G;      // blocks this source contributes to the concatenated input
+    a.src[s] = H8Src{reinterpret_cast<const uint4*>(S.ptr), S.scale, gc, g, S.nbatch, S.shuffle};
+    g += gc;
   }
-  for (int s = d->nsrc; s < SLU_MAX_SRC; ++s) a.src[s] = H8Src{nullptr, nullptr, 0, 0x7fffffff, 0};
+  for (int s = d->nsrc; s < SLU_MAX_SRC; ++s) a.src[s] = H8Src{nullptr, nullptr, 0, 0x7fffffff, 0, 0};
   if (((uintptr_t)d->out & 15) || ((uintptr_t)d->resid & 15) || ((uintptr_t)d->wpack & 15)) return SLU_EINVAL;
   if (d->resid && d->out_f32_nchw) return SLU_EINVAL;
   a.nsrc = d->nsrc;
@@ -1241,6 +1296,10 @@ int launch_h8_k(H8Args& a, const slu_conv_h8_desc* d, const SluEmit& e) {
   const size_t lds = (size_t)3 * MBLK * 32 * 4 + (SCALED ? 2048 : 0) + 2 * nb_alloc * 16 + (size_t)MBLK * (WRES ? a.nks : 2 * KPC) * T * 64 * 16;
   if (lds > 160 * 1024) return SLU_EUNSUPPORTED;
   if (SCALED && a.Gin > 64) return SLU_EUNSUPPORTED;
+  if (a.src[0].shuf) {      // a source read through PixelShuffle in place: the SCALED 3x3 kernels only; one table record per stored block of it
+    if (!(SCALED && KS == 3 && DIL == 1 && PAD == 1 && !ONE && KPC == 1 && !F32OUT)) return SLU_EUNSUPPORTED;
+    if (3 * a.src[0].G + a.Gin > 64) return SLU_EUNSUPPORTED;
+  }
   a.tiles_x = (a.W + 63) / 64;
   a.tiles_y = (a.H + TH - 1) / TH;
   static const int order = [] { const char* e = getenv("SLU_H8_ORDER"); return e ? atoi(e) : 1; }();      // 0 is kept for A/B runs
@@ -1289,6 +1348,10 @@ struct RingArgs {
   float slope;                 // 1 = no activation
   uint4* out;                  // h8 [N][4 MB][H][W]
   int N, H, W, tiles_x, tiles_y;
+  // x read through PixelShuffle(2) in place (NKS = 5 only): x is [N][4 G0][H/2][W/2] with channels stored in shuffle order, so the record of
+  // contributed block g at pixel (gy, gx) is the stored record of plane 4 g + 2 (gy & 1) + (gx & 1) at (gy >> 1, gx >> 1)
+  int shuf;
+  const float* sc0;            // shuf: [N][32 G0] fp32 multipliers per stored channel (stored order) or nullptr
 };
 
 template <int NKS, int NIB, int P, int NST>
@@ -1320,6 +1383,7 @@ __global__ __launch_bounds__(512, 2) void ring3_h8_kernel(const RingArgs a) {
   uint4* s_w = reinterpret_cast<uint4*>(smem);                      // [MB][NKS][9][64]
   uint4* s_ring = s_w + MB * NKS * T * 64;                          // [D][BUFREC]
   uint4* s_trash = s_ring + D * BUFREC;                             // [64]
+  uint4* s_mul = s_trash + 64;                                      // shuf with multipliers: [N][4 G0] fp16 records, one per stored block
 
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), wn = wave;
   const int hh = lane >> 5, jj = lane & 31;
@@ -1342,6 +1406,20 @@ __global__ __launch_bounds__(512, 2) void ring3_h8_kernel(const RingArgs a) {
     s_epi[2 * C + tid] = a.bn_a ? a.bn_b[tid] : 0.0f;
   }
   for (int blk = wave; blk < MB * NKS * T; blk += NWAVE) SLU_GLDS16(a.wpack + (size_t)blk * 64 + lane, s_w + blk * 64);
+  const bool mul0 = NKS == 5 && a.shuf && a.sc0;
+  if constexpr (NKS == 5) {
+    // the multiplier table goes to LDS once, here: the tile loop's VM operations (and ring3_younger) stay what they are
+    if (mul0) {
+      for (int e = tid; e < a.N * 4 * a.G0; e += 64 * NWAVE) {
+        const float4 s0 = *reinterpret_cast<const float4*>(a.sc0 + (size_t)e * 8), s1 = *reinterpret_cast<const float4*>(a.sc0 + (size_t)e * 8 + 4);
+        half8 h;
+        h[0] = (_Float16)s0.x; h[1] = (_Float16)s0.y; h[2] = (_Float16)s0.z; h[3] = (_Float16)s0.w;
+        h[4] = (_Float16)s1.x; h[5] = (_Float16)s1.y; h[6] = (_Float16)s1.z; h[7] = (_Float16)s1.w;
+        s_mul[e] = __builtin_bit_cast(uint4, h);
+      }
+    }
+  }
+  const int hw4 = (a.H >> 1) * (a.W >> 1), w2 = a.W >> 1;
 
   struct TilePos { int x0, y0, n; };
   auto decode = [&](int t) {
@@ -1367,8 +1445,9 @@ __global__ __launch_bounds__(512, 2) void ring3_h8_kernel(const RingArgs a) {
     const bool second = 2 * c >= a.G0;                  // a K-step never straddles the two sources (G0 is even)
     const uint4* src = second ? a.x1 : a.x;
     const int gs = second ? a.G1 : a.G0, g = second ? 2 * c - a.G0 : 2 * c;
+    const bool sh = NKS == 5 && a.shuf && !second;      // the 4 stored planes of a contributed block span HW records, as a plain block does
     const uintptr_t base0 = reinterpret_cast<uintptr_t>(src) +
-                            16 * ((long long)(((size_t)tp.n * gs + g) * HW) + (long long)(tp.y0 - PAD) * a.W + (tp.x0 - PAD));
+                            16 * ((long long)(((size_t)tp.n * gs + g) * HW) + (sh ? 0ll : (long long)(tp.y0 - PAD) * a.W + (tp.x0 - PAD)));
     const uintptr_t base1 = base0 + 16 * (long long)HW;
 #pragma unroll
     for (int i = 0; i < NIB; ++i) {
@@ -1376,7 +1455,11 @@ __global__ __launch_bounds__(512, 2) void ring3_h8_kernel(const RingArgs a) {
       const int rc = pc_rc[i];
       const int gy = tp.y0 - PAD + (rc & 255), gx = tp.x0 - PAD + ((rc >> 8) & 255);
       const bool ok = valid && (rc >> 17) && (unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W;
-      const uintptr_t p = ok ? (((rc >> 16) & 1) ? base1 : base0) + (long long)pc_off[i] : zero;
+      int off = pc_off[i];
+      if constexpr (NKS == 5) {
+        if (sh) off = 16 * ((2 * (gy & 1) + (gx & 1)) * hw4 + (gy >> 1) * w2 + (gx >> 1));
+      }
+      const uintptr_t p = ok ? (((rc >> 16) & 1) ? base1 : base0) + (long long)off : zero;
       SLU_GLDS16(reinterpret_cast<const uint4*>(p), (NBLK_B % NWAVE == 0 || blk < NBLK_B) ? db + blk * 64 : s_trash);
     }
     asm volatile("" ::: "memory");
@@ -1420,12 +1503,31 @@ __global__ __launch_bounds__(512, 2) void ring3_h8_kernel(const RingArgs a) {
       const uint4* sb = s_ring + rslot * BUFREC + bbase;
       rslot = rslot + 1 == D ? 0 : rslot + 1;
       half8 fa[2][MB], fb[2][NB];
+      // K-step 0 of a shuffled source with multipliers: the lane's B fragment at tap (ty, tx) is input pixel (y0 + wn + ty - 1, x0 + 32 b + jj + tx - 1)
+      // of contributed block hh = stored block 4 hh + 2 (row parity) + (column parity); y0 and x0 are even, so the lane needs four records of
+      // its image's table: msc[ty & 1][tx & 1]
+      constexpr bool MUL = NKS == 5 && c == 0 && RPW == 1 && DIL == 1;
+      half8 msc[MUL ? 2 : 1][MUL ? 2 : 1];
+      if constexpr (MUL) {
+        if (mul0) {
+#pragma unroll
+          for (int ty = 0; ty < 2; ++ty)
+#pragma unroll
+            for (int tx = 0; tx < 2; ++tx)
+              msc[ty][tx] = __builtin_bit_cast(half8, s_mul[cur.n * 4 * a.G0 + 4 * hh + 2 * ((wn + ty + 1) & 1) + ((jj + tx + 1) & 1)]);
+        }
+      }
       auto rd = [&](int tap, int buf) {
         const int dy = (tap / KS) * DIL, dx = (tap % KS) * DIL;
 #pragma unroll
         for (int i = 0; i < MB; ++i) fa[buf][i] = __builtin_bit_cast(half8, s_w[((i * NKS + c) * T + tap) * 64 + lane]);
 #pragma unroll
-        for (int b = 0; b < NB; ++b) fb[buf][b] = __builtin_bit_cast(half8, sb[((b >> 1) + dy) * LW + (b & 1) * 32 + dx]);
+        for (int b = 0; b < NB; ++b) {
+          fb[buf][b] = __builtin_bit_cast(half8, sb[((b >> 1) + dy) * LW + (b & 1) * 32 + dx]);
+          if constexpr (MUL) {
+            if (mul0) fb[buf][b] *= msc[(tap / KS) & 1][(tap % KS) & 1];
+          }
+        }
       };
       rd(0, 0);
 #pragma unroll
@@ -1485,9 +1587,16 @@ template <int DIL, int MB, int NKS, int RPW, int D>
 int launch_ring3(const H8Args& h, const slu_conv_h8_desc* d, const SluEmit& e) {
   constexpr int TH = 8 * RPW, PAD = DIL;
   constexpr size_t nblk_b = (size_t)(2 * (TH + 2 * PAD) * (64 + 2 * PAD) + 63) / 64;
-  constexpr size_t lds = ((size_t)MB * NKS * 9 * 64 + (size_t)D * nblk_b * 64 + 64) * 16;      // + 3 * 32 MB floats static
-  static_assert(lds + 3 * 32 * MB * 4 <= 160 * 1024, "ring does not fit in LDS");
+  constexpr size_t lds0 = ((size_t)MB * NKS * 9 * 64 + (size_t)D * nblk_b * 64 + 64) * 16;      // + 3 * 32 MB floats static
+  static_assert(lds0 + 3 * 32 * MB * 4 <= 160 * 1024, "ring does not fit in LDS");
+  // a shuffled first source (NKS = 5: UpBlock.conv1 at full resolution): its multiplier table [N][4 G0] records joins the ring in LDS
+  const bool shuf = h.src[0].shuf != 0;
+  if (shuf && (NKS != 5 || RPW != 1 || DIL != 1 || h.src[0].G != 2)) return SLU_EUNSUPPORTED;      // K-step 0 is the only one multiplied
+  const size_t lds = lds0 + ((shuf && h.src[0].scale) ? (size_t)h.N * 4 * h.src[0].G * 16 : 0);
+  if (lds + 3 * 32 * MB * 4 > 160 * 1024) return -1;      // the table does not fit: the tiled SCALED kernel
   RingArgs a{};
+  a.shuf = shuf ? 1 : 0;
+  a.sc0 = shuf ? h.src[0].scale : nullptr;
   a.x = h.src[0].ptr; a.G0 = h.src[0].G;
   a.x1 = h.nsrc > 1 ? h.src[1].ptr : h.src[0].ptr; a.G1 = h.nsrc > 1 ? h.src[1].G : 0;
   a.wpack = h.wpack; a.bias = h.bias; a.bn_a = h.bn_a; a.bn_b = h.bn_b;
@@ -1514,9 +1623,12 @@ bool ring3_ok(const slu_conv_h8_desc* d, const H8Args& a) {
   if (off || d->ksize != 3 || d->pad != d->dil || (d->dil != 1 && d->dil != 2) || a.nsrc < 1 || a.nsrc > 2) return false;
   int gsum = 0;
   for (int s = 0; s < a.nsrc; ++s) {
-    if (a.src[s].scale || a.src[s].nb) return false;
+    if ((a.src[s].scale && !a.src[s].shuf) || a.src[s].nb) return false;
     gsum += a.src[s].G;
   }
+  // in-place PixelShuffle: the 80 -> 32 instantiation with exactly ONE shuffled K-step (64 stored channels -> blocks 0, 1): the kernel
+  // stages any K-step of source 0 through the shuffle but multiplies K-step 0 only
+  if (a.src[0].shuf && !(a.nsrc == 2 && a.Gin == 10 && a.src[0].G == 2)) return false;
   if (gsum != a.Gin || (a.nsrc == 2 && (a.src[0].G & 1)) || a.out_f32 || d->resid || (a.has_act & ~1)) return false;
   if ((a.has_act & 1) && !(a.slope >= 0.0f && a.slope <= 1.0f)) return false;      // LeakyReLU as max(t, slope t)
   return (a.Cout == 32 || a.Cout == 64) && ((a.Gin == 4 || a.Gin == 8) || (a.Gin == 10 && a.Cout == 32 && d->dil == 1));
@@ -1709,6 +1821,14 @@ int conv_h8_dispatch(const slu_conv_h8_desc* d, const SluEmit& e) {
   H8Args a{};
   const int rc = fill_h8(d, a);
   if (rc != SLU_OK) return rc;
+  if (a.src[0].shuf) {      // read in place by ring3_h8_kernel<1, 1, 5, 1, 4> or by the SCALED 3x3 tiled kernels; anything else: slu_pixel_shuffle_h8
+    if (ring3_ok(d, a)) {
+      const int rc2 = launch_ring3_any(a, d, e);
+      if (rc2 != -1) return rc2;
+    }
+    if (!any_scale(d) || d->ksize != 3 || d->dil != 1 || d->pad != 1 || a.out_f32) return SLU_EUNSUPPORTED;
+    return launch_h8_family<3, 1, 1>(a, d, choose_h8(a), true, e);
+  }
   if (gemm1x1_ok(d, a)) return a.Cout == 128 ? launch_gemm1x1<2, GEMM1X1_D128>(a, d, e) : launch_gemm1x1<4, GEMM1X1_D256>(a, d, e);
   if (stream_ok(d, a)) {
     if (a.nmblk <= 2) {

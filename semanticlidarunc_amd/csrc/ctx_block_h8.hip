@@ -38,12 +38,13 @@ typedef float float2v __attribute__((ext_vector_type(2)));
 namespace {
 
 struct CtxArgs {
-  const uint4* x;              // h8 [N][Gin][H][W]
+  const uint4* x;              // h8 [N][Gin][H][W], or [nb][Gin][H][W] when nb > 0
   const uint4 *w1, *w2, *w3;   // packed weights: [nks1][1][64], [2][9][64], [2][9][64] records
   const float *b1, *b2, *bn1_a, *bn1_b, *b3, *bn2_a, *bn2_b;      // [32] fp32 or nullptr
   float slope;                 // LeakyReLU slope of the three activations
   uint2* out;                  // h8 [N][4][H][W] as 8-byte half records
   int N, H, W, Gin;
+  int nb;                      // > 0: x holds nb images and output image n reads image n % nb (the stacked MC passes of one batch)
   int strips_x, nseg, seg_rows;  // strips of TW columns; row segments of seg_rows rows (a multiple of R) per strip
 };
 
@@ -162,7 +163,7 @@ __global__ __launch_bounds__(64 * NWAVE, 2) void ctx_h8_kernel(const CtxArgs a) 
   const int i_w1 = opaque(OFF_W1 + lane), i_w2 = opaque(OFF_W2 + lane), i_w3 = opaque(OFF_W3 + lane), i_epi = opaque(OFF_EPI + hh);
 
   // one band: image n, strip columns [x0, x0 + 64), output rows [y0, y0 + R), band j of the segment that ends at row r1
-  struct Band { int x0, y0, n, j, r1; };
+  struct Band { int x0, y0, n, xn, j, r1; };      // xn: the image of x that output image n reads
   auto decode = [&](int t) {
     Band p;
     const int tx = t % a.strips_x;
@@ -170,6 +171,7 @@ __global__ __launch_bounds__(64 * NWAVE, 2) void ctx_h8_kernel(const CtxArgs a) 
     p.x0 = tx * TW;
     p.y0 = (t % a.nseg) * a.seg_rows;
     p.n = t / a.nseg;
+    p.xn = a.nb > 0 ? p.n % a.nb : p.n;
     p.j = 0;
     p.r1 = min(a.H, p.y0 + a.seg_rows);
     return p;
@@ -193,7 +195,7 @@ __global__ __launch_bounds__(64 * NWAVE, 2) void ctx_h8_kernel(const CtxArgs a) 
       for (int k = 0; k < NKS1; ++k) {
         const int g = 2 * k + hh;
         const bool ok = in && g < a.Gin;
-        xr[i][k] = *(ok ? a.x + (long long)(((size_t)bd.n * a.Gin + g) * HW) + org + p1_goff[i] : &g_zero_rec_c);
+        xr[i][k] = *(ok ? a.x + (long long)(((size_t)bd.xn * a.Gin + g) * HW) + org + p1_goff[i] : &g_zero_rec_c);
       }
     }
   };
@@ -495,6 +497,7 @@ extern "C" int slu_ctx_block_h8_fwd(const slu_ctx_block_h8_desc* d, slu_stream_t
   if (!slu_ctx_block_h8_supported(d->Cin, d->C, d->H, d->W)) return SLU_EUNSUPPORTED;
   if (!(d->slope >= 0.0f && d->slope <= 1.0f)) return SLU_EINVAL;      // LeakyReLU as max(t, slope t)
   if (d->x == d->out) return SLU_EINVAL;                                  // strips read their neighbours' halo
+  if (d->nbatch < 0 || (d->nbatch > 0 && d->N % d->nbatch)) return SLU_EINVAL;
   CtxArgs a{};
   a.x = reinterpret_cast<const uint4*>(d->x);
   a.w1 = reinterpret_cast<const uint4*>(d->w1);
@@ -504,6 +507,7 @@ extern "C" int slu_ctx_block_h8_fwd(const slu_ctx_block_h8_desc* d, slu_stream_t
   a.slope = d->slope;
   a.out = reinterpret_cast<uint2*>(d->out);
   a.N = d->N; a.H = d->H; a.W = d->W; a.Gin = (d->Cin + 7) / 8;
+  a.nb = d->nbatch;
   hipStream_t st = slu_stream(stream);
   return d->Cin <= 16 ? launch_ctx<1>(a, st) : launch_ctx<2>(a, st);
 }

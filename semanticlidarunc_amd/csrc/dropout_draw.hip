@@ -44,8 +44,11 @@ __global__ __launch_bounds__(256) void dropout_draw_kernel(const slu_dropout_sit
     while (o + 1 < nout && e >= outs[o + 1].begin) ++o;         // (a handful of outputs: linear search)
     const slu_dropout_out d = outs[o];
     const long long r = e - d.begin;
-    const int c = (int)(r % d.C);
+    int c = (int)(r % d.C);
     const long long n = r / d.C;
+    // shuffled == 2: the table is written in the STORED order of a tensor whose consumer reads it through PixelShuffle(2) in place
+    // (slu_h8_src.shuffle): position c = slot k of stored block 4 go + sub holds the multiplier of channel 32 go + 4 k + sub
+    if (d.shuffled == 2) c = 32 * (c >> 5) + 4 * (c & 7) + ((c >> 3) & 3);
     float v = 1.0f;
     if (d.site_a >= 0) v *= site_mult(sites, d.site_a, n * sites[d.site_a].C + d.off_a + c, seed, offset);
     // b and c act on the PixelShuffle'd tensor: stored channel c feeds shuffled channel c / 4

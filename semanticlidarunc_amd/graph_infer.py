@@ -39,7 +39,8 @@ class GraphedMCPredict:
             torch.cuda.current_stream().wait_stream(side)
             self._scales = None
             self._plan = None
-            drawn = model._predraw_dropout(n, example.device)            # None: no Dropout2d site is active (a deterministic model)
+            # (tables in the order the captured forward reads them; None: no Dropout2d site is active, a deterministic model)
+            drawn = model._predraw_dropout(n, example.device, sx_stored=model._in_place_blocks(n, example.shape[2], example.shape[3]))
             if drawn is not None:
                 plan = model.__dict__.get("_drop_plan")
                 if plan is None:

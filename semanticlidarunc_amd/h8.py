@@ -21,6 +21,62 @@ class H8Source(NamedTuple):
     tensor: torch.Tensor                    # [nimg, G, H, W, 8] fp16
     scale: Optional[torch.Tensor] = None    # [N, 8 G] fp32 multiplier (folded Dropout2d) or None
     nbatch: int = 0                         # > 0: tensor holds nbatch images, output image n reads image n % nbatch
+    shuffle: bool = False                   # first source only: nn.PixelShuffle(2) of `tensor` ([N, G, H/2, W/2, 8], channels stored in
+                                            # shuffle order: shuffle_store_perm), read in place; scale [N, 8 G] in stored order.
+                                            # Covered: the 80 -> 32 3x3 layer (ring3) and 3x3 layers with multipliers (slu.h)
+
+
+def shuffle_store_perm(channels: int, device=None) -> torch.Tensor:
+    """perm[p] = the channel that position p of a tensor STORED IN SHUFFLE ORDER holds: stored block 4 go + sub, slot k <- channel
+    32 go + 4 k + sub (sub = 2 i + j), so that block go of nn.PixelShuffle(2)(t) at pixel (2 h + i, 2 w + j) is the stored record of block
+    4 go + sub at (h, w).  A producer stores t[:, perm] by permuting the rows of its weight, bias and folded BatchNorm with perm."""
+    if channels % 32:
+        raise RuntimeError(f"shuffle_store_perm: {channels} channels are not whole groups of 32")
+    key = (int(channels), None if device is None else str(device))
+    perm = _STORE_PERM.get(key)
+    if perm is None:
+        p = torch.arange(channels, device=device)
+        perm = _STORE_PERM[key] = 32 * (p // 32) + 4 * (p % 8) + (p // 8) % 4
+    return perm
+
+
+_STORE_PERM = {}
+
+
+_SHUFFLE_OK = {}
+
+
+def conv_shuffle_in_place_supported(*args, **kw) -> bool:
+    """conv_shuffle_in_place_kernel(...) is not None."""
+    return conv_shuffle_in_place_kernel(*args, **kw) is not None
+
+
+def conv_shuffle_in_place_kernel(n: int, h: int, w: int, c_stored: int, c_skip: int, cout: int, ksize: int, dil: int, pad: int,
+                                 scaled: bool, skip_scaled: bool = False, skip_nbatch: int = 0) -> Optional[str]:
+    """Does slu_conv2d_h8_fwd read a first source of `c_stored` stored channels through PixelShuffle in place for this layer (output n x h x w,
+    a second source of c_skip channels)?  Asked of the launch's own dispatch (slu_conv2d_h8_kernel_name on a descriptor of that shape: no
+    memory is touched), cached per shape: the name of the kernel that would, or None.  Today: ring3_h8_kernel<1, 1, 5, 1, 4> (64 stored
+    channels, plain 64-channel skip, 32 outputs, >= 256 tiles) and the SCALED 3x3 conv_h8_kernel instantiations (some source carries
+    multipliers, 3 * c_stored / 32 + input blocks <= 64)."""
+    key = (n, h, w, c_stored, c_skip, cout, ksize, dil, pad, bool(scaled), bool(skip_scaled), int(skip_nbatch))
+    ok = _SHUFFLE_OK.get(key, 0)
+    if ok == 0:
+        ok = None
+        if c_stored % 64 == 0 and c_skip % 8 == 0 and h % 2 == 0 and w % 2 == 0:
+            d = ConvH8Desc()
+            fake = 1 << 20                                   # an aligned non-null address: the dispatch only tests and formats
+            d.src[0].ptr, d.src[0].scale, d.src[0].G, d.src[0].shuffle = fake, (fake if scaled else None), c_stored // 8, 1
+            d.nsrc = 1
+            if c_skip:
+                d.src[1].ptr, d.src[1].scale, d.src[1].G, d.src[1].nbatch = fake, (fake if skip_scaled else None), c_skip // 8, int(skip_nbatch)
+                d.nsrc = 2
+            d.N, d.H, d.W, d.Cout, d.ksize, d.dil, d.pad = n, h, w, cout, ksize, dil, pad
+            d.wpack, d.out, d.has_act, d.slope = fake, fake, 1, 0.01
+            buf = C.create_string_buffer(96)
+            if _lib.load().slu_conv2d_h8_kernel_name(C.byref(d), buf, 96) == 0:
+                ok = buf.value.decode()
+        _SHUFFLE_OK[key] = ok
+    return ok
 
 
 def _req_h8(t: torch.Tensor, name: str) -> torch.Tensor:
@@ -88,6 +144,11 @@ def conv2d_h8(srcs: Sequence[H8Source], wpack: torch.Tensor, cin: int, cout: int
     for i, s in enumerate(srcs):
         t = _req_h8(s.tensor, f"src[{i}]")
         sn, sg, sh, sw, _ = t.shape
+        gstored = sg
+        if s.shuffle:
+            if i != 0 or sg % 8 or s.nbatch:
+                raise RuntimeError("src[0] only may be read through PixelShuffle in place, with whole groups of 64 stored channels")
+            sg, sh, sw = sg // 4, 2 * sh, 2 * sw
         if s.nbatch:
             if i == 0 or sn != s.nbatch or n % sn:
                 raise RuntimeError(f"src[{i}]: a batch-broadcast source must follow a full-batch source and divide N")
@@ -98,9 +159,10 @@ def conv2d_h8(srcs: Sequence[H8Source], wpack: torch.Tensor, cin: int, cout: int
             raise RuntimeError(f"src[{i}]: spatial/batch size {(sn, sh, sw)} != {(n, h, w)}")
         if s.scale is not None:
             _req(s.scale, f"src[{i}].scale")
-            if tuple(s.scale.shape) != (n, 8 * sg):
-                raise RuntimeError(f"src[{i}].scale: expected {(n, 8 * sg)}, got {tuple(s.scale.shape)}")
-        d.src[i].ptr, d.src[i].scale, d.src[i].G, d.src[i].nbatch = t.data_ptr(), _ptr(s.scale), sg, int(s.nbatch)
+            if tuple(s.scale.shape) != (n, 8 * gstored):
+                raise RuntimeError(f"src[{i}].scale: expected {(n, 8 * gstored)}, got {tuple(s.scale.shape)}")
+        d.src[i].ptr, d.src[i].scale, d.src[i].G, d.src[i].nbatch = t.data_ptr(), _ptr(s.scale), gstored, int(s.nbatch)
+        d.src[i].shuffle = 1 if s.shuffle else 0
         gin += sg
         keep.append(t)
     if not 8 * (gin - 1) < cin <= 8 * gin:
@@ -144,6 +206,7 @@ def conv2d_h8(srcs: Sequence[H8Source], wpack: torch.Tensor, cin: int, cout: int
     check(lib.slu_conv2d_h8_fwd(C.byref(d), _stream()), "slu_conv2d_h8_fwd")
     e1.record()
     flops = 2.0 * cin * cout * ksize * ksize * n * h * w
+    # (a source read through PixelShuffle in place contributes cin / 4 of its stored channels at 4x the pixels: its tensor, once)
     nbytes = n * h * w * (2.0 * cin + (4.0 if out_f32_nchw else 2.0) * cout) + 2.0 * cout * cin * ksize * ksize
     ops.TIMING.append((buf.value.decode(), flops, nbytes, e0, e1, nbytes + (n * h * w * 2.0 * cout if resid is not None else 0.0)))
     ops.TIMING_TAGS.append(f"N{n} {cin}->{cout} k{ksize}d{dil} {h}x{w}")
@@ -243,13 +306,17 @@ def ctx_block_supported(cin: int, c: int, h: int, w: int) -> bool:
 
 def ctx_block_h8(x: torch.Tensor, cin: int, w1: torch.Tensor, w2: torch.Tensor, w3: torch.Tensor, bias1: Optional[torch.Tensor],
                  bias2: Optional[torch.Tensor], bn1: Optional[tuple], bias3: Optional[torch.Tensor], bn2: Optional[tuple],
-                 slope: float) -> torch.Tensor:
+                 slope: float, n_out: Optional[int] = None) -> torch.Tensor:
     """One fused ResContextBlock (slu_ctx_block_h8_fwd, SalsaNext.py:25-39):
         s = leaky(conv1x1(x) + bias1);  a1 = bn1(leaky(conv3x3(s) + bias2));  out = s + bn2(leaky(conv3x3_dil2(a1) + bias3))
-    x: h8 [N, ceil(cin/8), H, W, 8]; w1 / w2 / w3: pack_conv_weight_h8 of [32, cin, 1, 1] / [32, 32, 3, 3] / [32, 32, 3, 3]; bn*: (scale, shift)."""
+    x: h8 [N, ceil(cin/8), H, W, 8]; w1 / w2 / w3: pack_conv_weight_h8 of [32, cin, 1, 1] / [32, 32, 3, 3] / [32, 32, 3, 3]; bn*: (scale, shift).
+    n_out: a multiple of N: output image n is the block of x[n % N] (the stacked passes of an MC-dropout evaluation share their input)."""
     lib = _lib.load()
     _req_h8(x, "x")
-    n, g, h, w, _ = x.shape
+    nimg, g, h, w, _ = x.shape
+    n = nimg if n_out is None else int(n_out)
+    if n <= 0 or n % nimg:
+        raise RuntimeError(f"ctx_block_h8: n_out={n} is not a multiple of the {nimg} input images")
     if not 8 * (g - 1) < cin <= 8 * g or not ctx_block_supported(cin, 32, h, w):
         raise RuntimeError(f"ctx_block_h8: cin={cin} with {g} input blocks is not covered by the fused kernel")
     for t, nme, shape in ((w1, "w1", (32, cin, 1)), (w2, "w2", (32, 32, 3)), (w3, "w3", (32, 32, 3))):
@@ -271,6 +338,7 @@ def ctx_block_h8(x: torch.Tensor, cin: int, w1: torch.Tensor, w2: torch.Tensor, 
     d.bn1_a, d.bn1_b = _ptr(None if bn1 is None else bn1[0]), _ptr(None if bn1 is None else bn1[1])
     d.bn2_a, d.bn2_b = _ptr(None if bn2 is None else bn2[0]), _ptr(None if bn2 is None else bn2[1])
     d.slope, d.out = float(slope), out.data_ptr()
+    d.nbatch = 0 if n == nimg else nimg
     if ops.TIMING is None:
         check(lib.slu_ctx_block_h8_fwd(C.byref(d), _stream()), "slu_ctx_block_h8_fwd")
         return out
@@ -282,7 +350,8 @@ def ctx_block_h8(x: torch.Tensor, cin: int, w1: torch.Tensor, w2: torch.Tensor, 
     flops = 2.0 * (cin * 32 + 2 * 9 * 32 * 32) * px
     # SURVEY 8(d) layer-granular bytes of the three convs (each reads its input and writes its output once) vs what the fused kernel moves
     nbytes = px * 2.0 * ((8 * g + 32) + (32 + 32) + (32 + 32)) + 2.0 * (32 * cin + 2 * 9 * 32 * 32)
-    min_bytes = px * 2.0 * (8 * g + 32) + 2.0 * (32 * cin + 2 * 9 * 32 * 32)
+    # (a broadcast input is counted once: its nimg images, not the n reads of them)
+    min_bytes = float(h * w) * 2.0 * (nimg * 8 * g + n * 32) + 2.0 * (32 * cin + 2 * 9 * 32 * 32)
     ops.TIMING.append((f"ctx_h8_kernel<{1 if cin <= 16 else 2}>", flops, nbytes, e0, e1, min_bytes))
     ops.TIMING_TAGS.append(f"N{n} {cin}->32 k1 + 32->32 k3d1 + 32->32 k3d2 fused {h}x{w}")
     return out

@@ -1382,7 +1382,8 @@ def range_image_split(img: torch.Tensor, normals: Optional[torch.Tensor], range_
 # Dropout2d multipliers of a whole MC evaluation in one launch (csrc/dropout_draw.hip)
 # ------------------------------------------------------------------------------------------------
 class DropoutPlan:
-    """Device tables for slu_dropout_draw: `sites` = [(C, p, active)], `outs` = [(key, C, (site, offset) x <= 3, shuffled)] for batch size n."""
+    """Device tables for slu_dropout_draw: `sites` = [(C, p, active)], `outs` = [(key, C, (site, offset) x <= 3, shuffled)] for batch size n
+    (shuffled: 0 / 1, or 2 = shuffled and written in the stored order of a tensor read through PixelShuffle in place)."""
 
     def __init__(self, n: int, sites, outs, device):
         import numpy as np
@@ -1399,7 +1400,7 @@ class DropoutPlan:
         e, self.slices = 0, []
         for i, (key, c, refs, shuffled) in enumerate(outs):
             refs = list(refs) + [(-1, 0)] * (3 - len(refs))
-            ot[i] = (e, c, refs[0][0], refs[0][1], refs[1][0], refs[1][1], refs[2][0], refs[2][1], 1 if shuffled else 0)
+            ot[i] = (e, c, refs[0][0], refs[0][1], refs[1][0], refs[1][1], refs[2][0], refs[2][1], int(shuffled))
             self.slices.append((key, e, c))
             e += self.n * c
         self.total = e

@@ -49,6 +49,12 @@ _FUSE_CTX = os.environ.get("SLU_FUSE_CTX", "1") != "0"
 _PACK_MULTI = os.environ.get("SLU_PACK_MULTI", "1") != "0"          # A/B: training step packs all conv weights in one launch
 # half-precision MC inference: head conv + softmax / entropy / MI reduction over the T passes as one launch (0: logits + slu_mc_reduce)
 _FUSE_HEAD_MC = os.environ.get("SLU_FUSE_HEAD_MC", "1") != "0"
+# half-precision MC inference, every pass recomputed: the first context block reads the B distinct input images in place, image n % B
+# for stacked image n (0: x.repeat(T) is materialised and converted to h8 T times; A/B switch)
+_MC_BCAST_INPUT = os.environ.get("SLU_MC_BCAST_INPUT", "1") != "0"
+# half-precision inference: UpBlock.conv1 reads its PixelShuffle'd input in place -- the producer stores its channels in shuffle order
+# (h8.shuffle_store_perm) -- where the conv kernel covers it (SalsaNext._in_place_blocks); 0: pixel_shuffle_h8 materialises it (A/B switch)
+_SHUFFLE_IN_PLACE = os.environ.get("SLU_SHUFFLE_IN_PLACE", "1") != "0"
 
 
 def set_train_conv_precision(precision: str) -> None:
@@ -74,10 +80,11 @@ class _Prepared:
     """Device-side derived constants of one conv (+ its BatchNorm): the MFMA-ordered weight image and
     the folded BN affine.  Rebuilt lazily whenever the owning parameters/buffers change."""
 
-    __slots__ = ("key", "wpack", "bn_key", "bn_a", "bn_b", "dgrad", "key16", "wpack16", "key8", "wpack8")
+    __slots__ = ("key", "wpack", "bn_key", "bn_a", "bn_b", "dgrad", "key16", "wpack16", "key8", "wpack8", "key8p", "wpack8p", "vecp_key", "vecp")
 
     def __init__(self):
         self.key = self.bn_key = None
+        self.key8p = self.wpack8p = self.vecp_key = self.vecp = None      # output channels in shuffle order (h8.shuffle_store_perm)
         self.wpack = self.bn_a = self.bn_b = None
         self.key16 = self.wpack16 = None
         self.key8 = self.wpack8 = None
@@ -108,17 +115,37 @@ class _FusedBlock(nn.Module):
             p.bn_key = bkey
         return p.bn_a, p.bn_b
 
-    def _run_h8(self, p: _Prepared, conv: nn.Conv2d, bn, srcs, resid, act, out_f32):
-        """Half-precision inference form: sources / residual / result are h8 tensors (see h8.py)."""
+    def _permuted_h8(self, p: _Prepared, conv: nn.Conv2d, bn):
+        """(wpack, bias, bn_a, bn_b) of a conv that stores its output channels in shuffle order: the rows of the weight, the bias and the
+        folded BatchNorm permuted at pack time, cached per weight / BatchNorm version like wpack8.  Every value is computed as before and
+        only stored elsewhere; a residual added to it must be permuted the same way."""
         wkey = _tkey(conv.weight)
-        if p.key8 != wkey:
-            p.wpack8 = h8.pack_conv_weight_h8(conv.weight.detach().contiguous())
-            p.key8 = wkey
+        if p.key8p != wkey:
+            perm = h8.shuffle_store_perm(conv.out_channels, conv.weight.device)
+            p.wpack8p = h8.pack_conv_weight_h8(conv.weight.detach().index_select(0, perm).contiguous())
+            p.key8p = wkey
         bn_a, bn_b = self._folded_bn(p, bn)
-        return h8.conv2d_h8([h8.H8Source(s.tensor, s.scale, s.nbatch) for s in srcs], p.wpack8, conv.in_channels,
-                            conv.out_channels, conv.kernel_size[0], conv.dilation[0], conv.padding[0],
-                            bias=None if conv.bias is None else conv.bias.detach(), slope=_SLOPE if act else None,
-                            bn_a=bn_a, bn_b=bn_b, resid=resid, out_f32_nchw=out_f32)
+        vkey = (p.bn_key if bn is not None else None, None if conv.bias is None else _tkey(conv.bias))
+        if p.vecp_key != vkey:
+            perm = h8.shuffle_store_perm(conv.out_channels, conv.weight.device)
+            p.vecp = tuple(None if v is None else v.detach().index_select(0, perm).contiguous() for v in (conv.bias, bn_a, bn_b))
+            p.vecp_key = vkey
+        return (p.wpack8p,) + p.vecp
+
+    def _run_h8(self, p: _Prepared, conv: nn.Conv2d, bn, srcs, resid, act, out_f32, out_perm=False):
+        """Half-precision inference form: sources / residual / result are h8 tensors (see h8.py)."""
+        if out_perm:
+            wpack, bias, bn_a, bn_b = self._permuted_h8(p, conv, bn)
+        else:
+            wkey = _tkey(conv.weight)
+            if p.key8 != wkey:
+                p.wpack8 = h8.pack_conv_weight_h8(conv.weight.detach().contiguous())
+                p.key8 = wkey
+            wpack, bias = p.wpack8, None if conv.bias is None else conv.bias.detach()
+            bn_a, bn_b = self._folded_bn(p, bn)
+        return h8.conv2d_h8([h8.H8Source(s.tensor, s.scale, s.nbatch, bool(s.pixel_shuffle)) for s in srcs], wpack,
+                            conv.in_channels, conv.out_channels, conv.kernel_size[0], conv.dilation[0], conv.padding[0],
+                            bias=bias, slope=_SLOPE if act else None, bn_a=bn_a, bn_b=bn_b, resid=resid, out_f32_nchw=out_f32)
 
     def _prepared(self, conv: nn.Conv2d) -> _Prepared:
         cache: Dict[str, _Prepared] = self.__dict__.setdefault("_prep", {})
@@ -133,19 +160,31 @@ class _FusedBlock(nn.Module):
                     and conv_b.kernel_size == (1, 1) and conv_b.in_channels == 3 * c and conv_b.out_channels == c
                     and c <= _FUSE_TAIL_MAX_C and h8.conv_tail_supported(c, a1.shape[2], a1.shape[3]))
 
-    def _run_tail(self, conv_a: nn.Conv2d, bn_a, conv_b: nn.Conv2d, bn_b, a1, a2, resid=None, shortcut=None):
+    def _run_tail(self, conv_a: nn.Conv2d, bn_a, conv_b: nn.Conv2d, bn_b, a1, a2, resid=None, shortcut=None, out_perm=False):
         """The last two layers of a block, `conv_b(cat(a1, a2, conv_a(a2)))`, each followed by LeakyReLU and eval BatchNorm.
         Half-precision inference with 32 / 64 channels: one fused launch that keeps conv_a's output on chip (csrc/conv_tail_h8.hip);
-        otherwise the two layers one after the other."""
+        otherwise the two layers one after the other.  out_perm (half precision, no residual): the block's output channels are stored in
+        shuffle order for a consumer that reads them through PixelShuffle in place."""
+        if out_perm and a1.dtype != torch.float16:
+            raise RuntimeError("a block output in shuffle order exists on the half-precision inference path only")
+        if out_perm and shortcut is not None and self._tail_is_fused(conv_a, conv_b, a1):
+            raise RuntimeError("a block output in shuffle order: the shortcut computed inside the fused tail is not permuted")
         if self._tail_is_fused(conv_a, conv_b, a1):
-            packs, folded = [], []
-            for conv, bn in ((conv_a, bn_a), (conv_b, bn_b)):
+            packs, folded, biases = [], [], []
+            for conv, bn, perm in ((conv_a, bn_a, False), (conv_b, bn_b, out_perm)):
                 p = self._prepared(conv)
+                if perm:
+                    wp, bias, fa, fb = self._permuted_h8(p, conv, bn)
+                    packs.append(wp)
+                    biases.append(bias)
+                    folded.append(None if fa is None else (fa, fb))
+                    continue
                 wkey = _tkey(conv.weight)
                 if p.key8 != wkey:
                     p.wpack8 = h8.pack_conv_weight_h8(conv.weight.detach().contiguous())
                     p.key8 = wkey
                 packs.append(p.wpack8)
+                biases.append(None if conv.bias is None else conv.bias.detach())
                 fa, fb = self._folded_bn(p, bn)
                 folded.append(None if fa is None else (fa, fb))
             sc = None
@@ -157,21 +196,22 @@ class _FusedBlock(nn.Module):
                     p.wpack8 = h8.pack_conv_weight_h8(sconv.weight.detach().contiguous())
                     p.key8 = wkey
                 sc = (sx, p.wpack8, None if sconv.bias is None else sconv.bias.detach(), _SLOPE, sconv.in_channels)
-            return h8.conv_tail_h8(a1, a2, packs[0], packs[1], None if conv_a.bias is None else conv_a.bias.detach(), _SLOPE, folded[0],
-                                   None if conv_b.bias is None else conv_b.bias.detach(), _SLOPE, folded[1], resid=resid, shortcut=sc)
+            return h8.conv_tail_h8(a1, a2, packs[0], packs[1], biases[0], _SLOPE, folded[0], biases[1], _SLOPE, folded[1], resid=resid, shortcut=sc)
         if shortcut is not None:
-            resid = self._run(shortcut[1], None, [ConvSource(shortcut[0])])
+            resid = self._run(shortcut[1], None, [ConvSource(shortcut[0])], out_perm=out_perm)
         a3 = self._run(conv_a, bn_a, [ConvSource(a2)])
-        return self._run(conv_b, bn_b, [ConvSource(a1), ConvSource(a2), ConvSource(a3)], resid=resid)
+        return self._run(conv_b, bn_b, [ConvSource(a1), ConvSource(a2), ConvSource(a3)], resid=resid, out_perm=out_perm)
 
-    def _run(self, conv: nn.Conv2d, bn: Optional[nn.BatchNorm2d], srcs, resid=None, act=True, out_f32=False):
+    def _run(self, conv: nn.Conv2d, bn: Optional[nn.BatchNorm2d], srcs, resid=None, act=True, out_f32=False, out_perm=False):
         cache: Dict[str, _Prepared] = self.__dict__.setdefault("_prep", {})
         name = str(id(conv))
         p = cache.get(name)
         if p is None:
             p = cache[name] = _Prepared()
         if srcs[0].tensor.dtype == torch.float16:
-            return self._run_h8(p, conv, bn, srcs, resid, act, out_f32)
+            return self._run_h8(p, conv, bn, srcs, resid, act, out_f32, out_perm)
+        if out_perm:
+            raise RuntimeError("an output in shuffle order exists on the half-precision inference path only")
         wkey = _tkey(conv.weight)
         if p.key != wkey:
             p.wpack = ops.pack_conv_weight(conv.weight.detach().contiguous())
@@ -237,9 +277,13 @@ class ResContextBlock(_FusedBlock):
         self.conv3 = nn.Conv2d(out_filters, out_filters, 3, dilation=2, padding=2)
         self.bn2 = nn.BatchNorm2d(out_filters)
 
-    def forward(self, x):
-        if (_FUSE_CTX and x.dtype == torch.float16 and x.dim() == 5 and self.conv1.out_channels == 32
-                and h8.ctx_block_supported(self.conv1.in_channels, 32, x.shape[2], x.shape[3])):
+    def fused_for(self, h: int, w: int) -> bool:
+        """Half-precision inference at h x w runs this block as the one fused launch."""
+        return bool(_FUSE_CTX and self.conv1.out_channels == 32 and h8.ctx_block_supported(self.conv1.in_channels, 32, h, w))
+
+    def forward(self, x, n_out=None):
+        """n_out (fused half-precision launch only): a multiple of x's batch; output image n is the block of x[n % batch]."""
+        if x.dtype == torch.float16 and x.dim() == 5 and self.fused_for(x.shape[2], x.shape[3]):
             # half-precision inference: the whole block as one launch, shortcut and a1 never leave the CU (csrc/ctx_block_h8.hip)
             packs, folded = [], []
             for conv, bn in ((self.conv1, None), (self.conv2, self.bn1), (self.conv3, self.bn2)):
@@ -252,7 +296,10 @@ class ResContextBlock(_FusedBlock):
                 fa, fb = self._folded_bn(p, bn)
                 folded.append(None if fa is None else (fa, fb))
             b = [None if c.bias is None else c.bias.detach() for c in (self.conv1, self.conv2, self.conv3)]
-            return h8.ctx_block_h8(x, self.conv1.in_channels, packs[0], packs[1], packs[2], b[0], b[1], folded[1], b[2], folded[2], _SLOPE)
+            return h8.ctx_block_h8(x, self.conv1.in_channels, packs[0], packs[1], packs[2], b[0], b[1], folded[1], b[2], folded[2], _SLOPE,
+                                   n_out=n_out)
+        if n_out is not None and n_out != x.shape[0]:
+            raise RuntimeError("ResContextBlock: a broadcast input needs the fused half-precision launch")
         shortcut = self._run(self.conv1, None, [ConvSource(x)])
         a1 = self._run(self.conv2, self.bn1, [ConvSource(shortcut)])
         return self._run(self.conv3, self.bn2, [ConvSource(a1)], resid=shortcut)
@@ -275,24 +322,26 @@ class ResBlock(_FusedBlock):
         self.bn4 = nn.BatchNorm2d(out_filters)
         self.dropout = nn.Dropout2d(p=dropout_rate)
 
-    def features(self, x):
-        """The block up to (not including) dropout / pooling: deterministic given x."""
+    def features(self, x, out_perm=False):
+        """The block up to (not including) dropout / pooling: deterministic given x.  out_perm (half precision, resBlock5): the output
+        channels are stored in shuffle order for an UpBlock that reads them in place -- conv5's rows and the shortcut conv's rows (its
+        residual) permuted alike."""
         src = [ConvSource(x)]
         # half precision, 32 -> 64 (resBlock1): the shortcut conv runs inside the fused tail, from x, and its tensor never exists
         fuse_sc = (_FUSE_SHORTCUT and x.dtype == torch.float16 and x.dim() == 5 and x.shape[1] * 8 == self.conv1.in_channels
-                   and h8.conv_tail_shortcut_supported(self.conv1.out_channels, self.conv1.in_channels))
-        shortcut = None if fuse_sc else self._run(self.conv1, None, src)
+                   and h8.conv_tail_shortcut_supported(self.conv1.out_channels, self.conv1.in_channels) and not out_perm)
+        shortcut = None if fuse_sc else self._run(self.conv1, None, src, out_perm=out_perm)
         a1 = self._run(self.conv2, self.bn1, src)
         a2 = self._run(self.conv3, self.bn2, [ConvSource(a1)])
         if fuse_sc and self._tail_is_fused(self.conv4, self.conv5, a1):
             return self._run_tail(self.conv4, self.bn3, self.conv5, self.bn4, a1, a2, shortcut=(x, self.conv1))
         if shortcut is None:
-            shortcut = self._run(self.conv1, None, src)
-        return self._run_tail(self.conv4, self.bn3, self.conv5, self.bn4, a1, a2, resid=shortcut)
+            shortcut = self._run(self.conv1, None, src, out_perm=out_perm)
+        return self._run_tail(self.conv4, self.bn3, self.conv5, self.bn4, a1, a2, resid=shortcut, out_perm=out_perm)
 
-    def forward(self, x, _scales=None, _name=""):
+    def forward(self, x, _scales=None, _name="", out_perm=False):
         """pooling: (pooled, full_res);  else: (full_res, deferred dropout multiplier or None)."""
-        full = self.features(x)
+        full = self.features(x, out_perm)
         s = None
         if self.drop_out:
             s = _draw(self.dropout, full.shape[0], self.conv5.out_channels, full.device, _scales, _name + ".dropout")
@@ -333,9 +382,32 @@ class UpBlock(_FusedBlock):
             sx = _mul(sx, up.repeat_interleave(4, dim=1))
         return sx, ss
 
-    def forward(self, x, skip, x_scale=None, _scales=None, _name="", skip_nbatch=0):
+    def reads_in_place(self, n: int, h: int, w: int, skip_nbatch: int = 0, scaled: bool = True) -> bool:
+        """Half-precision inference on n stored inputs of h x w: conv1 reads the PixelShuffle'd input in place, so the producer has to
+        store its channels in shuffle order.  Blocks with live dropout1 / dropout2 multiply the skip too, which the in-place form does
+        not cover: the question goes to the conv's own dispatch (h8.conv_shuffle_in_place_supported)."""
+        if not _SHUFFLE_IN_PLACE:
+            return False
+        ask = lambda sc, skip_sc: h8.conv_shuffle_in_place_kernel(n, 2 * h, 2 * w, self.in_filters, self.conv1.in_channels - self.in_filters // 4,
+                                                                  self.out_filters, 3, 1, 1, sc, skip_sc, skip_nbatch)
+        if self.drop_out:
+            # the tiled kernels read in place in their SCALED form, which these blocks run anyway when multipliers are live (`scaled`): the same
+            # instantiation as with a materialised shuffle; with and without dropout2's multipliers on the skip
+            return bool(scaled and ask(True, False) and ask(True, True))
+        # no multipliers of its own (upBlock4): only where the deep-ring kernel takes the layer, with or without the producer's multiplier
+        return all((ask(sc, False) or "").startswith("ring3_h8_kernel") for sc in (True, False))
+
+    def _ones(self, n, c, dev):
+        t = self.__dict__.get("_ones_table")
+        if t is None or tuple(t.shape) != (n, c) or t.device != dev:
+            t = self.__dict__["_ones_table"] = torch.ones((n, c), dtype=torch.float32, device=dev)
+        return t
+
+    def forward(self, x, skip, x_scale=None, _scales=None, _name="", skip_nbatch=0, x_perm=False, out_perm=False):
         """x is read through PixelShuffle(2); x_scale is the producer's deferred dropout multiplier.
         skip_nbatch > 0: `skip` holds that many images shared by the stacked MC passes.
+        x_perm (half precision): x's channels are stored in shuffle order and conv1 reads it in place (reads_in_place); out_perm: this
+        block stores its own output that way for the next one.
         Returns (out, deferred multiplier of dropout3 or None)."""
         n, cx, dev = x.shape[0], self.in_filters, x.device
         cu, cs = cx // 4, self.conv1.in_channels - cx // 4
@@ -346,8 +418,19 @@ class UpBlock(_FusedBlock):
                                           _draw(self.dropout2, n, cu + cs, dev, _scales, _name + ".dropout2"))
         else:
             sx, ss = x_scale, None
-        if x.dtype == torch.float16:
+        if x.dtype == torch.float16 and x_perm:
+            # h8, in place: the conv's staging fetches the shuffled records from the stored tensor and multiplies after the LDS read
+            if sx is not None and not (_scales is not None and _scales.get(_name + "._sx_stored")):
+                sx = sx.index_select(1, h8.shuffle_store_perm(cx, dev))      # multipliers given per channel: into the stored order
+            if sx is None and not h8.conv_shuffle_in_place_supported(n, 2 * x.shape[2], 2 * x.shape[3], cx, cs, self.out_filters, 3, 1, 1, False,
+                                                                     ss is not None, skip_nbatch):
+                sx = self._ones(n, cx, dev)      # no multiplier at all (deterministic pass): the tiled kernels read in place in their SCALED form only
+            e1 = self._run(self.conv1, self.bn1, [ConvSource(x, None if sx is None else sx.contiguous(), True),
+                                                  ConvSource(skip, ss, False, skip_nbatch)])
+        elif x.dtype == torch.float16:
             # h8: PixelShuffle is a (tiny) data-movement launch that also applies the producer's multiplier and dropout1/2
+            if _scales is not None and _scales.get(_name + "._sx_stored"):      # SalsaNext._in_place_blocks owns that decision for both
+                raise RuntimeError(f"{_name}: multipliers drawn in stored order for a block that does not read in place")
             xs = h8.pixel_shuffle_h8(x, None if sx is None else sx.contiguous())
             e1 = self._run(self.conv1, self.bn1, [ConvSource(xs), ConvSource(skip, ss, False, skip_nbatch)])
         else:
@@ -355,7 +438,7 @@ class UpBlock(_FusedBlock):
                 sx = sx.contiguous()
             e1 = self._run(self.conv1, self.bn1, [ConvSource(x, sx, True), ConvSource(skip, ss, False, skip_nbatch)])
         e2 = self._run(self.conv2, self.bn2, [ConvSource(e1)])
-        out = self._run_tail(self.conv3, self.bn3, self.conv4, self.bn4, e1, e2)
+        out = self._run_tail(self.conv3, self.bn3, self.conv4, self.bn4, e1, e2, out_perm=out_perm)
         s3 = None
         if self.drop_out:
             s3 = _draw(self.dropout3, n, self.out_filters, dev, _scales, _name + ".dropout3")
@@ -408,7 +491,12 @@ class SalsaNext(_FusedBlock):
         b = x.shape[0]
         self.__dict__["_features_only"] = True
         try:
-            u1 = self.forward_mc(x, T, scales) if share_prefix else self._forward(x.repeat(int(T), 1, 1, 1), scales)
+            if share_prefix:
+                u1 = self.forward_mc(x, T, scales)
+            elif _MC_BCAST_INPUT and int(T) > 1 and x.dim() == 4 and self.downCntx.fused_for(x.shape[2], x.shape[3]):
+                u1 = self._forward(x, scales, passes=int(T))      # the B images are converted once; every conv still runs T * B times
+            else:
+                u1 = self._forward(x.repeat(int(T), 1, 1, 1), scales)
         finally:
             self.__dict__["_features_only"] = False
         p = self._prepared(self.logits)
@@ -438,7 +526,7 @@ class SalsaNext(_FusedBlock):
         x = x.contiguous().float()
         half = _CONV_PRECISION == "f16"
         if scales is None and not torch.cuda.is_current_stream_capturing():
-            scales = self._predraw_dropout(n, x.device)
+            scales = self._predraw_dropout(n, x.device)      # upBlock4's skip is a broadcast here: its shuffle stays materialised
         if half:
             x = h8.to_h8(x)
         d = self.downCntx3(self.downCntx2(self.downCntx(x)))
@@ -469,15 +557,28 @@ class SalsaNext(_FusedBlock):
                       ("upBlock2", "dropout1", 32), ("upBlock2", "dropout2", 288), ("upBlock2", "dropout3", 128),
                       ("upBlock3", "dropout1", 32), ("upBlock3", "dropout2", 160), ("upBlock3", "dropout3", 64))
 
-    def _predraw_dropout(self, n: int, device):
+    def _in_place_blocks(self, n: int, h: int, w: int, scaled=None):
+        """The UpBlocks that read their PixelShuffle'd input in place for n stacked images of h x w in `_forward`: THE decision that both
+        the producer's channel order / the consumer's addressing (`_forward`) and the order of the drawn `_sx` tables (`_predraw_dropout`,
+        also when a caller such as graph_infer draws ahead of the forward) follow.  `forward_mc` never reads in place."""
+        if not (_CONV_PRECISION == "f16" and self._inference_only()):
+            return ()
+        if scaled is None:      # multipliers are live: some Dropout2d site samples (a caller that hands in its own tables says so)
+            scaled = any(m.training and m.p > 0.0 for m in self.modules() if isinstance(m, nn.Dropout2d))
+        return tuple(blk for blk, f in (("upBlock1", 16), ("upBlock2", 8), ("upBlock3", 4), ("upBlock4", 2))
+                     if getattr(self, blk).reads_in_place(n, h // f, w // f, scaled=scaled))
+
+    def _predraw_dropout(self, n: int, device, sx_stored=()):
         """Inference with live Dropout2d (MC sampling): draw the multipliers of all 13 sites up front, through the real nn.Dropout2d
         children and in the reference's call order (same RNG consumption as drawing them inside the blocks), on a side stream, so the
-        ~60 tiny launches overlap the context blocks instead of sitting between the convs.  None when no site is active."""
+        ~60 tiny launches overlap the context blocks instead of sitting between the convs.  None when no site is active.
+        sx_stored: the UpBlocks whose `_sx` is written in the stored (shuffle) order of their input and flagged `<block>._sx_stored`:
+        `_in_place_blocks(n, h, w)` for a `_forward` on that shape, nothing otherwise."""
         sites = [(f"{blk}.{name}", getattr(getattr(self, blk), name), c) for blk, name, c in self._DROPOUT_SITES]
         if not any(d.training and d.p > 0.0 for _, d, _ in sites):
             return None
         if _DROPOUT_KERNEL:
-            return self._predraw_dropout_kernel(n, device, sites)
+            return self._predraw_dropout_kernel(n, device, sites, tuple(sx_stored))
         main = torch.cuda.current_stream(device)
         side = self.__dict__.get("_drop_stream")
         if side is None or side.device != device:
@@ -503,12 +604,12 @@ class SalsaNext(_FusedBlock):
         self.__dict__["_drop_event"] = side.record_event()
         return out
 
-    def _predraw_dropout_kernel(self, n: int, device, sites):
+    def _predraw_dropout_kernel(self, n: int, device, sites, sx_stored=()):
         """The same dictionary from ONE hand-written launch (csrc/dropout_draw.hip): every multiplier a consumer needs -- the plain masks of the
         encoder sites and of the deferred dropout3 sites, and the decoder's composed products -- is a stateless Philox function of torch's CUDA
         generator state, so no intermediate mask is materialised and no ATen launch (bernoulli, mul, fill, copy: ~64 per MC step before) is left
         on the path.  The generator's offset is advanced, so `torch.manual_seed` reproduces the masks and successive calls differ."""
-        sig = (n, str(device), tuple((bool(d.training), float(d.p)) for _, d, _ in sites))
+        sig = (n, str(device), tuple((bool(d.training), float(d.p)) for _, d, _ in sites), sx_stored)
         plan = self.__dict__.get("_drop_plan")
         if plan is None or plan[0] != sig:
             index = {key: i for i, (key, _, _) in enumerate(sites)}
@@ -528,7 +629,7 @@ class SalsaNext(_FusedBlock):
                 m = getattr(self, blk)
                 cu, cs = m.in_filters // 4, m.conv1.in_channels - m.in_filters // 4
                 d1, d2, d3 = (f"{blk}.dropout{k}" if f"{blk}.dropout{k}" in index else None for k in (1, 2, 3))
-                add(f"{blk}._sx", m.in_filters, [(prod, 0), (d1, 0), (d2, 0)], shuffled=True)
+                add(f"{blk}._sx", m.in_filters, [(prod, 0), (d1, 0), (d2, 0)], shuffled=2 if blk in sx_stored else 1)
                 # (the shuffled flag applies to the second and third factor: the producer's multiplier is per STORED channel)
                 add(f"{blk}._ss", cs, [(d2, cu)])
                 if d3 is not None:
@@ -540,7 +641,7 @@ class SalsaNext(_FusedBlock):
                     refs = [(-1, 0)] + refs          # no (active) producer multiplier: keep the shuffled factors in slots b / c
                 fixed.append((key, c, refs[:3], shuffled))
             plan = (sig, ops.DropoutPlan(n, [(c, float(d.p), bool(d.training and d.p > 0.0)) for _, d, c in sites], fixed, device),
-                    [f"{blk}._composed" for blk in ("upBlock1", "upBlock2", "upBlock3", "upBlock4")])
+                    [f"{blk}._composed" for blk in ("upBlock1", "upBlock2", "upBlock3", "upBlock4")] + [f"{blk}._sx_stored" for blk in sx_stored])
             self.__dict__["_drop_plan"] = plan
         out = plan[1].run()
         for k in plan[2]:
@@ -581,7 +682,9 @@ class SalsaNext(_FusedBlock):
         if ev is not None:
             torch.cuda.current_stream().wait_event(ev)
 
-    def _forward(self, x, scales):
+    def _forward(self, x, scales, passes: int = 1):
+        """passes > 1 (half-precision inference, mc_predict_fused): the result of x.repeat(passes, 1, 1, 1) without building it -- the first
+        context block reads image n % B of the B converted images for stacked image n."""
         if not isinstance(x, torch.Tensor) or x.dim() != 4:
             raise RuntimeError("SalsaNext expects a [B, C, H, W] tensor")
         if not x.is_cuda:
@@ -590,16 +693,24 @@ class SalsaNext(_FusedBlock):
         if x.shape[2] % 16 or x.shape[3] % 16:
             raise RuntimeError("SalsaNext needs H and W divisible by 16")
         x = x.contiguous().float()
+        n = x.shape[0] * passes
+        if passes != 1 and not (_CONV_PRECISION == "f16" and self._inference_only()):
+            raise RuntimeError("SalsaNext: stacked passes over a shared input are a half-precision inference form")
         if not self._inference_only():
             self._pack_training_weights()
         # all 13 Dropout2d sites drawn (and the decoder's products composed) up front: in inference always; in training through the one-launch
         # kernel (the per-site nn.Dropout2d path costs ~60 tiny launches per step there as well).  Not under HIP-graph capture: the Philox
         # offset is a launch argument and would be frozen into the graph.
+        half = _CONV_PRECISION == "f16" and self._inference_only()
+        # upBlock4's conv1 reads upBlock3's output through PixelShuffle in place where its kernel covers the shape: upBlock3 then stores its
+        # channels in shuffle order and the multipliers of that tensor are drawn in the same order
+        in_place = self._in_place_blocks(n, x.shape[2], x.shape[3], scaled=True if scales else None)
+        perm1, perm2, perm3, perm4 = (f"upBlock{k}" in in_place for k in (1, 2, 3, 4))
         if scales is None and (self._inference_only() or _DROPOUT_KERNEL) and not torch.cuda.is_current_stream_capturing():
-            scales = self._predraw_dropout(x.shape[0], x.device)
-        if _CONV_PRECISION == "f16" and self._inference_only():
+            scales = self._predraw_dropout(n, x.device, sx_stored=in_place)
+        if half:
             x = h8.to_h8(x)             # everything downstream stays in the fp16 channel-blocked layout
-        d = self.downCntx(x)
+        d = self.downCntx(x) if passes == 1 else self.downCntx(x, n_out=n)
         d = self.downCntx2(d)
         d = self.downCntx3(d)
         d0c, d0b = self.resBlock1(d, scales, "resBlock1")
@@ -607,9 +718,9 @@ class SalsaNext(_FusedBlock):
         d1c, d1b = self.resBlock2(d0c, scales, "resBlock2")
         d2c, d2b = self.resBlock3(d1c, scales, "resBlock3")
         d3c, d3b = self.resBlock4(d2c, scales, "resBlock4")
-        d5c, s5 = self.resBlock5(d3c, scales, "resBlock5")
-        u4, s = self.upBlock1(d5c, d3b, s5, scales, "upBlock1")
-        u3, s = self.upBlock2(u4, d2b, s, scales, "upBlock2")
-        u2, s = self.upBlock3(u3, d1b, s, scales, "upBlock3")
-        u1, _ = self.upBlock4(u2, d0b, s, scales, "upBlock4")
+        d5c, s5 = self.resBlock5(d3c, scales, "resBlock5", out_perm=perm1)
+        u4, s = self.upBlock1(d5c, d3b, s5, scales, "upBlock1", x_perm=perm1, out_perm=perm2)
+        u3, s = self.upBlock2(u4, d2b, s, scales, "upBlock2", x_perm=perm2, out_perm=perm3)
+        u2, s = self.upBlock3(u3, d1b, s, scales, "upBlock3", x_perm=perm3, out_perm=perm4)
+        u1, _ = self.upBlock4(u2, d0b, s, scales, "upBlock4", x_perm=perm4)
         return self._head(u1)
