@@ -13,14 +13,8 @@
 //   conv1x1_h8_kernel   1x1 convs: no halo => B operands straight from global memory, weights through LDS
 //   plus layout / pooling / pixel-shuffle helpers at the end of the file.
 #include <stdio.h>
-#include "slu_common.h"
+#include "h8_common.h"
 #include <cstdlib>
-#include <utility>
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float float2v __attribute__((ext_vector_type(2)));
 
 // scheduling options of the 8-wave 128-channel configuration (conv_h8_kernel's OPT), as measured with tools/h8_ab.py (one process,
 // interleaved rounds, N = 64, single-source form): 15 is +1 ... +3 % on the 3x3 layers and +3 ... +7 % on the 2x2-dilated ones; two K-steps
@@ -76,23 +70,6 @@ __device__ __forceinline__ SrcSel select_src(const H8Args& a, const int (&img)[S
   return p;
 }
 
-// 8 halves * 8 fp32 multipliers (rounded to fp16 first, then packed multiplies)
-__device__ __forceinline__ uint4 scale_record(uint4 v, const float* sp) {
-  const float4 s0 = *reinterpret_cast<const float4*>(sp);
-  const float4 s1 = *reinterpret_cast<const float4*>(sp + 4);
-  half8 h = __builtin_bit_cast(half8, v);
-  h[0] *= (_Float16)s0.x; h[1] *= (_Float16)s0.y; h[2] *= (_Float16)s0.z; h[3] *= (_Float16)s0.w;
-  h[4] *= (_Float16)s1.x; h[5] *= (_Float16)s1.y; h[6] *= (_Float16)s1.z; h[7] *= (_Float16)s1.w;
-  return __builtin_bit_cast(uint4, h);
-}
-
-__device__ __forceinline__ unsigned pack2(float x, float y) {
-  half2v h;
-  h[0] = (_Float16)x;      // round to nearest even
-  h[1] = (_Float16)y;
-  return __builtin_bit_cast(unsigned, h);
-}
-
 // Epilogue shared by both kernels: one 32-channel x 32-pixel accumulator tile of a lane -> 4 x (4 channels)
 //   chan0: first channel of the 32-block; se: LDS constants bias | bn_a | bn_b indexed by `cl0 + ...`
 template <int STRIDE>
@@ -129,11 +106,6 @@ __device__ __forceinline__ void store_tile(const H8Args& a, const f32x16& acc, c
   }
 }
 
-// the source of every out-of-range / padding record of an LDS-DMA copy (never written)
-__device__ uint4 g_zero_rec;
-// where the lanes of a border tile that lie outside the image store (so that every lane of every tile issues its stores)
-__device__ uint4 g_trash_rec;
-
 // Epilogue of the persistent kernel (h8 output): EVERY lane issues its 4 stores (and its 4 residual loads when they were
 // not prefetched) -- lanes outside the image / past the last channel block read the zero record and store to a scratch
 // record -- so the number of vector-memory operations per tile is a compile-time constant the kernel's counted waits rely on.
@@ -141,8 +113,6 @@ template <int STRIDE, bool PRE>
 __device__ __forceinline__ void store_tile_full(const H8Args& a, const f32x16& acc, const float* se, int cl0, int go0, int hh, bool pix_ok, size_t n,
                                                 size_t pix, size_t HW, const uint2* __restrict__ resid, const uint2 (&rv)[4],
                                                 uint2* __restrict__ out, float slope_pre, uintptr_t zero_addr, uintptr_t trash_addr) {
-  // packed fp32 arithmetic (v_pk_add / v_pk_mul / v_pk_fma: two channels per instruction); LeakyReLU as max(t, slope t),
-  // exact for 0 <= slope <= 1 (slope_pre = 1 means "no activation"); the per-channel constants come as 16-byte LDS reads
   const float4* se4 = reinterpret_cast<const float4*>(se);
   const float2v sl = {slope_pre, slope_pre};
   const size_t plane2 = HW * 2;
@@ -150,30 +120,17 @@ __device__ __forceinline__ void store_tile_full(const H8Args& a, const f32x16& a
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int c4 = (cl0 + 8 * q) / 4 + hh;
-    const float4 bi = se4[c4], ba = se4[STRIDE / 4 + c4], bb = se4[2 * STRIDE / 4 + c4];
-    float2v t0 = {acc[4 * q], acc[4 * q + 1]}, t1 = {acc[4 * q + 2], acc[4 * q + 3]};
-    t0 += float2v{bi.x, bi.y};
-    t1 += float2v{bi.z, bi.w};
-    t0 = __builtin_elementwise_max(t0, t0 * sl);
-    t1 = __builtin_elementwise_max(t1, t1 * sl);
-    t0 = t0 * float2v{ba.x, ba.y} + float2v{bb.x, bb.y};
-    t1 = t1 * float2v{ba.z, ba.w} + float2v{bb.z, bb.w};
+    H8Quad t = h8_epilogue(acc, q, se4[c4], se4[STRIDE / 4 + c4], se4[2 * STRIDE / 4 + c4], sl);
     const bool ok = pix_ok && go0 + q < a.Gout;
     const size_t idx = idx0 + q * plane2;
-    if (resid) {
-      const uint2 r = PRE ? rv[q] : *(ok ? resid + idx : reinterpret_cast<const uint2*>(zero_addr));
-      t0 += __builtin_convertvector(__builtin_bit_cast(half2v, r.x), float2v);
-      t1 += __builtin_convertvector(__builtin_bit_cast(half2v, r.y), float2v);
-    }
-    *(ok ? out + idx : reinterpret_cast<uint2*>(trash_addr)) =
-        make_uint2(__builtin_bit_cast(unsigned, __builtin_convertvector(t0, half2v)), __builtin_bit_cast(unsigned, __builtin_convertvector(t1, half2v)));
+    if (resid) h8_add_resid(t, PRE ? rv[q] : *(ok ? resid + idx : reinterpret_cast<const uint2*>(zero_addr)));
+    *(ok ? out + idx : reinterpret_cast<uint2*>(trash_addr)) = pack4(t);
   }
 }
 
-// The same epilogue with whole 16-byte records on the way out: the accumulator holds half of each record per lane (4 channels of
-// block q in lane half hh); v_permlane32_swap trades halves between lanes jj and jj + 32 so that lane half 0 stores the record of
-// block 2 pr and lane half 1 that of block 2 pr + 1 -- 2 store instructions per accumulator tile instead of 4.  The residual (rare on
-// the layers this serves) is added before the exchange from 8-byte loads of the lane's own channels.
+// The same epilogue with whole 16-byte records on the way out (h8_swap16): lane half 0 stores the record of block 2 pr and lane half 1
+// that of block 2 pr + 1 -- 2 store instructions per accumulator tile instead of 4.  The residual (rare on the layers this serves) is
+// added before the exchange from 8-byte loads of the lane's own channels.
 template <int STRIDE>
 __device__ __forceinline__ void store_tile_swap16(const H8Args& a, const f32x16& acc, const float* se, int cl0, int go0, int hh, bool pix_ok, size_t n,
                                                   size_t pix, size_t HW, const uint2* __restrict__ resid, uint4* __restrict__ out, float slope_pre,
@@ -187,28 +144,17 @@ __device__ __forceinline__ void store_tile_swap16(const H8Args& a, const f32x16&
     for (int q2 = 0; q2 < 2; ++q2) {
       const int q = 2 * pr + q2;
       const int c4 = (cl0 + 8 * q) / 4 + hh;
-      const float4 bi = se4[c4], ba = se4[STRIDE / 4 + c4], bb = se4[2 * STRIDE / 4 + c4];
-      float2v t0 = {acc[4 * q], acc[4 * q + 1]}, t1 = {acc[4 * q + 2], acc[4 * q + 3]};
-      t0 += float2v{bi.x, bi.y};
-      t1 += float2v{bi.z, bi.w};
-      t0 = __builtin_elementwise_max(t0, t0 * sl);
-      t1 = __builtin_elementwise_max(t1, t1 * sl);
-      t0 = t0 * float2v{ba.x, ba.y} + float2v{bb.x, bb.y};
-      t1 = t1 * float2v{ba.z, ba.w} + float2v{bb.z, bb.w};
+      H8Quad t = h8_epilogue(acc, q, se4[c4], se4[STRIDE / 4 + c4], se4[2 * STRIDE / 4 + c4], sl);
       if (resid) {
         const bool okq = pix_ok && go0 + q < a.Gout;
-        const uint2 r = *(okq ? resid + (((n * a.Gout + go0 + q) * HW + pix) * 2 + hh) : reinterpret_cast<const uint2*>(zero_addr));
-        t0 += __builtin_convertvector(__builtin_bit_cast(half2v, r.x), float2v);
-        t1 += __builtin_convertvector(__builtin_bit_cast(half2v, r.y), float2v);
+        h8_add_resid(t, *(okq ? resid + (((n * a.Gout + go0 + q) * HW + pix) * 2 + hh) : reinterpret_cast<const uint2*>(zero_addr)));
       }
-      hw[2 * q2] = __builtin_bit_cast(unsigned, __builtin_convertvector(t0, half2v));
-      hw[2 * q2 + 1] = __builtin_bit_cast(unsigned, __builtin_convertvector(t1, half2v));
+      hw[2 * q2] = pack2(t.t0);
+      hw[2 * q2 + 1] = pack2(t.t1);
     }
-    const auto s0 = __builtin_amdgcn_permlane32_swap(hw[0], hw[2], false, false);
-    const auto s1 = __builtin_amdgcn_permlane32_swap(hw[1], hw[3], false, false);
+    const uint4 rec = h8_swap16(hw[0], hw[1], hw[2], hw[3]);
     const int go = go0 + 2 * pr + hh;
-    uint4* dst = (pix_ok && go < a.Gout) ? out + ((n * a.Gout + go) * HW + pix) : reinterpret_cast<uint4*>(trash_addr);
-    *dst = make_uint4(s0[0], s1[0], s0[1], s1[1]);
+    *((pix_ok && go < a.Gout) ? out + ((n * a.Gout + go) * HW + pix) : reinterpret_cast<uint4*>(trash_addr)) = rec;
   }
 }
 
@@ -224,11 +170,6 @@ __device__ unsigned long long g_h8_prof[8];
 #else
 #define H8_PROF_MARK(i)
 #endif
-
-// one global_load_lds_dwordx4: lane l copies the 16 bytes at its own `gsrc` to LDS address `ldst_wave_base + 16 l`
-#define SLU_GLDS16(gsrc, ldst_wave_base)                                                                  \
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gsrc),                 \
-                                   (__attribute__((address_space(3))) void*)(ldst_wave_base), 16, 0, 0)
 
 // -----------------------------------------------------------------------------------------------------------
 // Tiled kernel, persistent, LDS-DMA staged.  Workgroup = WM x WN waves; output tile = TH rows x 64 columns x
@@ -287,17 +228,18 @@ __global__ __launch_bounds__(64 * WM * WN, h8_waves_per_simd(MB, WM * WN, RPW)) 
   const int wm = wave / WN, wn = wave % WN;
   const bool late_half = wave >= NWAVE / 2;      // waves 4..7 share their SIMDs with waves 0..3
   const int mblk0 = blockIdx.y * MBLK;
-  // contiguous run of tiles of this workgroup; workgroups that share an XCD (blockIdx.x % 8) get neighbouring runs
+  // h8_tile_run's numbering with the `order` switch, written out: as a branch of the helper (by value, by reference, as a returned struct)
+  // the interleaved form re-associated the t_end arithmetic of every instantiation
   int t_beg, t_end, t_step = 1;
   {
     const int nwg = gridDim.x, b = blockIdx.x, xcd = b & 7, qq = nwg >> 3, rr = nwg & 7;
     const int w = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (b >> 3);
     const long long nt = (long long)a.tiles_x * a.tiles_y * a.N;
-    if (a.order) {      // interleaved: at any moment the resident workgroups cover a compact band of the image
+    if (a.order) {      // interleaved (the default)
       t_step = nwg;
       t_beg = w;
       t_end = w < nt ? w + (int)((nt - w + nwg - 1) / nwg) * nwg : w;
-    } else {
+    } else {            // contiguous run [nt w / nwg, nt (w + 1) / nwg), kept for A/B runs
       t_beg = (int)(nt * w / nwg);
       t_end = (int)(nt * (w + 1) / nwg);
     }
@@ -310,9 +252,7 @@ __global__ __launch_bounds__(64 * WM * WN, h8_waves_per_simd(MB, WM * WN, RPW)) 
   if (tid < MBLK * 32) {
     const int co = mblk0 * 32 + tid;
     const bool ok = co < a.Cout;
-    s_epi[tid] = (ok && a.bias) ? a.bias[co] : 0.0f;
-    s_epi[MBLK * 32 + tid] = (ok && a.bn_a) ? a.bn_a[co] : 1.0f;
-    s_epi[2 * MBLK * 32 + tid] = (ok && a.bn_a) ? a.bn_b[co] : 0.0f;
+    H8_FILL_EPI(s_epi, 0, MBLK * 32, tid, ok, co, a.bias, a.bn_a, a.bn_b);
   }
 
   const int hh = lane >> 5, jj = lane & 31;
@@ -360,12 +300,8 @@ __global__ __launch_bounds__(64 * WM * WN, h8_waves_per_simd(MB, WM * WN, RPW)) 
     return p;
   };
   static_assert(SLU_MAX_SRC == 3, "TilePos carries one image index per source");
-  // The address of the zero record, once, in an SGPR pair the compiler cannot rematerialise: left alone it re-loaded the address from the
-  // GOT for every piece (s_getpc + s_load_dwordx2 + s_waitcnt lgkmcnt(0): a scalar-memory round trip in every tap's staging slot).
-  uintptr_t zero_addr = reinterpret_cast<uintptr_t>(&g_zero_rec);
-  asm volatile("" : "+s"(zero_addr));
-  uintptr_t trash_addr = reinterpret_cast<uintptr_t>(&g_trash_rec);
-  asm volatile("" : "+s"(trash_addr));
+  H8_OPAQUE_ADDR(zero_addr, h8_zero_rec);
+  H8_OPAQUE_ADDR(trash_addr, h8_trash_rec);
   // Per-lane description of the input-tile pieces this wave copies (the same for every chunk and tile): piece i covers
   // records [64 (i NWAVE + wave), +64) of the [2 KPC][LH][LW] tile image; pc_rc = row | col << 8 | block << 16 | inside << 20.
   int pc_rc[NIB], pc_off[NIB];
@@ -474,19 +410,13 @@ __global__ __launch_bounds__(64 * WM * WN, h8_waves_per_simd(MB, WM * WN, RPW)) 
       }
       if (stored0) {
         if (a.src[0].scale) {
-          const float* sp = a.src[0].scale + ((size_t)n * 4 * a.src[0].G + tid) * 8;
-          const float4 s0 = *reinterpret_cast<const float4*>(sp), s1 = *reinterpret_cast<const float4*>(sp + 4);
-          h[0] = (_Float16)s0.x; h[1] = (_Float16)s0.y; h[2] = (_Float16)s0.z; h[3] = (_Float16)s0.w;
-          h[4] = (_Float16)s1.x; h[5] = (_Float16)s1.y; h[6] = (_Float16)s1.z; h[7] = (_Float16)s1.w;
+          h = h8_multipliers(a.src[0].scale + ((size_t)n * 4 * a.src[0].G + tid) * 8);
         }
       } else if (g < a.Gin) {
         int img[SLU_MAX_SRC] = {0, 0, 0};
         const SrcSel p = select_src(a, img, g);
         if (p.scale) {
-          const float* sp = p.scale + ((size_t)n * p.G + p.gl) * 8;
-          const float4 s0 = *reinterpret_cast<const float4*>(sp), s1 = *reinterpret_cast<const float4*>(sp + 4);
-          h[0] = (_Float16)s0.x; h[1] = (_Float16)s0.y; h[2] = (_Float16)s0.z; h[3] = (_Float16)s0.w;
-          h[4] = (_Float16)s1.x; h[5] = (_Float16)s1.y; h[6] = (_Float16)s1.z; h[7] = (_Float16)s1.w;
+          h = h8_multipliers(p.scale + ((size_t)n * p.G + p.gl) * 8);
         }
       }
       s_scale[par * 64 + tid] = __builtin_bit_cast(uint4, h);
@@ -497,7 +427,7 @@ __global__ __launch_bounds__(64 * WM * WN, h8_waves_per_simd(MB, WM * WN, RPW)) 
     const int per_m = nks * T;
     for (int blk = wave; blk < MBLK * per_m; blk += NWAVE) {
       const int m = blk / per_m;
-      const uint4* src = mblk0 + m < a.nmblk ? a.wpack + ((size_t)(mblk0 + m) * per_m + (blk - m * per_m)) * 64 + lane : &g_zero_rec;
+      const uint4* src = mblk0 + m < a.nmblk ? a.wpack + ((size_t)(mblk0 + m) * per_m + (blk - m * per_m)) * 64 + lane : &h8_zero_rec;
       SLU_GLDS16(src, s_a + blk * 64);
     }
   }
@@ -528,6 +458,7 @@ __global__ __launch_bounds__(64 * WM * WN, h8_waves_per_simd(MB, WM * WN, RPW)) 
   int tile_no = 0;
   for (int tile = t_beg; tile < t_end; tile += t_step, ++tile_no) {
     f32x16 acc[MB][NB];                                // per tile (not carried around the loop: keeps it in the MFMA registers)
+    // written out: with h8_zero the fp32-output instantiation takes one VGPR more
 #pragma unroll
     for (int i = 0; i < MB; ++i)
 #pragma unroll
@@ -543,12 +474,11 @@ __global__ __launch_bounds__(64 * WM * WN, h8_waves_per_simd(MB, WM * WN, RPW)) 
       // Chunk (tile, q) has landed and nobody reads the other buffer any more.  vmcnt counts loads, LDS-DMA and stores in
       // issue order: at a tile's first chunk the only operations younger than the DMA we wait for are the NST stores of the
       // previous tile's epilogue, which may stay in flight (waiting for them would expose the HBM write latency per tile).
-      if (!F32OUT && q == 0 && tile != t_beg) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NST < 63 ? NST : 63) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      if (!F32OUT && q == 0 && tile != t_beg) h8_vmcnt<(NST < 63 ? NST : 63)>();
+      else h8_vmcnt<0>();
+      h8_lgkmcnt0();
       H8_PROF_MARK(0)                                    // waiting for the chunk's DMA (and, at q = 0, the epilogue before it)
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
+      h8_barrier();
       H8_PROF_MARK(1)                                    // barrier
       if constexpr ((OPT & 4) == 0) setup_next(tile, q);
       if constexpr (PRE) {
@@ -742,18 +672,11 @@ __global__ __launch_bounds__(256, (MB * NBW >= 8) ? 2 : ((MB * NBW >= 4) ? 3 : 4
 
   if (tid < MB * 32) {
     const bool ok = tid < a.Cout;
-    s_epi[tid] = (ok && a.bias) ? a.bias[tid] : 0.0f;
-    s_epi[MB * 32 + tid] = (ok && a.bn_a) ? a.bn_a[tid] : 1.0f;
-    s_epi[2 * MB * 32 + tid] = (ok && a.bn_a) ? a.bn_b[tid] : 0.0f;
+    H8_FILL_EPI(s_epi, 0, MB * 32, tid, ok, tid, a.bias, a.bn_a, a.bn_b);
   }
 
   f32x16 acc[MB][NBW];
-#pragma unroll
-  for (int i = 0; i < MB; ++i)
-#pragma unroll
-    for (int b = 0; b < NBW; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][b][r] = 0.0f;
+  h8_zero(acc);
 
   int nimg[NBW];
   long long hw[NBW];
@@ -867,9 +790,7 @@ __global__ __launch_bounds__(256, h8_1x1_res_waves_per_simd(MB, NKS)) void conv1
 
   if (tid < MB * 32) {
     const bool ok = tid < a.Cout;
-    s_epi[tid] = (ok && a.bias) ? a.bias[tid] : 0.0f;
-    s_epi[MB * 32 + tid] = (ok && a.bn_a) ? a.bn_a[tid] : 1.0f;
-    s_epi[2 * MB * 32 + tid] = (ok && a.bn_a) ? a.bn_b[tid] : 0.0f;
+    H8_FILL_EPI(s_epi, 0, MB * 32, tid, ok, tid, a.bias, a.bn_a, a.bn_b);
   }
   for (int e = tid; e < MB * NKS * 64; e += 256) {
     const int m = e / (NKS * 64);
@@ -910,7 +831,7 @@ __global__ __launch_bounds__(256, h8_1x1_res_waves_per_simd(MB, NKS)) void conv1
     }
     f32x16 acc[MB];
 #pragma unroll
-    for (int i = 0; i < MB; ++i)
+    for (int i = 0; i < MB; ++i)      // written out: a helper inverts a branch of <1, 1>
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][r] = 0.0f;
 #pragma unroll
@@ -987,13 +908,10 @@ __global__ __launch_bounds__(512, 2) void gemm1x1_h8_kernel(const H8Args a, cons
 
   if (tid < MBLK * 32) {
     const bool ok = tid < a.Cout;
-    s_epi[tid] = (ok && a.bias) ? a.bias[tid] : 0.0f;
-    s_epi[MBLK * 32 + tid] = (ok && a.bn_a) ? a.bn_a[tid] : 1.0f;
-    s_epi[2 * MBLK * 32 + tid] = (ok && a.bn_a) ? a.bn_b[tid] : 0.0f;
+    H8_FILL_EPI(s_epi, 0, MBLK * 32, tid, ok, tid, a.bias, a.bn_a, a.bn_b);
   }
-  uintptr_t zero_addr = reinterpret_cast<uintptr_t>(&g_zero_rec), trash_addr = reinterpret_cast<uintptr_t>(&g_trash_rec);
-  asm volatile("" : "+s"(zero_addr));
-  asm volatile("" : "+s"(trash_addr));
+  H8_OPAQUE_ADDR(zero_addr, h8_zero_rec);
+  H8_OPAQUE_ADDR(trash_addr, h8_trash_rec);
 
   // the staging cursor runs D - 1 chunks ahead of the compute cursor: (s_tile, s_q) = the next chunk to copy, into ring slot s_slot
   int s_tile = t_beg, s_q = 0, s_slot = 0;
@@ -1042,19 +960,11 @@ __global__ __launch_bounds__(512, 2) void gemm1x1_h8_kernel(const H8Args a, cons
 
   for (int tile = t_beg; tile < ntiles; tile += t_step) {
     f32x16 acc[MB][NB];
-#pragma unroll
-    for (int i = 0; i < MB; ++i)
-#pragma unroll
-      for (int b = 0; b < NB; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][b][r] = 0.0f;
+    h8_zero(acc);
     for (int q = 0; q < nch; ++q) {
       // the oldest chunk in flight has landed once at most the (D - 2) younger chunks' pieces are outstanding (stores of an epilogue in
       // between only make the wait stricter); then every wave is past its reads of the slot that is re-filled next
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"((D - 2) * NPIECE) : "memory");
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
+      h8_chunk_landed<(D - 2) * NPIECE>();
       stage_next();
       const uint4* sb = s_b + r_slot * NREC_B + bbase;
       const uint4* sa = s_a + r_slot * NREC_A + abase;
@@ -1318,11 +1228,9 @@ int launch_h8_k(H8Args& a, const slu_conv_h8_desc* d, const SluEmit& e) {
   long long gx = (256 * per_cu + gy - 1) / gy;
   if (gx < 8) gx = 8;
   if (gx > nt) gx = nt;
-  auto kern = conv_h8_kernel<KS, DIL, PAD, MB, WM, WN, RPW, SCALED, WRES, F32OUT, KPC, OPT, ONE>;
   static SluLdsGrant grant;
-  if (slu_grant_dynamic_lds(reinterpret_cast<const void*>(kern), lds, grant) != SLU_OK) return SLU_ELAUNCH;
-  hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)gy), dim3(64 * NWAVE), lds, e.st, a, d->resid, d->out);
-  SLU_CHECK_LAUNCH();
+  return slu_launch_lds(conv_h8_kernel<KS, DIL, PAD, MB, WM, WN, RPW, SCALED, WRES, F32OUT, KPC, OPT, ONE>, dim3((unsigned)gx, (unsigned)gy), dim3(64 * NWAVE),
+                        lds, e.st, grant, a, d->resid, d->out);
 }
 
 // -----------------------------------------------------------------------------------------------------------
@@ -1338,8 +1246,6 @@ int launch_h8_k(H8Args& a, const slu_conv_h8_desc* d, const SluEmit& e) {
 //   * whole 16-byte records per lane on the way out (v_permlane32_swap between lanes jj and jj + 32).
 // One tile = NKS positions: wait(chunk s) | barrier | DMA(chunk s + P) | 9 taps of chunk s ; after the last: epilogue, NST stores.
 // -----------------------------------------------------------------------------------------------------------
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-
 struct RingArgs {
   const uint4 *x, *x1;         // h8 [N][G0][H][W] (+ a second plain source [N][G1][H][W], G0 + G1 = 2 NKS, G0 even: the concatenation)
   int G0, G1;
@@ -1360,10 +1266,6 @@ constexpr int ring3_younger(int c) {             // VM operations issued after t
   int n = s0 == NKS - 1 ? NST : 0;
   for (int d = 1; d < P; ++d) n += NIB + ((s0 + d) % NKS == NKS - 1 ? NST : 0);
   return n;
-}
-template <class F, int... Cs>
-__device__ __forceinline__ void ring3_static_for(F&& f, std::integer_sequence<int, Cs...>) {
-  (f(std::integral_constant<int, Cs>{}), ...);
 }
 
 template <int DIL, int MB, int NKS, int RPW, int D>
@@ -1389,33 +1291,18 @@ __global__ __launch_bounds__(512, 2) void ring3_h8_kernel(const RingArgs a) {
   const int hh = lane >> 5, jj = lane & 31;
   const size_t HW = (size_t)a.H * a.W;
 
-  int t_beg, t_end, t_step;
-  {
-    const int nwg = gridDim.x, b = blockIdx.x, xcd = b & 7, qq = nwg >> 3, rr = nwg & 7;
-    const int w = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (b >> 3);
-    const long long nt = (long long)a.tiles_x * a.tiles_y * a.N;
-    t_step = nwg;
-    t_beg = w;
-    t_end = w < nt ? w + (int)((nt - w + nwg - 1) / nwg) * nwg : w;
-  }
+  const H8Run run = h8_tile_run(a.tiles_x, a.tiles_y, a.N);
+  const int t_beg = run.beg, t_end = run.end, t_step = run.step;
   if (t_beg >= t_end) return;
 
-  if (tid < C) {
-    s_epi[tid] = a.bias ? a.bias[tid] : 0.0f;
-    s_epi[C + tid] = a.bn_a ? a.bn_a[tid] : 1.0f;
-    s_epi[2 * C + tid] = a.bn_a ? a.bn_b[tid] : 0.0f;
-  }
+  if (tid < C) H8_FILL_EPI(s_epi, 0, C, tid, true, tid, a.bias, a.bn_a, a.bn_b);
   for (int blk = wave; blk < MB * NKS * T; blk += NWAVE) SLU_GLDS16(a.wpack + (size_t)blk * 64 + lane, s_w + blk * 64);
   const bool mul0 = NKS == 5 && a.shuf && a.sc0;
   if constexpr (NKS == 5) {
     // the multiplier table goes to LDS once, here: the tile loop's VM operations (and ring3_younger) stay what they are
     if (mul0) {
       for (int e = tid; e < a.N * 4 * a.G0; e += 64 * NWAVE) {
-        const float4 s0 = *reinterpret_cast<const float4*>(a.sc0 + (size_t)e * 8), s1 = *reinterpret_cast<const float4*>(a.sc0 + (size_t)e * 8 + 4);
-        half8 h;
-        h[0] = (_Float16)s0.x; h[1] = (_Float16)s0.y; h[2] = (_Float16)s0.z; h[3] = (_Float16)s0.w;
-        h[4] = (_Float16)s1.x; h[5] = (_Float16)s1.y; h[6] = (_Float16)s1.z; h[7] = (_Float16)s1.w;
-        s_mul[e] = __builtin_bit_cast(uint4, h);
+        s_mul[e] = __builtin_bit_cast(uint4, h8_multipliers(a.sc0 + (size_t)e * 8));
       }
     }
   }
@@ -1441,7 +1328,7 @@ __global__ __launch_bounds__(512, 2) void ring3_h8_kernel(const RingArgs a) {
   }
   auto stage = [&](const TilePos& tp, int c, int slot, bool valid) {
     uint4* db = s_ring + slot * BUFREC;
-    const uintptr_t zero = reinterpret_cast<uintptr_t>(&g_zero_rec);
+    const uintptr_t zero = reinterpret_cast<uintptr_t>(&h8_zero_rec);
     const bool second = 2 * c >= a.G0;                  // a K-step never straddles the two sources (G0 is even)
     const uint4* src = second ? a.x1 : a.x;
     const int gs = second ? a.G1 : a.G0, g = second ? 2 * c - a.G0 : 2 * c;
@@ -1478,22 +1365,15 @@ __global__ __launch_bounds__(512, 2) void ring3_h8_kernel(const RingArgs a) {
 
   for (int tile = t_beg; tile < t_end; tile += t_step) {
     f32x16 acc[MB][NB];
-#pragma unroll
-    for (int i = 0; i < MB; ++i)
-#pragma unroll
-      for (int b = 0; b < NB; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][b][r] = 0.0f;
+    h8_zero(acc);
 
     auto position = [&](auto cc) {
       constexpr int c = decltype(cc)::value;
       constexpr int YOUNG = ring3_younger<NKS, NIB, P, NST>(c);
       static_assert(YOUNG <= 63, "vmcnt is a 6-bit counter");
-      if (first && c < P) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the first tile's prologue (and the resident weights)
-      else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(YOUNG) : "memory");
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
+      if (first && c < P) h8_vmcnt<0>();          // the first tile's prologue (and the resident weights)
+      else h8_vmcnt<YOUNG>();
+      h8_lds_barrier();
       {
         constexpr int cn = (c + P) % NKS;
         if (c + P < NKS) stage(cur, cn, wslot, true);
@@ -1541,7 +1421,7 @@ __global__ __launch_bounds__(512, 2) void ring3_h8_kernel(const RingArgs a) {
         __builtin_amdgcn_sched_barrier(0);
       }
     };
-    ring3_static_for(position, std::make_integer_sequence<int, NKS>{});
+    h8_static_for(position, std::make_integer_sequence<int, NKS>{});
     first = false;
 
 #pragma unroll
@@ -1558,21 +1438,12 @@ __global__ __launch_bounds__(512, 2) void ring3_h8_kernel(const RingArgs a) {
           for (int q2 = 0; q2 < 2; ++q2) {
             const int q = 2 * pr + q2;
             const int c4 = (i * 32 + 8 * q) / 4;
-            const f32x4v bi = se4p[c4], ba = se4p[C / 4 + c4], bb = se4p[2 * C / 4 + c4];
-            float2v t0 = {acc[i][b][4 * q], acc[i][b][4 * q + 1]}, t1 = {acc[i][b][4 * q + 2], acc[i][b][4 * q + 3]};
-            t0 += float2v{bi.x, bi.y};
-            t1 += float2v{bi.z, bi.w};
-            t0 = __builtin_elementwise_max(t0, t0 * sl);
-            t1 = __builtin_elementwise_max(t1, t1 * sl);
-            t0 = t0 * float2v{ba.x, ba.y} + float2v{bb.x, bb.y};
-            t1 = t1 * float2v{ba.z, ba.w} + float2v{bb.z, bb.w};
-            hw[2 * q2] = __builtin_bit_cast(unsigned, __builtin_convertvector(t0, half2v));
-            hw[2 * q2 + 1] = __builtin_bit_cast(unsigned, __builtin_convertvector(t1, half2v));
+            const H8Quad t = h8_epilogue(acc[i][b], q, se4p[c4], se4p[C / 4 + c4], se4p[2 * C / 4 + c4], sl);
+            hw[2 * q2] = pack2(t.t0);
+            hw[2 * q2 + 1] = pack2(t.t1);
           }
-          const auto s0 = __builtin_amdgcn_permlane32_swap(hw[0], hw[2], false, false);
-          const auto s1 = __builtin_amdgcn_permlane32_swap(hw[1], hw[3], false, false);
-          uint4* dst = ok ? a.out + idx0 + (size_t)(2 * pr) * HW : &g_trash_rec;
-          *dst = make_uint4(s0[0], s1[0], s0[1], s1[1]);
+          const uint4 rec = h8_swap16(hw[0], hw[1], hw[2], hw[3]);
+          *(ok ? a.out + idx0 + (size_t)(2 * pr) * HW : &h8_trash_rec) = rec;
         }
       }
     asm volatile("" ::: "memory");
@@ -1609,11 +1480,8 @@ int launch_ring3(const H8Args& h, const slu_conv_h8_desc* d, const SluEmit& e) {
   if (nt < 256) return -1;      // too few tiles to fill the chip: the tiled kernel
   if (nt > 0x7fffffffLL) return SLU_EUNSUPPORTED;
   if (e.name) return slu_emit_name(e, "ring3_h8_kernel<%d, %d, %d, %d, %d>", DIL, MB, NKS, RPW, D);
-  auto kern = ring3_h8_kernel<DIL, MB, NKS, RPW, D>;
   static SluLdsGrant grant;
-  if (slu_grant_dynamic_lds(reinterpret_cast<const void*>(kern), lds, grant) != SLU_OK) return SLU_ELAUNCH;
-  hipLaunchKernelGGL(kern, dim3(256), dim3(512), lds, e.st, a);
-  SLU_CHECK_LAUNCH();
+  return slu_launch_lds(ring3_h8_kernel<DIL, MB, NKS, RPW, D>, dim3(256), dim3(512), lds, e.st, grant, a);
 }
 
 // the layers ring3_h8_kernel covers: 3x3 (dil 1 / 2), one or two plain sources of 32 / 64 (80 -> 32: dil 1) channels in all, 32 / 64 output
@@ -1799,11 +1667,8 @@ int launch_gemm1x1(H8Args& a, const slu_conv_h8_desc* d, const SluEmit& e) {
   const long long nt = (long long)a.N * a.H * a.W / 256;
   const long long gx = nt < 256 ? nt : 256;
   if (e.name) return slu_emit_name(e, "gemm1x1_h8_kernel<%d, %d, %d>", MB, KC, D);
-  auto kern = gemm1x1_h8_kernel<MB, KC, D>;
   static SluLdsGrant grant;
-  if (slu_grant_dynamic_lds(reinterpret_cast<const void*>(kern), lds, grant) != SLU_OK) return SLU_ELAUNCH;
-  hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(512), lds, e.st, a, d->resid, d->out);
-  SLU_CHECK_LAUNCH();
+  return slu_launch_lds(gemm1x1_h8_kernel<MB, KC, D>, dim3((unsigned)gx), dim3(512), lds, e.st, grant, a, d->resid, d->out);
 }
 
 bool any_scale(const slu_conv_h8_desc* d) {

@@ -15,25 +15,10 @@
 // C = 32 MB WM channels, 8 waves = WM x WN, a wave owns MB channel blocks and RPW output rows: (C, TH) = (32, 16), (64, 8), (128, 4)
 // -- the a3 image takes C * TH * 128 B = 64 KB in each.  W3RES: the 1x1 weights over a3 stay resident in LDS (C <= 64); otherwise
 // they stream through the chunk pipeline as NKS more (weights-only) chunks, for which the LDS has no room at C = 128.
-#include "slu_common.h"
+#include "h8_common.h"
 #include <cstdlib>
-#include <utility>
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float float2v __attribute__((ext_vector_type(2)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 
 namespace {
-
-__device__ uint4 g_zero_rec_t;      // source of every out-of-image record of an LDS-DMA copy (never written)
-__device__ uint4 g_trash_rec_t;     // where lanes outside the image store
-
-#define SLU_GLDS16_T(gsrc, ldst_wave_base)                                                                \
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gsrc),                 \
-                                   (__attribute__((address_space(3))) void*)(ldst_wave_base), 16, 0, 0)
 
 struct TailArgs {
   const uint4 *a1, *a2;        // h8 [N][G][H][W]
@@ -76,29 +61,18 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void tail_h8_kernel(const TailArgs
   const int hh = lane >> 5, jj = lane & 31;
   const size_t HW = (size_t)a.H * a.W;
 
-  int t_beg, t_end, t_step;
-  {
-    const int nwg = gridDim.x, b = blockIdx.x, xcd = b & 7, qq = nwg >> 3, rr = nwg & 7;
-    const int w = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (b >> 3);
-    const long long nt = (long long)a.tiles_x * a.tiles_y * a.N;
-    t_step = nwg;
-    t_beg = w;
-    t_end = w < nt ? w + (int)((nt - w + nwg - 1) / nwg) * nwg : w;
-  }
+  const H8Run run = h8_tile_run(a.tiles_x, a.tiles_y, a.N);
+  const int t_beg = run.beg, t_end = run.end, t_step = run.step;
   if (t_beg >= t_end) return;
 
   if (tid < C) {
-    s_epi[tid] = a.biasA ? a.biasA[tid] : 0.0f;
-    s_epi[C + tid] = a.bnA_a ? a.bnA_a[tid] : 1.0f;
-    s_epi[2 * C + tid] = a.bnA_a ? a.bnA_b[tid] : 0.0f;
-    s_epi[3 * C + tid] = a.biasB ? a.biasB[tid] : 0.0f;
-    s_epi[4 * C + tid] = a.bnB_a ? a.bnB_a[tid] : 1.0f;
-    s_epi[5 * C + tid] = a.bnB_a ? a.bnB_b[tid] : 0.0f;
+    H8_FILL_EPI(s_epi, 0, C, tid, true, tid, a.biasA, a.bnA_a, a.bnA_b);
+    H8_FILL_EPI(s_epi, 3 * C, C, tid, true, tid, a.biasB, a.bnB_a, a.bnB_b);
   }
   if constexpr (W3RES) {
     for (int blk = wave; blk < MBLK * NKS; blk += NWAVE) {             // resident 1x1 weights of the a3 third: K-steps 2 NKS .. 3 NKS - 1
       const int m = blk / NKS, k = blk - m * NKS;
-      SLU_GLDS16_T(a.w1 + ((size_t)m * 3 * NKS + 2 * NKS + k) * 64 + lane, s_w3 + blk * 64);
+      SLU_GLDS16(a.w1 + ((size_t)m * 3 * NKS + 2 * NKS + k) * 64 + lane, s_w3 + blk * 64);
     }
   }
 
@@ -137,8 +111,8 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void tail_h8_kernel(const TailArgs
         const int rc = pc_rc[i];
         const int gy = tp.y0 - PAD + (rc & 255), gx = tp.x0 - PAD + ((rc >> 8) & 255);
         const bool ok = (rc >> 17) && (unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W;
-        const uintptr_t p = ok ? (((rc >> 16) & 1) ? base1 : base0) + 16 * (long long)pc_off[i] : reinterpret_cast<uintptr_t>(&g_zero_rec_t);
-        SLU_GLDS16_T(reinterpret_cast<const uint4*>(p), db + blk * 64);
+        const uintptr_t p = ok ? (((rc >> 16) & 1) ? base1 : base0) + 16 * (long long)pc_off[i] : reinterpret_cast<uintptr_t>(&h8_zero_rec);
+        SLU_GLDS16(reinterpret_cast<const uint4*>(p), db + blk * 64);
       }
     }
     uint4* da = s_a + buf * NREC_A;
@@ -148,9 +122,9 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void tail_h8_kernel(const TailArgs
       if (NBLK_A % NWAVE == 0 || blk < NBLK_A) {
         const int m = blk / (T + 1), f = blk - m * (T + 1);
         if (f < T) {
-          if (!second) SLU_GLDS16_T(a.w2 + (((size_t)m * NKS + q) * T + f) * 64 + lane, da + blk * 64);      // a1 chunks have no 2x2 taps
+          if (!second) SLU_GLDS16(a.w2 + (((size_t)m * NKS + q) * T + f) * 64 + lane, da + blk * 64);      // a1 chunks have no 2x2 taps
         } else {
-          SLU_GLDS16_T(a.w1 + ((size_t)m * 3 * NKS + (third ? 2 * NKS + q : (second ? q : NKS + q))) * 64 + lane, da + blk * 64);   // cat order (a1, a2, a3)
+          SLU_GLDS16(a.w1 + ((size_t)m * 3 * NKS + (third ? 2 * NKS + q : (second ? q : NKS + q))) * 64 + lane, da + blk * 64);   // cat order (a1, a2, a3)
         }
       }
     }
@@ -165,6 +139,8 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void tail_h8_kernel(const TailArgs
 
   for (int tile = t_beg; tile < t_end; tile += t_step) {
     f32x16 acc3[MB][NB], acco[MB][NB];
+    // the two sets element by element in turn, written out: h8_zero on one set after the other (or `= {}`) commutes the operands of this
+    // kernel's packed adds and re-schedules tail_h8_kernel<2, 1, 8, 1, true>
 #pragma unroll
     for (int i = 0; i < MB; ++i)
 #pragma unroll
@@ -183,16 +159,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void tail_h8_kernel(const TailArgs
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             const int c4 = (ml * 32 + 8 * q) / 4 + hh;
-            const float4 bi = se4[c4], ba = se4[C / 4 + c4], bb = se4[2 * C / 4 + c4];
-            float2v t0 = {acc3[i][b][4 * q], acc3[i][b][4 * q + 1]}, t1 = {acc3[i][b][4 * q + 2], acc3[i][b][4 * q + 3]};
-            t0 += float2v{bi.x, bi.y};
-            t1 += float2v{bi.z, bi.w};
-            t0 = __builtin_elementwise_max(t0, t0 * slA);
-            t1 = __builtin_elementwise_max(t1, t1 * slA);
-            t0 = t0 * float2v{ba.x, ba.y} + float2v{bb.x, bb.y};
-            t1 = t1 * float2v{ba.z, ba.w} + float2v{bb.z, bb.w};
-            s3[((((ml * 4 + q) * TH + row) * 64 + px) << 1) + hh] =
-                make_uint2(__builtin_bit_cast(unsigned, __builtin_convertvector(t0, half2v)), __builtin_bit_cast(unsigned, __builtin_convertvector(t1, half2v)));
+            s3[((((ml * 4 + q) * TH + row) * 64 + px) << 1) + hh] = pack4(h8_epilogue(acc3[i][b], q, se4[c4], se4[C / 4 + c4], se4[2 * C / 4 + c4], slA));
           }
           __builtin_amdgcn_sched_barrier(0);
         }
@@ -212,11 +179,9 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void tail_h8_kernel(const TailArgs
 
     for (int c = 0; c < NCH; ++c) {
       // the chunk has landed; at a tile's first chunk only the NST stores of the previous tile's epilogue are younger than its DMA
-      if (c == 0 && tile != t_beg) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NST < 63 ? NST : 63) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
+      if (c == 0 && tile != t_beg) h8_vmcnt<(NST < 63 ? NST : 63)>();
+      else h8_vmcnt<0>();
+      h8_lds_barrier();
       if (c + 1 < NCH) {
         stage(cur, c + 1, buf ^ 1);
       } else if (tile + t_step < t_end) {
@@ -259,9 +224,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void tail_h8_kernel(const TailArgs
 
     if constexpr (W3RES) {
       a3_to_lds();
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
+      h8_lds_barrier();
 #pragma unroll
       for (int k = 0; k < NKS; ++k) a3_step(k, s_w3 + ((wm * MB) * NKS + k) * 64 + lane, NKS * 64);
     }
@@ -277,22 +240,10 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void tail_h8_kernel(const TailArgs
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int c4 = (ml * 32 + 8 * q) / 4 + hh;
-          const float4 bi = se4[3 * C / 4 + c4], ba = se4[4 * C / 4 + c4], bb = se4[5 * C / 4 + c4];
-          float2v t0 = {acco[i][b][4 * q], acco[i][b][4 * q + 1]}, t1 = {acco[i][b][4 * q + 2], acco[i][b][4 * q + 3]};
-          t0 += float2v{bi.x, bi.y};
-          t1 += float2v{bi.z, bi.w};
-          t0 = __builtin_elementwise_max(t0, t0 * slB);
-          t1 = __builtin_elementwise_max(t1, t1 * slB);
-          t0 = t0 * float2v{ba.x, ba.y} + float2v{bb.x, bb.y};
-          t1 = t1 * float2v{ba.z, ba.w} + float2v{bb.z, bb.w};
+          H8Quad t = h8_epilogue(acco[i][b], q, se4[3 * C / 4 + c4], se4[4 * C / 4 + c4], se4[5 * C / 4 + c4], slB);
           const size_t idx = idx0 + (size_t)q * HW * 2;
-          if (a.resid) {
-            const uint2 r = *(ok ? a.resid + idx : reinterpret_cast<const uint2*>(&g_zero_rec_t));
-            t0 += __builtin_convertvector(__builtin_bit_cast(half2v, r.x), float2v);
-            t1 += __builtin_convertvector(__builtin_bit_cast(half2v, r.y), float2v);
-          }
-          *(ok ? a.out + idx : reinterpret_cast<uint2*>(&g_trash_rec_t)) =
-              make_uint2(__builtin_bit_cast(unsigned, __builtin_convertvector(t0, half2v)), __builtin_bit_cast(unsigned, __builtin_convertvector(t1, half2v)));
+          if (a.resid) h8_add_resid(t, *(ok ? a.resid + idx : reinterpret_cast<const uint2*>(&h8_zero_rec)));
+          *(ok ? a.out + idx : reinterpret_cast<uint2*>(&h8_trash_rec)) = pack4(t);
         }
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -329,10 +280,6 @@ constexpr int tail2_younger(int c) {             // ... issued after the DMA of 
   for (int d = 1; d < P; ++d) n += NIB + tail2_ops_after_dma<NKS, NIB, P, NA1, NRES, NST>((s0 + d) % NKS);
   return n;
 }
-template <class F, int... Cs>
-__device__ __forceinline__ void tail2_static_for(F&& f, std::integer_sequence<int, Cs...>) {
-  (f(std::integral_constant<int, Cs>{}), ...);
-}
 
 // RES: 0 no residual; 1 residual tensor; 2 residual = LeakyReLU(conv1x1(sc_x) + sc_bias), the shortcut of a ResBlock whose input has 32
 // channels, computed in the epilogue from 2 K-steps of sc_x (4 record loads per lane instead of 8, and no shortcut tensor in HBM at all)
@@ -368,33 +315,22 @@ __global__ __launch_bounds__(512, 2) void tail2_h8_kernel(const TailArgs a) {
   const int hh = lane >> 5, jj = lane & 31;
   const size_t HW = (size_t)a.H * a.W;
 
-  int t_beg, t_end, t_step;
-  {
-    const int nwg = gridDim.x, b = blockIdx.x, xcd = b & 7, qq = nwg >> 3, rr = nwg & 7;
-    const int w = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (b >> 3);
-    const long long nt = (long long)a.tiles_x * a.tiles_y * a.N;
-    t_step = nwg;
-    t_beg = w;
-    t_end = w < nt ? w + (int)((nt - w + nwg - 1) / nwg) * nwg : w;
-  }
+  const H8Run run = h8_tile_run(a.tiles_x, a.tiles_y, a.N);
+  const int t_beg = run.beg, t_end = run.end, t_step = run.step;
   if (t_beg >= t_end) return;
 
   if (tid < C) {
-    s_epi[tid] = a.biasA ? a.biasA[tid] : 0.0f;
-    s_epi[C + tid] = a.bnA_a ? a.bnA_a[tid] : 1.0f;
-    s_epi[2 * C + tid] = a.bnA_a ? a.bnA_b[tid] : 0.0f;
-    s_epi[3 * C + tid] = a.biasB ? a.biasB[tid] : 0.0f;
-    s_epi[4 * C + tid] = a.bnB_a ? a.bnB_a[tid] : 1.0f;
-    s_epi[5 * C + tid] = a.bnB_a ? a.bnB_b[tid] : 0.0f;
+    H8_FILL_EPI(s_epi, 0, C, tid, true, tid, a.biasA, a.bnA_a, a.bnA_b);
+    H8_FILL_EPI(s_epi, 3 * C, C, tid, true, tid, a.biasB, a.bnB_a, a.bnB_b);
     s_epi[6 * C + tid] = (RES == 2 && a.sc_bias) ? a.sc_bias[tid] : 0.0f;
   }
   if constexpr (RES == 2)
-    for (int blk = wave; blk < MB * NKX; blk += NWAVE) SLU_GLDS16_T(a.sc_w + (size_t)blk * 64 + lane, s_ws + blk * 64);
-  for (int blk = wave; blk < MB * NKS * T; blk += NWAVE) SLU_GLDS16_T(a.w2 + (size_t)blk * 64 + lane, s_w2 + blk * 64);
+    for (int blk = wave; blk < MB * NKX; blk += NWAVE) SLU_GLDS16(a.sc_w + (size_t)blk * 64 + lane, s_ws + blk * 64);
+  for (int blk = wave; blk < MB * NKS * T; blk += NWAVE) SLU_GLDS16(a.w2 + (size_t)blk * 64 + lane, s_w2 + blk * 64);
   for (int blk = wave; blk < MB * 3 * NKS; blk += NWAVE) {
     const int k = blk % (3 * NKS);
     if (k < 2 * NKS) {
-      SLU_GLDS16_T(a.w1 + (size_t)blk * 64 + lane, s_w1 + blk * 64);
+      SLU_GLDS16(a.w1 + (size_t)blk * 64 + lane, s_w1 + blk * 64);
     } else {   // K-step over a3 in accumulator order: elements 4 hh .. 4 hh + 3 of the standard fragments of lanes (row, 0) and (row, 1)
       const uint2* w = reinterpret_cast<const uint2*>(a.w1 + (size_t)blk * 64);
       const uint2 lo = w[jj * 2 + hh], hi = w[(32 + jj) * 2 + hh];
@@ -424,7 +360,7 @@ __global__ __launch_bounds__(512, 2) void tail2_h8_kernel(const TailArgs a) {
   // zero record
   auto stage = [&](const TilePos& tp, int c, int slot, bool valid) {
     uint4* db = s_ring + slot * BUFREC;
-    const uintptr_t zero = reinterpret_cast<uintptr_t>(&g_zero_rec_t);
+    const uintptr_t zero = reinterpret_cast<uintptr_t>(&h8_zero_rec);
     const uintptr_t base0 = reinterpret_cast<uintptr_t>(a.a2) +
                             16 * ((long long)(((size_t)tp.n * a.G + 2 * c) * HW) + (long long)(tp.y0 - PAD) * a.W + (tp.x0 - PAD));
     const uintptr_t base1 = base0 + 16 * (long long)HW;
@@ -435,7 +371,7 @@ __global__ __launch_bounds__(512, 2) void tail2_h8_kernel(const TailArgs a) {
       const int gy = tp.y0 - PAD + (rc & 255), gx = tp.x0 - PAD + ((rc >> 8) & 255);
       const bool ok = valid && (rc >> 17) && (unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W;
       const uintptr_t p = ok ? (((rc >> 16) & 1) ? base1 : base0) + (long long)pc_off[i] : zero;
-      SLU_GLDS16_T(reinterpret_cast<const uint4*>(p), (NBLK_B % NWAVE == 0 || blk < NBLK_B) ? db + blk * 64 : s_trash);
+      SLU_GLDS16(reinterpret_cast<const uint4*>(p), (NBLK_B % NWAVE == 0 || blk < NBLK_B) ? db + blk * 64 : s_trash);
     }
     asm volatile("" ::: "memory");
   };
@@ -458,7 +394,7 @@ __global__ __launch_bounds__(512, 2) void tail2_h8_kernel(const TailArgs a) {
     u32x4v res[HASRES ? MB : 1][HASRES ? NB : 1][2];
     u32x4v xs[RES == 2 ? NKX : 1][RES == 2 ? NB : 1];
 #pragma unroll
-    for (int i = 0; i < MB; ++i)
+    for (int i = 0; i < MB; ++i)      // the two sets in turn, as in tail_h8_kernel
 #pragma unroll
       for (int b = 0; b < NB; ++b)
 #pragma unroll
@@ -476,11 +412,9 @@ __global__ __launch_bounds__(512, 2) void tail2_h8_kernel(const TailArgs a) {
       constexpr int c = decltype(cc)::value;
       constexpr int YOUNG = tail2_younger<NKS, NIB, P, NA1, NRES, NST>(c);
       static_assert(YOUNG <= 63, "vmcnt is a 6-bit counter");
-      if (first && c < P) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the first tile's prologue (and the resident weights)
-      else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(YOUNG) : "memory");
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
+      if (first && c < P) h8_vmcnt<0>();          // the first tile's prologue (and the resident weights)
+      else h8_vmcnt<YOUNG>();
+      h8_lds_barrier();
       {
         constexpr int cn = (c + P) % NKS;
         if (c + P < NKS) stage(cur, cn, wslot, !SLU_ABLATE(a, 1));
@@ -583,16 +517,9 @@ __global__ __launch_bounds__(512, 2) void tail2_h8_kernel(const TailArgs a) {
               for (int q2 = 0; q2 < 2; ++q2) {
                 const int q = 2 * p + q2;
                 const int c4 = (i * 32 + 8 * q) / 4;
-                const f32x4v bi = se4(c4), ba = se4(C / 4 + c4), bb = se4(2 * C / 4 + c4);
-                float2v t0 = {acc3[i][b][4 * q], acc3[i][b][4 * q + 1]}, t1 = {acc3[i][b][4 * q + 2], acc3[i][b][4 * q + 3]};
-                t0 += float2v{bi.x, bi.y};
-                t1 += float2v{bi.z, bi.w};
-                t0 = __builtin_elementwise_max(t0, t0 * slA);
-                t1 = __builtin_elementwise_max(t1, t1 * slA);
-                t0 = t0 * float2v{ba.x, ba.y} + float2v{bb.x, bb.y};
-                t1 = t1 * float2v{ba.z, ba.w} + float2v{bb.z, bb.w};
-                u[2 * q2] = __builtin_bit_cast(unsigned, __builtin_convertvector(t0, half2v));
-                u[2 * q2 + 1] = __builtin_bit_cast(unsigned, __builtin_convertvector(t1, half2v));
+                const H8Quad t = h8_epilogue(acc3[i][b], q, se4(c4), se4(C / 4 + c4), se4(2 * C / 4 + c4), slA);
+                u[2 * q2] = pack2(t.t0);
+                u[2 * q2 + 1] = pack2(t.t1);
               }
               const half8 bf = __builtin_bit_cast(half8, make_uint4(u[0], u[1], u[2], u[3]));
 #pragma unroll
@@ -601,7 +528,7 @@ __global__ __launch_bounds__(512, 2) void tail2_h8_kernel(const TailArgs a) {
           }
       }
     };
-    tail2_static_for(position, std::make_integer_sequence<int, NKS>{});
+    h8_static_for(position, std::make_integer_sequence<int, NKS>{});
     first = false;
 
     // ---- epilogue B: NST stores per lane (counted in tail2_younger).  The accumulator gives lane (jj, hh) HALF of each 16-byte record
@@ -627,54 +554,32 @@ __global__ __launch_bounds__(512, 2) void tail2_h8_kernel(const TailArgs a) {
         const size_t idx0 = ok ? ((size_t)cur.n * a.G + i * 4 + hh) * HW + (size_t)gy * a.W + gx : 0;
         f32x16 sacc;
         if constexpr (RES == 2) {      // the shortcut's 32 x 32 tile: 2 MFMAs, in the accumulator layout of acc_out
-#pragma unroll
-          for (int r = 0; r < 16; ++r) sacc[r] = 0.0f;
+          sacc = f32x16{};
 #pragma unroll
           for (int k = 0; k < NKX; ++k)
             sacc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8, s_ws[(i * NKX + k) * 64 + lane]), __builtin_bit_cast(half8, xs[k][b]), sacc, 0, 0, 0);
         }
 #pragma unroll
         for (int pr = 0; pr < 2; ++pr) {
-          unsigned rw[4] = {0u, 0u, 0u, 0u};       // residual words: [0..1] for q = 2 pr, [2..3] for q = 2 pr + 1
-          if constexpr (HASRES) {
-            const auto s0 = __builtin_amdgcn_permlane32_swap(res[i][b][pr].x, res[i][b][pr].z, false, false);
-            const auto s1 = __builtin_amdgcn_permlane32_swap(res[i][b][pr].y, res[i][b][pr].w, false, false);
-            rw[0] = s0[0]; rw[1] = s1[0]; rw[2] = s0[1]; rw[3] = s1[1];
-          }
+          uint4 rw = make_uint4(0u, 0u, 0u, 0u);       // residual words: x, y for q = 2 pr; z, w for q = 2 pr + 1
+          if constexpr (HASRES) rw = h8_swap16(res[i][b][pr].x, res[i][b][pr].y, res[i][b][pr].z, res[i][b][pr].w);
           unsigned hw[4];
 #pragma unroll
           for (int q2 = 0; q2 < 2; ++q2) {
             const int q = 2 * pr + q2;
             const int c4 = (i * 32 + 8 * q) / 4;
-            const f32x4v bi = se4(3 * C / 4 + c4), ba = se4(4 * C / 4 + c4), bb = se4(5 * C / 4 + c4);
-            float2v t0 = {acco[i][b][4 * q], acco[i][b][4 * q + 1]}, t1 = {acco[i][b][4 * q + 2], acco[i][b][4 * q + 3]};
-            t0 += float2v{bi.x, bi.y};
-            t1 += float2v{bi.z, bi.w};
-            t0 = __builtin_elementwise_max(t0, t0 * slB);
-            t1 = __builtin_elementwise_max(t1, t1 * slB);
-            t0 = t0 * float2v{ba.x, ba.y} + float2v{bb.x, bb.y};
-            t1 = t1 * float2v{ba.z, ba.w} + float2v{bb.z, bb.w};
-            if constexpr (HASRES) {
-              t0 += __builtin_convertvector(__builtin_bit_cast(half2v, rw[2 * q2]), float2v);
-              t1 += __builtin_convertvector(__builtin_bit_cast(half2v, rw[2 * q2 + 1]), float2v);
-            }
+            H8Quad t = h8_epilogue(acco[i][b], q, se4(3 * C / 4 + c4), se4(4 * C / 4 + c4), se4(5 * C / 4 + c4), slB);
+            if constexpr (HASRES) h8_add_resid(t, q2 ? make_uint2(rw.z, rw.w) : make_uint2(rw.x, rw.y));
             if constexpr (RES == 2) {      // rounded to fp16 where the separate launch stores the shortcut
-              const f32x4v bs = se4(6 * C / 4 + c4);
-              float2v u0 = {sacc[4 * q], sacc[4 * q + 1]}, u1 = {sacc[4 * q + 2], sacc[4 * q + 3]};
-              u0 += float2v{bs.x, bs.y};
-              u1 += float2v{bs.z, bs.w};
-              u0 = __builtin_elementwise_max(u0, u0 * slS);
-              u1 = __builtin_elementwise_max(u1, u1 * slS);
-              t0 += __builtin_convertvector(__builtin_convertvector(u0, half2v), float2v);
-              t1 += __builtin_convertvector(__builtin_convertvector(u1, half2v), float2v);
+              const H8Quad u = h8_bias_leaky(sacc, q, se4(6 * C / 4 + c4), slS);
+              t.t0 += round_f16(u.t0);
+              t.t1 += round_f16(u.t1);
             }
-            hw[2 * q2] = __builtin_bit_cast(unsigned, __builtin_convertvector(t0, half2v));
-            hw[2 * q2 + 1] = __builtin_bit_cast(unsigned, __builtin_convertvector(t1, half2v));
+            hw[2 * q2] = pack2(t.t0);
+            hw[2 * q2 + 1] = pack2(t.t1);
           }
-          const auto s0 = __builtin_amdgcn_permlane32_swap(hw[0], hw[2], false, false);
-          const auto s1 = __builtin_amdgcn_permlane32_swap(hw[1], hw[3], false, false);
-          uint4* dst = ok ? reinterpret_cast<uint4*>(a.out) + idx0 + (size_t)(2 * pr) * HW : &g_trash_rec_t;
-          *dst = make_uint4(s0[0], s1[0], s0[1], s1[1]);
+          const uint4 rec = h8_swap16(hw[0], hw[1], hw[2], hw[3]);
+          *(ok ? reinterpret_cast<uint4*>(a.out) + idx0 + (size_t)(2 * pr) * HW : &h8_trash_rec) = rec;
         }
       }
     asm volatile("" ::: "memory");
@@ -698,11 +603,8 @@ int launch_tail2(TailArgs& a, const SluEmit& e) {
   long long gx = 256;
   if (gx > nt) gx = nt;
   if (e.name) return slu_emit_name(e, "tail2_h8_kernel<%d, %d, %d, %d>", MB, RPW, D, RES);
-  auto kern = tail2_h8_kernel<MB, RPW, D, RES>;
   static SluLdsGrant grant;
-  if (slu_grant_dynamic_lds(reinterpret_cast<const void*>(kern), lds, grant) != SLU_OK) return SLU_ELAUNCH;
-  hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(512), lds, e.st, a);
-  SLU_CHECK_LAUNCH();
+  return slu_launch_lds(tail2_h8_kernel<MB, RPW, D, RES>, dim3((unsigned)gx), dim3(512), lds, e.st, grant, a);
 }
 
 template <int MB, int WM, int WN, int RPW, bool W3RES>
@@ -719,11 +621,8 @@ int launch_tail(TailArgs& a, const SluEmit& e) {
   long long gx = 256;                                                 // one 8-wave workgroup per CU (LDS)
   if (gx > nt) gx = nt;
   if (e.name) return slu_emit_name(e, "tail_h8_kernel<%d, %d, %d, %d, %s>", MB, WM, WN, RPW, slu_tf(W3RES));
-  auto kern = tail_h8_kernel<MB, WM, WN, RPW, W3RES>;
   static SluLdsGrant grant;
-  if (slu_grant_dynamic_lds(reinterpret_cast<const void*>(kern), lds, grant) != SLU_OK) return SLU_ELAUNCH;
-  hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(64 * WM * WN), lds, e.st, a);
-  SLU_CHECK_LAUNCH();
+  return slu_launch_lds(tail_h8_kernel<MB, WM, WN, RPW, W3RES>, dim3((unsigned)gx), dim3(64 * WM * WN), lds, e.st, grant, a);
 }
 
 }  // namespace

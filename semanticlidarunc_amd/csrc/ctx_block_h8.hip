@@ -9,7 +9,7 @@
 // network run at full resolution, where they are HBM-bound).
 //
 // Persistent workgroup of 8 waves.  A work item is one image x one STRIP of 64 output columns x a segment of rows, walked DOWN in bands
-// of R = 8 output rows; items dealt round-robin, XCD-aware (see conv2d_h8.hip).  s and a1 live in LDS row RINGS of R + 6 = 14 and
+// of R = 8 output rows; items dealt round-robin, XCD-aware (h8_tile_run, h8_common.h).  s and a1 live in LDS row RINGS of R + 6 = 14 and
 // R + 4 = 12 rows (s with 3 halo columns each side, a1 with 2): a band [b, b + 8) needs s rows [b - 3, b + 11) and a1 rows [b - 2, b + 10),
 // of which all but R rows of each were computed by the band above, so a band computes only R new rows of each.  The first band of a
 // segment fills both rings (14 rows of s, 12 of a1: the old 8 x 64 tile).  Rows outside the image are written as zeros: conv2's and
@@ -28,12 +28,7 @@
 // than CUs.  LDS: S 64.8 KB + A1 54.3 KB + all weights resident 38 KB + epilogue constants = 159 KB (one workgroup per CU).
 #include <algorithm>
 #include <type_traits>
-#include "slu_common.h"
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float float2v __attribute__((ext_vector_type(2)));
+#include "h8_common.h"
 
 namespace {
 
@@ -81,9 +76,6 @@ __device__ unsigned long long g_ctx_prof[8];
 #define CTX_PROF_MARK(i)
 #endif
 
-__device__ uint4 g_trash_rec_c;     // where lanes outside the image store (every lane of every band issues its stores: no branch)
-__device__ uint4 g_zero_rec_c;      // what lanes outside the image load (never written)
-
 // a value the optimiser must treat as unknown: keeps "index + constant" LDS addresses in base-register + immediate form
 __device__ __forceinline__ int opaque(int v) {
   asm volatile("" : "+v"(v));
@@ -100,8 +92,6 @@ __device__ __forceinline__ float2v leaky2(float2v t, float2v sl) {
   return r;
 }
 
-__device__ __forceinline__ unsigned pack2h(float2v t) { return __builtin_bit_cast(unsigned, __builtin_convertvector(t, half2v)); }
-
 // ring slot of v in [0, 2 n)
 __device__ __forceinline__ int wrap(int v, int n) { return v >= n ? v - n : v; }
 
@@ -117,15 +107,8 @@ __global__ __launch_bounds__(64 * NWAVE, 2) void ctx_h8_kernel(const CtxArgs a) 
   const int hh = lane >> 5, jj = lane & 31;
   const size_t HW = (size_t)a.H * a.W;
 
-  int t_beg, t_end, t_step;
-  {
-    const int nwg = gridDim.x, b = blockIdx.x, xcd = b & 7, qq = nwg >> 3, rr = nwg & 7;
-    const int w = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (b >> 3);
-    const long long nt = (long long)a.strips_x * a.nseg * a.N;
-    t_step = nwg;
-    t_beg = w;
-    t_end = w < nt ? w + (int)((nt - w + nwg - 1) / nwg) * nwg : w;
-  }
+  const H8Run run = h8_tile_run(a.strips_x, a.nseg, a.N);
+  const int t_beg = run.beg, t_end = run.end, t_step = run.step;
   if (t_beg >= t_end) return;
 
   {
@@ -195,7 +178,7 @@ __global__ __launch_bounds__(64 * NWAVE, 2) void ctx_h8_kernel(const CtxArgs a) 
       for (int k = 0; k < NKS1; ++k) {
         const int g = 2 * k + hh;
         const bool ok = in && g < a.Gin;
-        xr[i][k] = *(ok ? a.x + (long long)(((size_t)bd.xn * a.Gin + g) * HW) + org + p1_goff[i] : &g_zero_rec_c);
+        xr[i][k] = *(ok ? a.x + (long long)(((size_t)bd.xn * a.Gin + g) * HW) + org + p1_goff[i] : &h8_zero_rec);
       }
     }
   };
@@ -240,7 +223,7 @@ __global__ __launch_bounds__(64 * NWAVE, 2) void ctx_h8_kernel(const CtxArgs a) 
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             const float2v t0 = leaky2(float2v{acc[i][4 * q], acc[i][4 * q + 1]}, sl), t1 = leaky2(float2v{acc[i][4 * q + 2], acc[i][4 * q + 3]}, sl);
-            lds2[wi + q * SRING * 2] = in ? make_uint2(pack2h(t0), pack2h(t1)) : make_uint2(0u, 0u);
+            lds2[wi + q * SRING * 2] = in ? make_uint2(pack2(t0), pack2(t1)) : make_uint2(0u, 0u);
           }
         }
       };
@@ -325,7 +308,7 @@ __global__ __launch_bounds__(64 * NWAVE, 2) void ctx_h8_kernel(const CtxArgs a) 
           } else {
             const float4 ba = ba4[q & 1], bb = bb4[q & 1];
             tp2 = (pr & 1) ? tp2 * float2v{ba.z, ba.w} + float2v{bb.z, bb.w} : tp2 * float2v{ba.x, ba.y} + float2v{bb.x, bb.y};
-            hp[pr] = pack2h(tp2);
+            hp[pr] = pack2(tp2);
             if (pr & 1) {
               const int rc = p2_rc[ib];
               const int gy = ya + (rc & 255), gx = cur.x0 - 2 + (rc >> 8);
@@ -412,12 +395,12 @@ __global__ __launch_bounds__(64 * NWAVE, 2) void ctx_h8_kernel(const CtxArgs a) 
         } else {
           const float4 ba = ba4[q & 1], bb = bb4[q & 1];
           tp2 = (pr & 1) ? tp2 * float2v{ba.z, ba.w} + float2v{bb.z, bb.w} : tp2 * float2v{ba.x, ba.y} + float2v{bb.x, bb.y};
-          tp2 += __builtin_convertvector(__builtin_bit_cast(half2v, (pr & 1) ? sv[q & 1].y : sv[q & 1].x), float2v);
-          hp[pr] = pack2h(tp2);
+          tp2 += unpack2((pr & 1) ? sv[q & 1].y : sv[q & 1].x);
+          hp[pr] = pack2(tp2);
           if (pr & 1) {
             const int gx = cur.x0 + 32 * ib + jj;
             const bool ok = gy < a.H && gx < a.W;
-            uint2* dst = ok ? a.out + (((((size_t)cur.n * 4 + q) * HW + (size_t)gy * a.W + gx) << 1) + hh) : reinterpret_cast<uint2*>(&g_trash_rec_c);
+            uint2* dst = ok ? a.out + (((((size_t)cur.n * 4 + q) * HW + (size_t)gy * a.W + gx) << 1) + hh) : reinterpret_cast<uint2*>(&h8_trash_rec);
             *dst = make_uint2(hp[pr - 1], hp[pr]);
           }
         }
@@ -471,11 +454,8 @@ int launch_ctx(CtxArgs& a, hipStream_t st) {
   if (nt <= 0 || nt > 0x7fffffffLL || (long long)bands * R + 2 * R > 0x7fffffffLL) return SLU_EUNSUPPORTED;
   long long gx = NCU;
   if (gx > nt) gx = nt;
-  auto kern = ctx_h8_kernel<NKS1>;
   static SluLdsGrant grant;
-  if (slu_grant_dynamic_lds(reinterpret_cast<const void*>(kern), lds, grant) != SLU_OK) return SLU_ELAUNCH;
-  hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(64 * NWAVE), lds, st, a);
-  SLU_CHECK_LAUNCH();
+  return slu_launch_lds(ctx_h8_kernel<NKS1>, dim3((unsigned)gx), dim3(64 * NWAVE), lds, st, grant, a);
 }
 
 }  // namespace

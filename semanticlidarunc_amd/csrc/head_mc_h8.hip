@@ -8,10 +8,7 @@
 // classes of a pixel in TWO lanes (lane l and l ^ 32 hold classes 8q + 4h + k, h = l >> 5), so the per-pixel max / sum /
 // entropy / argmax reductions finish with one cross-half shuffle each.  fp32 throughout after the fp16 x fp16 products.
 #include <math.h>
-#include "slu_common.h"
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "h8_common.h"
 
 namespace {
 

@@ -55,6 +55,15 @@ static inline int slu_grant_dynamic_lds(const void* kern, size_t lds, SluLdsGran
   return SLU_OK;
 }
 
+// "grant dynamic LDS, launch, check": the tail of every launcher whose kernel takes more than the default 64 KB of dynamic LDS.  The caller
+// owns the grant record (`static SluLdsGrant grant;` in the launcher template: one per kernel instantiation).
+template <class K, class... Args>
+static inline int slu_launch_lds(K kern, dim3 grid, dim3 block, size_t lds, hipStream_t st, SluLdsGrant& grant, Args... args) {
+  if (slu_grant_dynamic_lds(reinterpret_cast<const void*>(kern), lds, grant) != SLU_OK) return SLU_ELAUNCH;
+  hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
+  SLU_CHECK_LAUNCH();
+}
+
 // 64-lane wavefront sum (all lanes receive the total).
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
