@@ -15,8 +15,6 @@
 // Work decomposition: a workgroup owns TH rows x 64 columns of one image and WM*MB*32 output
 // channels; per K-chunk (CK input channels) it stages the (TH+2*pad) x (64+2*pad) halo tile of
 // each channel and the matching weight fragments into LDS, then every wave runs KS*KS*CK/2 K-steps.
-#include <stdlib.h>
-
 #include "conv_common.h"
 
 using namespace slu_conv;
@@ -40,7 +38,6 @@ namespace {
 template <int KS, int DIL, int PAD, int CK, int MB, int WM, int WN, int RPW, bool GEN>
 __global__ __launch_bounds__(64 * WM * WN, (MB * RPW >= 4) ? 2 : ((MB * RPW >= 2) ? 3 : 4)) void conv_fwd_kernel(const ConvArgs a, const float* __restrict__ resid, float* __restrict__ out) {
   constexpr int NT = 64 * WM * WN;
-  constexpr bool _PIN = true;
   constexpr int TW = 64, TH = WN * RPW, NB = 2 * RPW;
   constexpr int XO = PAD ? 4 : 0;                 // the LDS tile starts XO (16-byte aligned) columns left of x0
   constexpr int LW = TW + 2 * XO, LH = TH + 2 * PAD, LW4 = LW / 4;
@@ -59,13 +56,7 @@ __global__ __launch_bounds__(64 * WM * WN, (MB * RPW >= 4) ? 2 : ((MB * RPW >= 2
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
-  // Workgroups are dealt round-robin over the 8 XCDs: give every XCD one contiguous run of tiles so that
-  // the halo rows/columns neighbouring tiles share are served by that XCD's own L2 (speed only).
-  int t = blockIdx.x;
-  {
-    const int nwg = gridDim.x, xcd = t & 7, qq = nwg >> 3, rr = nwg & 7;
-    t = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (t >> 3);
-  }
+  int t = conv_xcd_tile();
   const int tx = t % a.tiles_x;
   t /= a.tiles_x;
   const int ty = t % a.tiles_y;
@@ -75,19 +66,10 @@ __global__ __launch_bounds__(64 * WM * WN, (MB * RPW >= 4) ? 2 : ((MB * RPW >= 2
   const SrcImg im = src_images(a, n);
 
   f32x16 acc[MB][NB];
-#pragma unroll
-  for (int i = 0; i < MB; ++i)
-#pragma unroll
-    for (int b = 0; b < NB; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][b][r] = 0.0f;
+  SLU_ZERO_ACC2(acc, MB, NB);
 
   if (tid < MBLK * 32) {   // visible to everyone after the first barrier of the chunk loop
-    const int co = mblk0 * 32 + tid;
-    const bool ok = co < a.Cout;
-    s_epi[tid] = (ok && a.bias) ? a.bias[co] : 0.0f;
-    s_epi[MBLK * 32 + tid] = (ok && a.bn_a) ? a.bn_a[co] : 1.0f;
-    s_epi[2 * MBLK * 32 + tid] = (ok && a.bn_a) ? a.bn_b[co] : 0.0f;
+    CONV_FILL_EPI(a, s_epi, MBLK * 32, tid, mblk0 * 32 + tid)
     s_stat[tid] = 0.0;
     s_stat[MBLK * 32 + tid] = 0.0;
   }
@@ -258,12 +240,12 @@ __global__ __launch_bounds__(64 * WM * WN, (MB * RPW >= 4) ? 2 : ((MB * RPW >= 2
 #pragma unroll
     for (int s = 0; s < KSTEPS; ++s) {
       if (s + 1 < KSTEPS) read_step(s + 1, (s + 1) & 1);
-      if (_PIN) __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int b = 0; b < NB; ++b)
 #pragma unroll
         for (int i = 0; i < MB; ++i) acc[i][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s & 1][i], bv[s & 1][b], acc[i][b], 0, 0, 0);
-      if (_PIN) __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_sched_barrier(0);
     }
 #ifdef SLU_CONV_PROF
     asm volatile("s_nop 0" ::"v"(acc[MB - 1][NB - 1][0]));      // the last MFMA has retired
@@ -348,33 +330,11 @@ __global__ void pack_weight_multi_kernel(const slu_pack_job* __restrict__ jobs, 
 // ---------------------------------------------------------------------------------------------
 template <int KS, int DIL, int PAD, int CK, int MB, int WM, int WN, int RPW, bool GEN>
 int launch_cfg(ConvArgs& a, const SluEmit& e) {
-  constexpr int TH = WN * RPW, MBLK = WM * MB;
-  a.tiles_x = (a.W + 63) / 64;
-  a.tiles_y = (a.H + TH - 1) / TH;
-  const long long gx = (long long)a.tiles_x * a.tiles_y * a.N;
-  const int gy = (a.nmblk + MBLK - 1) / MBLK;
-  if (gx <= 0 || gx > 0x7fffffffLL || gy > 65535) return SLU_EUNSUPPORTED;
+  dim3 grid;
+  if (!conv_tile_grid(a, WN * RPW, WM * MB, grid)) return SLU_EUNSUPPORTED;
   if (e.name) return slu_emit_name(e, "conv_fwd_kernel<%d, %d, %d, %d, %d, %d, %d, %d, %s>", KS, DIL, PAD, CK, MB, WM, WN, RPW, slu_tf(GEN));
-  hipLaunchKernelGGL((conv_fwd_kernel<KS, DIL, PAD, CK, MB, WM, WN, RPW, GEN>), dim3((unsigned)gx, (unsigned)gy), dim3(64 * WM * WN),
-                     0, e.st, a, a.resid, a.out);
+  hipLaunchKernelGGL((conv_fwd_kernel<KS, DIL, PAD, CK, MB, WM, WN, RPW, GEN>), grid, dim3(64 * WM * WN), 0, e.st, a, a.resid, a.out);
   SLU_CHECK_LAUNCH();
-}
-
-template <int KS, int DIL, int PAD, int CK, bool GEN>
-int launch_tiles(ConvArgs& a, int cfg, const SluEmit& e) {
-  switch (cfg) {
-    case M32_TH8:  return launch_cfg<KS, DIL, PAD, CK, 1, 1, 4, 2, GEN>(a, e);
-    case M64_TH8:  return launch_cfg<KS, DIL, PAD, CK, 2, 1, 4, 2, GEN>(a, e);
-    case M128_TH4: return launch_cfg<KS, DIL, PAD, CK, 2, 2, 2, 2, GEN>(a, e);
-    case M32_TH4:  return launch_cfg<KS, DIL, PAD, CK, 1, 1, 4, 1, GEN>(a, e);
-    case M64_TH4:  return launch_cfg<KS, DIL, PAD, CK, 2, 1, 4, 1, GEN>(a, e);
-  }
-  return SLU_EUNSUPPORTED;
-}
-
-template <int KS, int DIL, int PAD, int CK>
-int launch_family(ConvArgs& a, int cfg, const SluEmit& e) {
-  return a.gen ? launch_tiles<KS, DIL, PAD, CK, true>(a, cfg, e) : launch_tiles<KS, DIL, PAD, CK, false>(a, cfg, e);
 }
 
 // the one traversal of the forward dispatch: slu_conv2d_fwd launches at its leaf, slu_conv2d_kernel_name has the leaf name itself
@@ -384,12 +344,13 @@ int conv_dispatch(const slu_conv_desc* d, const SluEmit& e) {
   const int rc = fill_args(d, a);
   if (rc != SLU_OK) return rc;
   const int cfg = choose_cfg(a);
-  if (d->ksize == 1 && d->dil == 1 && d->pad == 0) return launch_family<1, 1, 0, 16>(a, cfg, e);
-  if (d->ksize == 3 && d->dil == 1 && d->pad == 1) return launch_family<3, 1, 1, 8>(a, cfg, e);
-  if (d->ksize == 3 && d->dil == 2 && d->pad == 2) return launch_family<3, 2, 2, 8>(a, cfg, e);
-  if (d->ksize == 2 && d->dil == 2 && d->pad == 1) return launch_family<2, 2, 1, 8>(a, cfg, e);
-  if (d->ksize == 2 && d->dil == 1 && d->pad == 1) return launch_family<2, 1, 1, 8>(a, cfg, e);
-  return SLU_EUNSUPPORTED;
+  return slu_conv_family(d->ksize, d->dil, d->pad, [&](auto g) {
+    return conv_tile_shape(a, cfg, [&](auto s) {
+      using G = decltype(g);
+      using S = decltype(s);
+      return launch_cfg<G::KS, G::DIL, G::PAD, G::KS == 1 ? 16 : 8, S::MB, S::WM, S::WN, S::RPW, S::GEN>(a, e);
+    });
+  });
 }
 
 }  // namespace
@@ -407,15 +368,13 @@ extern "C" int slu_pack_conv_weight(const float* w, int cout, int cin, int ksize
   const size_t total = slu_packed_weight_floats(cout, cin, ksize, ck);
   if (total == 0) return SLU_EINVAL;
   const int nchunks = (cin + ck - 1) / ck;
-  const unsigned blocks = (unsigned)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-  hipLaunchKernelGGL(pack_weight_kernel, dim3(blocks), dim3(256), 0, slu_stream(stream), w, cout, cin, ksize, ck, nchunks, total, out);
+  hipLaunchKernelGGL(pack_weight_kernel, dim3(slu_grid_1d(total, 4096)), dim3(256), 0, slu_stream(stream), w, cout, cin, ksize, ck, nchunks, total, out);
   SLU_CHECK_LAUNCH();
 }
 
 extern "C" int slu_pack_conv_weights_multi(const slu_pack_job* jobs_dev, int njobs, size_t total, slu_stream_t stream) {
   if (!jobs_dev || njobs <= 0 || total == 0) return SLU_EINVAL;
-  const unsigned blocks = (unsigned)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
-  hipLaunchKernelGGL(pack_weight_multi_kernel, dim3(blocks), dim3(256), 0, slu_stream(stream), jobs_dev, njobs, total);
+  hipLaunchKernelGGL(pack_weight_multi_kernel, dim3(slu_grid_1d(total, 8192)), dim3(256), 0, slu_stream(stream), jobs_dev, njobs, total);
   SLU_CHECK_LAUNCH();
 }
 

@@ -1,8 +1,8 @@
-// Split-fp16 ("f16x3") variant of the fused conv (same fusion, same launch arguments, same epilogue as
-// conv2d.hip): every fp32 operand is split x = hi + lo with hi = fp16(x), lo = fp16(x - hi), and each K=16
-// step issues three v_mfma_f32_32x32x16_f16 (hi*hi + hi*lo + lo*hi, fp32 accumulate).  The dropped lo*lo
-// term is ~2^-22 relative, so results agree with the exact-fp32 kernel to fp32-level accuracy while the
-// matrix-core time drops 5.3x (3 x 32 cycles per 16 channels x 32 x 32 instead of 8 x 64), which moves the
+// Split-fp16 ("f16x3") variant of the fused conv (same fusion, same launch arguments and same epilogue options as
+// conv2d.hip, in the per-element form of conv_common.h's conv_epi_value): every fp32 operand is split
+// x = hi + lo with hi = fp16(x), lo = fp16(x - hi), and each K=16 step issues three v_mfma_f32_32x32x16_f16
+// (hi*hi + hi*lo + lo*hi, fp32 accumulate).  The dropped lo*lo term is ~2^-22 relative, so results agree
+// with the exact-fp32 kernel to fp32-level accuracy while the matrix-core time drops 5.3x (3 x 32 cycles per 16 channels x 32 x 32 instead of 8 x 64), which moves the
 // 3x3 / 2x2 convs of the range-image stack from MFMA-bound towards HBM-bound.
 //
 // LDS images (channel-innermost so one ds_read_b128 is one MFMA operand):
@@ -61,11 +61,7 @@ __global__ __launch_bounds__(64 * WM * WN, (MB * RPW >= 4) ? 1 : 2) void conv_f1
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
-  int t = blockIdx.x;
-  {
-    const int nwg = gridDim.x, xcd = t & 7, qq = nwg >> 3, rr = nwg & 7;
-    t = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (t >> 3);
-  }
+  int t = conv_xcd_tile();
   const int tx = t % a.tiles_x;
   t /= a.tiles_x;
   const int ty = t % a.tiles_y;
@@ -75,20 +71,9 @@ __global__ __launch_bounds__(64 * WM * WN, (MB * RPW >= 4) ? 1 : 2) void conv_f1
   const SrcImg im = src_images(a, n);
 
   f32x16 acc[MB][NB];
-#pragma unroll
-  for (int i = 0; i < MB; ++i)
-#pragma unroll
-    for (int b = 0; b < NB; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][b][r] = 0.0f;
+  SLU_ZERO_ACC2(acc, MB, NB);
 
-  if (tid < MBLK * 32) {
-    const int co = mblk0 * 32 + tid;
-    const bool ok = co < a.Cout;
-    s_epi[tid] = (ok && a.bias) ? a.bias[co] : 0.0f;
-    s_epi[MBLK * 32 + tid] = (ok && a.bn_a) ? a.bn_a[co] : 1.0f;
-    s_epi[2 * MBLK * 32 + tid] = (ok && a.bn_a) ? a.bn_b[co] : 0.0f;
-  }
+  if (tid < MBLK * 32) CONV_FILL_EPI(a, s_epi, MBLK * 32, tid, mblk0 * 32 + tid)
 
   const int hh = lane >> 5, jj = lane & 31;
   int bcol[KS];                                     // padded slot of (first column + lane + tap shift), per horizontal tap
@@ -255,12 +240,10 @@ __global__ __launch_bounds__(64 * WM * WN, (MB * RPW >= 4) ? 1 : 2) void conv_f1
     }
   }
 
-  // ---- epilogue (identical to the fp32 kernel: the D fragment layout does not depend on the input dtype) ----
-  // activation as two leaky slopes (1.0 = identity): before BatchNorm/residual, or (has_act & 4) after them
-  const int act_kind = a.has_act & 3;
-  const bool act_late = (a.has_act & 4) != 0, act_tanh = act_kind == 2, act_silu = act_kind == 3;
-  const float slope_pre = (act_kind == 1 && !act_late) ? a.slope : 1.0f;
-  const float slope_post = (act_kind == 1 && act_late) ? a.slope : 1.0f;
+  // ---- epilogue: the per-element form with every option, for all layers -- what the fp32 kernel (conv_epilogue) runs only for tanh / SiLU /
+  //      a late activation: one residual load and wait per stored element, no batched residual loads, no batch statistics.  The D fragment
+  //      layout (the pixel on the lane, the channel on the register) is the fp32 kernel's: it does not depend on the input dtype. ----
+  const ConvAct act = conv_act(a.has_act, a.slope);
   const size_t plane = (size_t)a.H * a.W;
 #pragma unroll
   for (int i = 0; i < MB; ++i) {
@@ -271,17 +254,11 @@ __global__ __launch_bounds__(64 * WM * WN, (MB * RPW >= 4) ? 1 : 2) void conv_f1
       const bool pix_ok = gy < a.H && gx < a.W;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int cl = ml * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+        const int cl = slu_frag_row(ml * 32, r, hh);
         const int co = mblk0 * 32 + cl;
         const bool ok = pix_ok && co < a.Cout;
         const size_t o = ok ? ((size_t)n * a.Cout + co) * plane + (size_t)gy * a.W + gx : 0;
-        float v = acc[i][b][r] + s_epi[cl];
-        v = v > 0.0f ? v : v * slope_pre;
-        if (act_tanh) v = tanhf(v);
-        if (act_silu) v = v / (1.0f + expf(-v));      // nn.SiLU (EfficientNetV2 blocks)
-        v = v * s_epi[MBLK * 32 + cl] + s_epi[2 * MBLK * 32 + cl];
-        if (resid) v += resid[o];
-        v = v > 0.0f ? v : v * slope_post;
+        const float v = conv_epi_value(acc[i][b][r], s_epi, MBLK * 32, cl, act, resid, o);
         if (ok) out[o] = v;
       }
     }
@@ -313,20 +290,10 @@ __global__ __launch_bounds__(256, (MB * NBW >= 8) ? 2 : ((MB * NBW >= 4) ? 3 : 4
   const long long nblocks = (long long)a.N * HW / 32;
   const long long pb0 = ((long long)blockIdx.x * 4 + wave) * NBW;
 
-  if (tid < MB * 32) {
-    const bool ok = tid < a.Cout;
-    s_epi[tid] = (ok && a.bias) ? a.bias[tid] : 0.0f;
-    s_epi[MB * 32 + tid] = (ok && a.bn_a) ? a.bn_a[tid] : 1.0f;
-    s_epi[2 * MB * 32 + tid] = (ok && a.bn_a) ? a.bn_b[tid] : 0.0f;
-  }
+  if (tid < MB * 32) CONV_FILL_EPI(a, s_epi, MB * 32, tid, tid)
 
   f32x16 acc[MB][NBW];
-#pragma unroll
-  for (int i = 0; i < MB; ++i)
-#pragma unroll
-    for (int b = 0; b < NBW; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][b][r] = 0.0f;
+  SLU_ZERO_ACC2(acc, MB, NBW);
 
   // per pixel block: image index and offset inside the H*W plane of this lane's pixel
   long long img[NBW];
@@ -425,27 +392,18 @@ __global__ __launch_bounds__(256, (MB * NBW >= 8) ? 2 : ((MB * NBW >= 4) ? 3 : 4
     }
   }
 
-  // activation as two leaky slopes (1.0 = identity): before BatchNorm/residual, or (has_act & 4) after them
-  const int act_kind = a.has_act & 3;
-  const bool act_late = (a.has_act & 4) != 0, act_tanh = act_kind == 2, act_silu = act_kind == 3;
-  const float slope_pre = (act_kind == 1 && !act_late) ? a.slope : 1.0f;
-  const float slope_post = (act_kind == 1 && act_late) ? a.slope : 1.0f;
+  // ---- epilogue: the per-element form, as in conv_f16x3_kernel ----
+  const ConvAct act = conv_act(a.has_act, a.slope);
 #pragma unroll
   for (int i = 0; i < MB; ++i)
 #pragma unroll
     for (int b = 0; b < NBW; ++b)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int co = i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+        const int co = slu_frag_row(i * 32, r, hh);
         const bool ok = live[b] && co < a.Cout;
         const size_t o = ok ? ((size_t)img[b] * a.Cout + co) * HW + hw[b] : 0;
-        float v = acc[i][b][r] + s_epi[co];
-        v = v > 0.0f ? v : v * slope_pre;
-        if (act_tanh) v = tanhf(v);
-        if (act_silu) v = v / (1.0f + expf(-v));      // nn.SiLU (EfficientNetV2 blocks)
-        v = v * s_epi[MB * 32 + co] + s_epi[2 * MB * 32 + co];
-        if (resid) v += resid[o];
-        v = v > 0.0f ? v : v * slope_post;
+        const float v = conv_epi_value(acc[i][b][r], s_epi, MB * 32, co, act, resid, o);
         if (ok) out[o] = v;
       }
 }
@@ -457,11 +415,8 @@ int launch_1x1(ConvArgs& a, const SluEmit& e) {
   const long long gx = (nblocks + 4 * NBW - 1) / (4 * NBW);
   if (gx <= 0 || gx > 0x7fffffffLL) return SLU_EUNSUPPORTED;
   if (e.name) return slu_emit_name(e, "conv1x1_f16x3_kernel<%d, %d>", MB, NBW);
-  auto kern = conv1x1_f16x3_kernel<MB, NBW>;
   static SluLdsGrant grant;
-  if (slu_grant_dynamic_lds(reinterpret_cast<const void*>(kern), lds, grant) != SLU_OK) return SLU_ELAUNCH;
-  hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(256), lds, e.st, a, a.resid, a.out);
-  SLU_CHECK_LAUNCH();
+  return slu_launch_lds(conv1x1_f16x3_kernel<MB, NBW>, dim3((unsigned)gx), dim3(256), lds, e.st, grant, a, a.resid, a.out);
 }
 
 // the streaming kernel applies when every source is plain and 16-channel aligned and pixel blocks do not straddle images
@@ -512,34 +467,11 @@ int launch_cfg16(ConvArgs& a, const SluEmit& e) {
   constexpr int REC = (TH + 2 * PAD) * ((64 + 2 * XO) + (64 + 2 * XO) / 8);
   constexpr size_t lds = (size_t)4 * REC * 16 + (size_t)2 * MBLK * T * 64 * 16 + (size_t)3 * MBLK * 32 * 4;
   static_assert(lds <= 160 * 1024, "LDS budget");
-  a.tiles_x = (a.W + 63) / 64;
-  a.tiles_y = (a.H + TH - 1) / TH;
-  const long long gx = (long long)a.tiles_x * a.tiles_y * a.N;
-  const int gy = (a.nmblk + MBLK - 1) / MBLK;
-  if (gx <= 0 || gx > 0x7fffffffLL || gy > 65535) return SLU_EUNSUPPORTED;
+  dim3 grid;
+  if (!conv_tile_grid(a, TH, MBLK, grid)) return SLU_EUNSUPPORTED;
   if (e.name) return slu_emit_name(e, "conv_f16x3_kernel<%d, %d, %d, %d, %d, %d, %d, %s>", KS, DIL, PAD, MB, WM, WN, RPW, slu_tf(GEN));
-  auto kern = conv_f16x3_kernel<KS, DIL, PAD, MB, WM, WN, RPW, GEN>;
   static SluLdsGrant grant;
-  if (slu_grant_dynamic_lds(reinterpret_cast<const void*>(kern), lds, grant) != SLU_OK) return SLU_ELAUNCH;
-  hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)gy), dim3(64 * WM * WN), lds, e.st, a, a.resid, a.out);
-  SLU_CHECK_LAUNCH();
-}
-
-template <int KS, int DIL, int PAD, bool GEN>
-int launch_tiles16(ConvArgs& a, int cfg, const SluEmit& e) {
-  switch (cfg) {
-    case M32_TH8:  return launch_cfg16<KS, DIL, PAD, 1, 1, 4, 2, GEN>(a, e);
-    case M64_TH8:  return launch_cfg16<KS, DIL, PAD, 2, 1, 4, 2, GEN>(a, e);
-    case M128_TH4: return launch_cfg16<KS, DIL, PAD, 2, 2, 2, 2, GEN>(a, e);
-    case M32_TH4:  return launch_cfg16<KS, DIL, PAD, 1, 1, 4, 1, GEN>(a, e);
-    case M64_TH4:  return launch_cfg16<KS, DIL, PAD, 2, 1, 4, 1, GEN>(a, e);
-  }
-  return SLU_EUNSUPPORTED;
-}
-
-template <int KS, int DIL, int PAD>
-int launch_family16(ConvArgs& a, int cfg, const SluEmit& e) {
-  return a.gen ? launch_tiles16<KS, DIL, PAD, true>(a, cfg, e) : launch_tiles16<KS, DIL, PAD, false>(a, cfg, e);
+  return slu_launch_lds(conv_f16x3_kernel<KS, DIL, PAD, MB, WM, WN, RPW, GEN>, grid, dim3(64 * WM * WN), lds, e.st, grant, a, a.resid, a.out);
 }
 
 }  // namespace
@@ -556,8 +488,7 @@ extern "C" int slu_pack_conv_weight_f16x3(const float* w, int cout, int cin, int
   if (bytes == 0) return SLU_EINVAL;
   const size_t frags = bytes / 32;      // one (hi, lo) pair of uint4 per lane
   const int nchunks = (cin + CK16 - 1) / CK16;
-  const unsigned blocks = (unsigned)((frags + 255) / 256 > 4096 ? 4096 : (frags + 255) / 256);
-  hipLaunchKernelGGL(pack_f16x3_kernel, dim3(blocks), dim3(256), 0, slu_stream(stream), w, cout, cin, ksize, nchunks, frags,
+  hipLaunchKernelGGL(pack_f16x3_kernel, dim3(slu_grid_1d(frags, 4096)), dim3(256), 0, slu_stream(stream), w, cout, cin, ksize, nchunks, frags,
                      reinterpret_cast<uint4*>(out));
   SLU_CHECK_LAUNCH();
 }
@@ -572,10 +503,11 @@ int slu_conv2d_f16x3_dispatch(const slu_conv_desc* d, const SluEmit& e) {
   // 4-row tiles only: the (hi, lo) input tile of an 8-row tile leaves room for a single workgroup per CU
   if (cfg == M32_TH8) cfg = M32_TH4;
   if (cfg == M64_TH8) cfg = M64_TH4;
-  if (d->ksize == 1 && d->dil == 1 && d->pad == 0) return launch_family16<1, 1, 0>(a, cfg, e);
-  if (d->ksize == 3 && d->dil == 1 && d->pad == 1) return launch_family16<3, 1, 1>(a, cfg, e);
-  if (d->ksize == 3 && d->dil == 2 && d->pad == 2) return launch_family16<3, 2, 2>(a, cfg, e);
-  if (d->ksize == 2 && d->dil == 2 && d->pad == 1) return launch_family16<2, 2, 1>(a, cfg, e);
-  if (d->ksize == 2 && d->dil == 1 && d->pad == 1) return launch_family16<2, 1, 1>(a, cfg, e);
-  return SLU_EUNSUPPORTED;
+  return slu_conv_family(d->ksize, d->dil, d->pad, [&](auto g) {
+    return conv_tile_shape(a, cfg, [&](auto s) {
+      using G = decltype(g);
+      using S = decltype(s);
+      return launch_cfg16<G::KS, G::DIL, G::PAD, S::MB, S::WM, S::WN, S::RPW, S::GEN>(a, e);
+    });
+  });
 }

@@ -1,13 +1,10 @@
 // Definitions shared by the conv kernels (fp32-exact and split-fp16): launch arguments, input addressing
 // (concatenated sources, PixelShuffle, folded-dropout multipliers), tile-shape choice.
 #pragma once
-#include <utility>
 #include <stdio.h>
 #include <stdlib.h>
 
 #include "slu_common.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace slu_conv {
 
@@ -20,17 +17,6 @@ struct SrcDev {
   int ccount;  // number of conv-input channels contributed
   int nb;      // images held by the tensor (output image n reads image n % nb); 0 = N
 };
-
-// compile-time loop: f(std::integral_constant<int, 0>{}), ..., f(std::integral_constant<int, N - 1>{}) -- for bodies too large for `#pragma unroll`
-// whose index must stay a constant (register arrays indexed by it would otherwise move to scratch memory)
-template <class F, int... Is>
-__device__ __forceinline__ void slu_static_for_impl(F&& f, std::integer_sequence<int, Is...>) {
-  (f(std::integral_constant<int, Is>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void slu_static_for(F&& f) {
-  slu_static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
 
 struct ConvArgs {
   SrcDev src[SLU_MAX_SRC];
@@ -150,6 +136,49 @@ __device__ __forceinline__ float4 item_value(const Item<GEN>& it, bool ok, bool 
 }
 
 
+// Workgroups are dealt round-robin over the 8 XCDs: give every XCD one contiguous run of tiles so that the halo rows / columns neighbouring
+// tiles share are served by that XCD's own L2 (speed only).  Returns the tile number of this workgroup of a grid whose x dimension counts tiles.
+__device__ __forceinline__ int conv_xcd_tile() {
+  const int t = blockIdx.x, nwg = gridDim.x, xcd = t & 7, qq = nwg >> 3, rr = nwg & 7;
+  return (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (t >> 3);
+}
+
+// s_epi = bias | bn_a | bn_b of `nch` output channels: entry i takes channel co (identity where the layer has none or co >= Cout).
+// A macro, as H8_FILL_EPI (h8_common.h) had to be.
+#define CONV_FILL_EPI(a, s_epi, nch, i, co)                                \
+  {                                                                        \
+    const bool ok = (co) < (a).Cout;                                       \
+    (s_epi)[i] = (ok && (a).bias) ? (a).bias[co] : 0.0f;                   \
+    (s_epi)[(nch) + (i)] = (ok && (a).bn_a) ? (a).bn_a[co] : 1.0f;         \
+    (s_epi)[2 * (nch) + (i)] = (ok && (a).bn_a) ? (a).bn_b[co] : 0.0f;     \
+  }
+
+// has_act decoded: tanh, SiLU, and the leaky activation as two slopes (1.0 = identity), before BatchNorm / residual or (has_act & 4) after them.
+// By value, and the members in the order the kernels' own copies computed them: in any other order the same instructions come out re-scheduled.
+struct ConvAct {
+  bool tanh_, silu_;
+  float slope_pre, slope_post;
+};
+__device__ __forceinline__ ConvAct conv_act(int has_act, float slope) {
+  const int act_kind = has_act & 3;
+  const bool act_late = (has_act & 4) != 0, act_tanh = act_kind == 2, act_silu = act_kind == 3;
+  const float slope_pre = (act_kind == 1 && !act_late) ? slope : 1.0f;
+  const float slope_post = (act_kind == 1 && act_late) ? slope : 1.0f;
+  return ConvAct{act_tanh, act_silu, slope_pre, slope_post};
+}
+// One stored value with every option: bias -> activation -> folded BatchNorm -> + residual (resid[o], nullable) -> late activation.  s_epi is
+// bias | bn_a | bn_b of nch channels (CONV_FILL_EPI), i the channel's entry.  The constants are read here, in this order: handed in as three
+// values (then read before the activation) 54 of the 55 split-fp16 kernels and all 50 conv_fwd_kernel come out different (profiles/r08).
+__device__ __forceinline__ float conv_epi_value(float acc, const float* s_epi, int nch, int i, ConvAct c, const float* __restrict__ resid, size_t o) {
+  float v = acc + s_epi[i];
+  v = v > 0.0f ? v : v * c.slope_pre;
+  if (c.tanh_) v = tanhf(v);
+  if (c.silu_) v = v / (1.0f + expf(-v));      // nn.SiLU (EfficientNetV2 blocks)
+  v = v * s_epi[nch + i] + s_epi[2 * nch + i];
+  if (resid) v += resid[o];
+  return v > 0.0f ? v : v * c.slope_post;
+}
+
 // Epilogue of the fp32 conv kernel (conv2d.hip): the accumulators of one wave (MB channel blocks x NB pixel blocks of the
 // workgroup's tile at (n, y0, x0), channel blocks from mblk0 + wm * MB) -> bias, activation, folded BatchNorm, residual, store, batch statistics
 // into the workgroup's LDS accumulators s_stat (flushed to a.stats by the caller after a barrier).
@@ -161,11 +190,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[M
   //      forbids out aliasing an input), so residual loads are scheduled ahead of the stores instead of
   //      each waiting behind the previous store. ----
   const size_t plane = (size_t)a.H * a.W;
-  // activation as two leaky slopes (1.0 = identity): before BatchNorm/residual, or (has_act & 4) after them
-  const int act_kind = a.has_act & 3;
-  const bool act_late = (a.has_act & 4) != 0, act_tanh = act_kind == 2, act_silu = act_kind == 3;
-  const float slope_pre = (act_kind == 1 && !act_late) ? a.slope : 1.0f;
-  const float slope_post = (act_kind == 1 && act_late) ? a.slope : 1.0f;
+  const ConvAct act = conv_act(a.has_act, a.slope);
   const bool want_stats = a.stats != nullptr;      // wave-uniform
   // The accumulator indices must be COMPILE-TIME constants: with a plain `#pragma unroll` over i the body (NB x 16 stores + the statistics
   // butterfly) was too large for the unroller in the MB = 2, NB = 4 instantiations ("loop not unrolled"), acc[i][b] became a dynamic index and
@@ -174,7 +199,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[M
   // LeakyReLU -> folded BatchNorm [-> + residual] -- is a tight loop with the residual loads of an accumulator tile issued 8 at a time: as
   // per-element branches the options cost ~60 instructions and, with a residual, one load + s_waitcnt vmcnt(0) per stored element (128 memory
   // round trips per lane in a row).
-  const bool special = act_tanh || act_silu || slope_post != 1.0f;
+  const bool special = act.tanh_ || act.silu_ || act.slope_post != 1.0f;
   slu_static_for<MB>([&](auto ic) __attribute__((always_inline)) {
     constexpr int i = decltype(ic)::value;
     const int ml = wm * MB + i;               // channel block inside the workgroup tile
@@ -189,17 +214,11 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[M
       if (special) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int cl = ml * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+          const int cl = slu_frag_row(ml * 32, r, hh);
           const int co = mblk0 * 32 + cl;
           const bool ok = pix_ok && co < a.Cout;
           const size_t o = ok ? ((size_t)n * a.Cout + co) * plane + pix : 0;
-          float v = acc[i][b][r] + s_epi[cl];
-          v = v > 0.0f ? v : v * slope_pre;
-          if (act_tanh) v = tanhf(v);
-          if (act_silu) v = v / (1.0f + expf(-v));      // nn.SiLU (EfficientNetV2 blocks)
-          v = v * s_epi[MBLK * 32 + cl] + s_epi[2 * MBLK * 32 + cl];
-          if (resid) v += resid[o];
-          v = v > 0.0f ? v : v * slope_post;
+          const float v = conv_epi_value(acc[i][b][r], s_epi, MBLK * 32, cl, act, resid, o);
           if (ok) out[o] = v;
           if (want_stats && ok) { ssum[r] += v; ssq[r] += v * v; }
         }
@@ -212,7 +231,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[M
         if (resid) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const int co = mblk0 * 32 + ml * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+            const int co = slu_frag_row(mblk0 * 32 + ml * 32, r, hh);
             rv[r] = resid[(pix_ok && co < a.Cout) ? ((size_t)n * a.Cout + co) * plane + pix : 0];
           }
         } else {
@@ -221,10 +240,10 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[M
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int cl = ml * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+          const int cl = slu_frag_row(ml * 32, r, hh);
           const bool ok = pix_ok && mblk0 * 32 + cl < a.Cout;
           float v = acc[i][b][r] + s_epi[cl];
-          v = v > 0.0f ? v : v * slope_pre;
+          v = v > 0.0f ? v : v * act.slope_pre;
           v = v * s_epi[MBLK * 32 + cl] + s_epi[2 * MBLK * 32 + cl] + rv[r];
           acc[i][b][r] = v;
           if (want_stats && ok) { ssum[r] += v; ssq[r] += v * v; }
@@ -232,7 +251,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[M
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int co = mblk0 * 32 + ml * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+          const int co = slu_frag_row(mblk0 * 32 + ml * 32, r, hh);
           if (pix_ok && co < a.Cout) out[((size_t)n * a.Cout + co) * plane + pix] = acc[i][b][r];
         }
       }
@@ -246,7 +265,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[M
 #pragma unroll
         for (int o = 16; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o, 64); s2 += __shfl_xor(s2, o, 64); }
         if (jj == 0) {
-          const int cl = ml * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+          const int cl = slu_frag_row(ml * 32, r, hh);
           atomicAdd(&s_stat[cl], (double)s1);
           atomicAdd(&s_stat[MBLK * 32 + cl], (double)s2);
         }
@@ -256,6 +275,39 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[M
 }
 
 enum TileCfg { M32_TH8 = 0, M64_TH8, M128_TH4, M32_TH4, M64_TH4 };
+
+// TileCfg -> tile shape <MB, WM, WN, RPW> (channel blocks per wave, waves along channels, waves along rows, rows per wave) and a.gen -> GEN:
+// f receives them as a type.  Both tiled forward kernels (conv2d.hip, conv2d_f16x3.hip) are instantiated for exactly these ten.
+template <int MB_, int WM_, int WN_, int RPW_, bool GEN_>
+struct TileShape {
+  static constexpr int MB = MB_, WM = WM_, WN = WN_, RPW = RPW_;
+  static constexpr bool GEN = GEN_;
+};
+template <bool GEN, class F>
+inline int conv_tile_shape(int cfg, F&& f) {
+  switch (cfg) {
+    case M32_TH8:  return f(TileShape<1, 1, 4, 2, GEN>{});
+    case M64_TH8:  return f(TileShape<2, 1, 4, 2, GEN>{});
+    case M128_TH4: return f(TileShape<2, 2, 2, 2, GEN>{});
+    case M32_TH4:  return f(TileShape<1, 1, 4, 1, GEN>{});
+    case M64_TH4:  return f(TileShape<2, 1, 4, 1, GEN>{});
+  }
+  return SLU_EUNSUPPORTED;
+}
+template <class F>
+inline int conv_tile_shape(const ConvArgs& a, int cfg, F&& f) {
+  return a.gen ? conv_tile_shape<true>(cfg, f) : conv_tile_shape<false>(cfg, f);
+}
+
+// grid of a tiled kernel with TH x 64 pixel tiles and MBLK channel blocks per workgroup (also sets a.tiles_x / a.tiles_y); false = refused
+inline bool conv_tile_grid(ConvArgs& a, int TH, int MBLK, dim3& grid) {
+  a.tiles_x = (a.W + 63) / 64;
+  a.tiles_y = (a.H + TH - 1) / TH;
+  const long long gx = (long long)a.tiles_x * a.tiles_y * a.N;
+  const int gy = (a.nmblk + MBLK - 1) / MBLK;
+  grid = dim3((unsigned)gx, (unsigned)gy);
+  return gx > 0 && gx <= 0x7fffffffLL && gy <= 65535;
+}
 
 inline long long wg_count(const ConvArgs& a, int th, int mblk) {
   return (long long)a.N * ((a.H + th - 1) / th) * ((a.W + 63) / 64) * ((a.nmblk + mblk - 1) / mblk);

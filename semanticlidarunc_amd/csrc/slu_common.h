@@ -4,7 +4,10 @@
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <utility>
 #include "slu.h"
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));      // D fragment of a 32x32 MFMA
 
 #define SLU_CHECK_LAUNCH()                                   \
   do {                                                       \
@@ -63,6 +66,48 @@ static inline int slu_launch_lds(K kern, dim3 grid, dim3 block, size_t lds, hipS
   hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
   SLU_CHECK_LAUNCH();
 }
+
+// blocks of a grid-stride kernel with 256 threads over `total` items, at most `cap`
+static inline unsigned slu_grid_1d(size_t total, unsigned cap) { return (unsigned)((total + 255) / 256 > cap ? cap : (total + 255) / 256); }
+
+// The conv geometries the kernels are instantiated for: f receives the one that matches (ksize, dil, pad) as a type.
+template <int KS_, int DIL_, int PAD_>
+struct SluConvGeo {
+  static constexpr int KS = KS_, DIL = DIL_, PAD = PAD_;
+};
+template <class F>
+static inline int slu_conv_family(int ksize, int dil, int pad, F&& f) {
+  if (ksize == 1 && dil == 1 && pad == 0) return f(SluConvGeo<1, 1, 0>{});
+  if (ksize == 3 && dil == 1 && pad == 1) return f(SluConvGeo<3, 1, 1>{});
+  if (ksize == 3 && dil == 2 && pad == 2) return f(SluConvGeo<3, 2, 2>{});
+  if (ksize == 2 && dil == 2 && pad == 1) return f(SluConvGeo<2, 2, 1>{});
+  if (ksize == 2 && dil == 1 && pad == 1) return f(SluConvGeo<2, 1, 1>{});
+  return SLU_EUNSUPPORTED;
+}
+
+// compile-time loop: f(std::integral_constant<int, 0>{}), ..., f(std::integral_constant<int, N - 1>{}) -- for bodies too large for `#pragma unroll`
+// whose index must stay a constant (register arrays indexed by it would otherwise move to scratch memory)
+template <class F, int... Is>
+__device__ __forceinline__ void slu_static_for_impl(F&& f, std::integer_sequence<int, Is...>) {
+  (f(std::integral_constant<int, Is>{}), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void slu_static_for(F&& f) {
+  slu_static_for_impl(f, std::make_integer_sequence<int, N>{});
+}
+
+// Row (the M index: an output channel) of register r of the f32x16 D fragment held by lane half hh = lane >> 5, counted from row0; the column
+// is lane & 31.  row0 comes first in the sum, as the copies had it: without it (`row0 + slu_frag_row(r, hh)`) the sum re-associates and 9 of
+// the 14 wgrad kernels change.
+__device__ __forceinline__ constexpr int slu_frag_row(int row0, int r, int hh) { return row0 + (r & 3) + 8 * (r >> 2) + 4 * hh; }
+
+// acc[0 .. n) = 0 for f32x16 accumulators; a 2-D array goes row by row.  Macros: as a function taking the array by reference the zeroing
+// re-scheduled 30 of the 55 split-fp16 conv kernels.
+#define SLU_ZERO_ACC(acc, n)                 \
+  _Pragma("unroll") for (int z_ = 0; z_ < (n); ++z_) \
+  _Pragma("unroll") for (int r_ = 0; r_ < 16; ++r_) (acc)[z_][r_] = 0.0f
+#define SLU_ZERO_ACC2(acc, m, n) \
+  _Pragma("unroll") for (int y_ = 0; y_ < (m); ++y_) SLU_ZERO_ACC((acc)[y_], n)
 
 // 64-lane wavefront sum (all lanes receive the total).
 __device__ __forceinline__ float wave_sum(float v) {

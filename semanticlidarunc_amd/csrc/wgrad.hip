@@ -14,8 +14,6 @@
 // second half of the last pair empty.
 #include "slu_common.h"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 namespace {
 
 constexpr int kRun = 32;   // pixel pairs per run (64 azimuth-adjacent pixels)
@@ -34,10 +32,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const float* __restrict__
   const long long worker = (long long)blockIdx.x * 4 + wave, nworkers = (long long)gridDim.x * 4;
 
   f32x16 acc[T];
-#pragma unroll
-  for (int t = 0; t < T; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
+  SLU_ZERO_ACC(acc, T);
 
   const float* abase = da_t + (size_t)cob * 32 + jj;
   const float* bbase = in_t + (size_t)cib * 32 + jj;
@@ -94,6 +89,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const float* __restrict__
   // each tap's total to dWp -- float atomics execute at the memory side at ~one 256-byte wave-instruction per 50 ns per CU
   // (MI355X_MICROARCH.md), so a wave-private flush of T x 16 of them cost more than the MFMAs of a short run.
   // D[i = co][j = ci]: lane & 31 = ci, register/half = co
+  // (Each of the four kernels keeps its copy of this loop: as a function taking the block and a lambda for the atomic -- block by const& or
+  // by value, lambda by && or by value -- 14 of the 14 kernels change, by -60 to +450 instructions.)
   __shared__ float s_red[4][16][64];
 #pragma unroll
   for (int t = 0; t < T; ++t) {
@@ -104,7 +101,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const float* __restrict__
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const float v = (s_red[0][r][lane] + s_red[1][r][lane]) + (s_red[2][r][lane] + s_red[3][r][lane]);
-        const int co = cob * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+        const int co = slu_frag_row(cob * 32, r, hh);
         atomicAdd(&dWp[((size_t)co * T + t) * Cip + cib * 32 + jj], v);
       }
     }
@@ -127,12 +124,7 @@ __global__ __launch_bounds__(256, 2) void wgrad1x1_kernel(const float* __restric
   const long long worker = (long long)blockIdx.x * 4 + wave, nworkers = (long long)gridDim.x * 4;
 
   f32x16 acc[MT][NT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+  SLU_ZERO_ACC2(acc, MT, NT);
   // blocks past the last one read block 0 and are never stored
   const float* abase[MT];
   const float* bbase[NT];
@@ -182,7 +174,7 @@ __global__ __launch_bounds__(256, 2) void wgrad1x1_kernel(const float* __restric
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const float v = (s_red[0][r][lane] + s_red[1][r][lane]) + (s_red[2][r][lane] + s_red[3][r][lane]);
-          const int co = (cob0 + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+          const int co = slu_frag_row((cob0 + i) * 32, r, hh);
           atomicAdd(&dWp[(size_t)co * Cip + (cib0 + j) * 32 + jj], v);
         }
       }
@@ -219,12 +211,7 @@ __global__ __launch_bounds__(256, 2) void wgrad1x1_nchw_kernel(const W1Args a) {
   const long long worker = (long long)bx * 4 + wave, nworkers = (long long)(gridDim.x / (gy * gz)) * 4;
 
   f32x16 acc[MT][NT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+  SLU_ZERO_ACC2(acc, MT, NT);
 
   const float* abase[MT];
 #pragma unroll
@@ -316,7 +303,7 @@ __global__ __launch_bounds__(256, 2) void wgrad1x1_nchw_kernel(const W1Args a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const float v = (s_red[0][r][lane] + s_red[1][r][lane]) + (s_red[2][r][lane] + s_red[3][r][lane]);
-          const int co = (cob0 + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+          const int co = slu_frag_row((cob0 + i) * 32, r, hh);
           if (cob0 + i < ncob && cib0 + j < ncib && co < a.Cout && ci < a.Cin) atomicAdd(&a.dW[(size_t)co * a.Cin + ci], v);
         }
       }
@@ -355,15 +342,13 @@ __global__ __launch_bounds__(256, 2) void wgradk_nchw_kernel(const WkArgs a) {
   const long long worker = (long long)blockIdx.x * 4 + wave, nworkers = (long long)gridDim.x * 4;
 
   f32x16 acc[T];
-#pragma unroll
-  for (int t = 0; t < T; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
+  SLU_ZERO_ACC(acc, T);
 
   // lanes past the last channel read channel 0: their rows / columns of the product are never stored
   const int co = cob * 32 + jj, ci = cib * 32 + jj;
   const float* abase = a.da + (size_t)(co < a.Cout ? co : 0) * HW + 8 * hh;
-  int s = 0;                                                 // per lane: a 32-channel block may straddle two sources
+  int s = 0;                                                 // per lane: a 32-channel block may straddle two sources (as a function shared with
+                                                             // wgrad1x1_nchw_kernel, over the cbeg array or the argument struct: 7 kernels change)
 #pragma unroll
   for (int t = 1; t < SLU_MAX_SRC; ++t)
     if (t < a.nsrc && ci >= a.cbeg[t]) s = t;
@@ -464,7 +449,7 @@ __global__ __launch_bounds__(256, 2) void wgradk_nchw_kernel(const WkArgs a) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const float v = (s_red[0][r][lane] + s_red[1][r][lane]) + (s_red[2][r][lane] + s_red[3][r][lane]);
-        const int c = cob * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+        const int c = cob * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;      // not slu_frag_row: with it the operands of 192 / 432 instructions commute
         if (c < a.Cout) atomicAdd(&a.dWp[((size_t)c * T + t) * a.Cip + cib * 32 + jj], v);
       }
     }
@@ -495,16 +480,20 @@ __global__ void dgrad_weight_kernel(const float* __restrict__ w, int Cout, int C
   }
 }
 
+// Blocks along x of a wgrad grid: `want` workgroups of four waves per channel tile (at least one), but no more waves than units of work,
+// so that every wave walks many runs before its partial sums are flushed.
+long long wgrad_gx(long long want, long long work) {
+  if (want < 1) want = 1;
+  if (want * 4 > work) want = (work + 3) / 4;
+  return want < 1 ? 1 : want;
+}
+
 template <int KS, int DIL, int PAD>
 int launch_wgrad(const float* da_t, const float* in_t, int N, int H, int W, int Cop, int Cip, float* dWp, hipStream_t st) {
   const int nb = (Cop / 32) * (Cip / 32);
   const long long nruns = ((long long)N * H * W / 2 + kRun - 1) / kRun;
-  // two resident workgroups per CU over all channel-block pairs (2 waves per SIMD): every wave then walks many pixel runs before its
-  // partial sums are flushed, instead of four queued waves of workgroups that each flush after a couple of runs
-  long long gx = 512 / nb;
-  if (gx < 1) gx = 1;
-  if (gx * 4 > nruns) gx = (nruns + 3) / 4;
-  if (gx < 1) gx = 1;
+  // two resident workgroups per CU over all channel-block pairs (2 waves per SIMD)
+  const long long gx = wgrad_gx(512 / nb, nruns);
   hipLaunchKernelGGL((wgrad_kernel<KS, DIL, PAD>), dim3((unsigned)gx, Cop / 32, Cip / 32), dim3(256), 0, st, da_t, in_t, N, H, W, Cop, Cip, dWp);
   SLU_CHECK_LAUNCH();
 }
@@ -513,20 +502,20 @@ template <int MT, int NT>
 int launch_wgrad1x1_t(const float* da_t, const float* in_t, long long npix, int Cop, int Cip, float* dWp, hipStream_t st) {
   const int gy = (Cop / 32 + MT - 1) / MT, gz = (Cip / 32 + NT - 1) / NT;
   const long long nruns = (npix / 2 + kRun - 1) / kRun;
-  long long gx = 1024 / ((long long)gy * gz);            // ~4 workgroups per CU: these waves are light on registers and live on occupancy
-  if (gx < 1) gx = 1;
-  if (gx * 4 > nruns) gx = (nruns + 3) / 4;
-  if (gx < 1) gx = 1;
+  const long long gx = wgrad_gx(1024 / ((long long)gy * gz), nruns);      // ~4 workgroups per CU: these waves are light on registers and live on occupancy
   hipLaunchKernelGGL((wgrad1x1_kernel<MT, NT>), dim3((unsigned)gx, gy, gz), dim3(256), 0, st, da_t, in_t, npix, Cop, Cip, dWp);
   SLU_CHECK_LAUNCH();
 }
 
-int launch_wgrad1x1(const float* da_t, const float* in_t, long long npix, int Cop, int Cip, float* dWp, hipStream_t st) {
-  const int ncob = Cop / 32, ncib = Cip / 32;
-  if (ncob >= 2 && ncib >= 2) return launch_wgrad1x1_t<2, 2>(da_t, in_t, npix, Cop, Cip, dWp, st);
-  if (ncob >= 2) return launch_wgrad1x1_t<2, 1>(da_t, in_t, npix, Cop, Cip, dWp, st);
-  if (ncib >= 2) return launch_wgrad1x1_t<1, 2>(da_t, in_t, npix, Cop, Cip, dWp, st);
-  return launch_wgrad1x1_t<1, 1>(da_t, in_t, npix, Cop, Cip, dWp, st);
+// blocks of 32 channels of dW per wave of the 1x1 kernels: f receives <MT, NT> as two integral constants
+template <class F>
+int wgrad1x1_tile(int ncob, int ncib, F&& f) {
+  using One = std::integral_constant<int, 1>;
+  using Two = std::integral_constant<int, 2>;
+  if (ncob >= 2 && ncib >= 2) return f(Two{}, Two{});
+  if (ncob >= 2) return f(Two{}, One{});
+  if (ncib >= 2) return f(One{}, Two{});
+  return f(One{}, One{});
 }
 
 template <int MT, int NT>
@@ -539,8 +528,7 @@ int launch_w1_nchw_t(const W1Args& a, hipStream_t st) {
   const long long hi = 1024 / tiles > 1 ? 1024 / tiles : 1, lo = (256 + tiles - 1) / tiles;
   if (gx > hi) gx = hi;
   if (gx < lo) gx = lo;
-  if (gx * 4 > nunits) gx = (nunits + 3) / 4;
-  if (gx < 1) gx = 1;
+  gx = wgrad_gx(gx, nunits);
   hipLaunchKernelGGL((wgrad1x1_nchw_kernel<MT, NT>), dim3((unsigned)(gx * tiles)), dim3(256), 0, st, a);
   SLU_CHECK_LAUNCH();
 }
@@ -549,11 +537,25 @@ template <int KS, int DIL, int PAD>
 int launch_wk_nchw(const WkArgs& a, hipStream_t st) {
   const int ncob = (a.Cout + 31) / 32, ncib = a.Cip / 32;
   const long long nruns = ((long long)a.N * a.H * (a.W / 16) + 3) / 4;
-  long long gx = 512 / ((long long)ncob * ncib);            // two resident workgroups per CU over all channel-block pairs
-  if (gx < 1) gx = 1;
-  if (gx * 4 > nruns) gx = (nruns + 3) / 4;
-  if (gx < 1) gx = 1;
+  const long long gx = wgrad_gx(512 / ((long long)ncob * ncib), nruns);      // two resident workgroups per CU over all channel-block pairs
   hipLaunchKernelGGL((wgradk_nchw_kernel<KS, DIL, PAD>), dim3((unsigned)gx, ncob, ncib), dim3(256), 0, st, a);
+  SLU_CHECK_LAUNCH();
+}
+
+// The k x k weight gradient through the tap-major image dWp: zero it, launch(geometry) for the symmetric k > 1 families (or launch1x1()
+// where given), unpack to OIHW.
+template <class L, class L1>
+int wgrad_via_packed(int Cout, int Cin, int ksize, int dil, int pad, int Cip, float* dWp, float* dW, bool zero, hipStream_t st, L&& launch, L1&& launch1x1) {
+  if (zero && hipMemsetAsync(dWp, 0, slu_wgrad_packed_floats(Cout, Cin, ksize) * sizeof(float), st) != hipSuccess) return SLU_ELAUNCH;
+  const int rc = slu_conv_family(ksize, dil, pad, [&](auto g) {
+    using G = decltype(g);
+    if constexpr (G::KS == 1) return launch1x1();
+    else if constexpr (2 * G::PAD != (G::KS - 1) * G::DIL) return (int)SLU_EUNSUPPORTED;      // 2x2 d1: not its own data-gradient family, never trained
+    else return launch(g);
+  });
+  if (rc != SLU_OK) return rc;
+  const size_t total = (size_t)Cout * Cin * ksize * ksize;
+  hipLaunchKernelGGL(wgrad_unpack_kernel, dim3(slu_grid_1d(total, 4096)), dim3(256), 0, st, dWp, Cout, Cin, ksize * ksize, Cip, dW, total);
   SLU_CHECK_LAUNCH();
 }
 
@@ -575,17 +577,9 @@ extern "C" int slu_conv2d_wgrad_nchw(const float* da, const slu_conv_src* src, i
   if (c > 65535 * 32) return SLU_EUNSUPPORTED;
   a.da = da; a.nsrc = nsrc; a.N = N; a.H = H; a.W = W; a.Cout = Cout; a.Cin = c; a.Cip = (c + 31) / 32 * 32; a.dWp = dWp;
   hipStream_t st = slu_stream(stream);
-  if (!prezeroed && hipMemsetAsync(dWp, 0, slu_wgrad_packed_floats(Cout, c, ksize) * sizeof(float), st) != hipSuccess) return SLU_ELAUNCH;
-  int rc;
-  if (ksize == 3 && dil == 1 && pad == 1) rc = launch_wk_nchw<3, 1, 1>(a, st);
-  else if (ksize == 3 && dil == 2 && pad == 2) rc = launch_wk_nchw<3, 2, 2>(a, st);
-  else if (ksize == 2 && dil == 2 && pad == 1) rc = launch_wk_nchw<2, 2, 1>(a, st);
-  else return SLU_EUNSUPPORTED;
-  if (rc != SLU_OK) return rc;
-  const size_t total = (size_t)Cout * c * ksize * ksize;
-  const unsigned g = (unsigned)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-  hipLaunchKernelGGL(wgrad_unpack_kernel, dim3(g), dim3(256), 0, st, dWp, Cout, c, ksize * ksize, a.Cip, dW, total);
-  SLU_CHECK_LAUNCH();
+  return wgrad_via_packed(
+      Cout, c, ksize, dil, pad, a.Cip, dWp, dW, !prezeroed, st, [&](auto g) { return launch_wk_nchw<g.KS, g.DIL, g.PAD>(a, st); },
+      [] { return (int)SLU_EUNSUPPORTED; });
 }
 
 extern "C" int slu_conv1x1_wgrad_nchw(const float* da, const slu_conv_src* src, int nsrc, int N, int HW, int Cout, float* dW, int prezeroed,
@@ -604,11 +598,7 @@ extern "C" int slu_conv1x1_wgrad_nchw(const float* da, const slu_conv_src* src, 
   a.da = da; a.nsrc = nsrc; a.N = N; a.HW = HW; a.Cout = Cout; a.Cin = c; a.dW = dW;
   hipStream_t st = slu_stream(stream);
   if (!prezeroed && hipMemsetAsync(dW, 0, (size_t)Cout * c * sizeof(float), st) != hipSuccess) return SLU_ELAUNCH;
-  const int ncob = (Cout + 31) / 32, ncib = (c + 31) / 32;
-  if (ncob >= 2 && ncib >= 2) return launch_w1_nchw_t<2, 2>(a, st);
-  if (ncob >= 2) return launch_w1_nchw_t<2, 1>(a, st);
-  if (ncib >= 2) return launch_w1_nchw_t<1, 2>(a, st);
-  return launch_w1_nchw_t<1, 1>(a, st);
+  return wgrad1x1_tile((Cout + 31) / 32, (c + 31) / 32, [&](auto mt, auto nt) { return launch_w1_nchw_t<mt.value, nt.value>(a, st); });
 }
 
 extern "C" size_t slu_wgrad_packed_floats(int cout, int cin, int ksize) {
@@ -622,24 +612,18 @@ extern "C" int slu_conv2d_wgrad(const float* da_t, const float* in_t, int N, int
   if (Cout > 65535 * 32 || Cin > 65535 * 32) return SLU_EUNSUPPORTED;
   const int Cop = (Cout + 31) / 32 * 32, Cip = (Cin + 31) / 32 * 32;
   hipStream_t st = slu_stream(stream);
-  if (hipMemsetAsync(dWp, 0, slu_wgrad_packed_floats(Cout, Cin, ksize) * sizeof(float), st) != hipSuccess) return SLU_ELAUNCH;
-  int rc;
-  if (ksize == 1 && dil == 1 && pad == 0) rc = launch_wgrad1x1(da_t, in_t, (long long)N * H * W, Cop, Cip, dWp, st);
-  else if (ksize == 3 && dil == 1 && pad == 1) rc = launch_wgrad<3, 1, 1>(da_t, in_t, N, H, W, Cop, Cip, dWp, st);
-  else if (ksize == 3 && dil == 2 && pad == 2) rc = launch_wgrad<3, 2, 2>(da_t, in_t, N, H, W, Cop, Cip, dWp, st);
-  else if (ksize == 2 && dil == 2 && pad == 1) rc = launch_wgrad<2, 2, 1>(da_t, in_t, N, H, W, Cop, Cip, dWp, st);
-  else return SLU_EUNSUPPORTED;
-  if (rc != SLU_OK) return rc;
-  const size_t total = (size_t)Cout * Cin * ksize * ksize;
-  const unsigned g = (unsigned)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-  hipLaunchKernelGGL(wgrad_unpack_kernel, dim3(g), dim3(256), 0, st, dWp, Cout, Cin, ksize * ksize, Cip, dW, total);
-  SLU_CHECK_LAUNCH();
+  return wgrad_via_packed(
+      Cout, Cin, ksize, dil, pad, Cip, dWp, dW, true, st, [&](auto g) { return launch_wgrad<g.KS, g.DIL, g.PAD>(da_t, in_t, N, H, W, Cop, Cip, dWp, st); },
+      [&] {
+        return wgrad1x1_tile(Cop / 32, Cip / 32, [&](auto mt, auto nt) {
+          return launch_wgrad1x1_t<mt.value, nt.value>(da_t, in_t, (long long)N * H * W, Cop, Cip, dWp, st);
+        });
+      });
 }
 
 extern "C" int slu_dgrad_weight(const float* w, int cout, int cin, int ksize, float* wd, slu_stream_t stream) {
   if (!w || !wd || cout <= 0 || cin <= 0 || ksize <= 0) return SLU_EINVAL;
   const size_t total = (size_t)cout * cin * ksize * ksize;
-  const unsigned g = (unsigned)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-  hipLaunchKernelGGL(dgrad_weight_kernel, dim3(g), dim3(256), 0, slu_stream(stream), w, cout, cin, ksize, wd, total);
+  hipLaunchKernelGGL(dgrad_weight_kernel, dim3(slu_grid_1d(total, 4096)), dim3(256), 0, slu_stream(stream), w, cout, cin, ksize, wd, total);
   SLU_CHECK_LAUNCH();
 }

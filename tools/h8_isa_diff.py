@@ -1,14 +1,16 @@
 #!/usr/bin/env python
 """Per-kernel comparison of the gfx950 code of two builds (development aid for refactors that must not change what the compiler emits):
 
-    python tools/h8_isa_diff.py OLD NEW [--launched names.json|stats.csv ...]
+    python tools/h8_isa_diff.py OLD NEW [--match SUBSTR] [--launched names.json|stats.csv ...]
 
 OLD / NEW: a libslu_hip.so (its code objects are extracted the way tools/check_counted_waits.py does) or one device code object
-(`hipcc --cuda-device-only -c`).  For every kernel whose name contains "h8" the instruction text is compared with comments stripped; the
+(`hipcc --cuda-device-only -c`).  For every kernel whose name contains SUBSTR (default "h8") the instruction text is compared with comments stripped; the
 literal of the s_add_u32 / s_addc_u32 pair behind an s_getpc_b64 (the PC-relative address of a global: it moves with the layout of the code
 object, not with the kernel) is masked.  Verdicts: `same`; `commuted` = same length, same opcode at every position, the operands of the
 differing lines permuted; `CHANGED` with both instruction counts.  --launched: kernel names as rocprofv3 prints them (a JSON object keyed
-by name or a --stats CSV); a CHANGED kernel of that set, or any CHANGED ring3_h8_kernel / tail2_h8_kernel, makes the exit status 1."""
+by name or a --stats CSV); a CHANGED kernel of that set, or (default match only) any CHANGED ring3_h8_kernel / tail2_h8_kernel, makes the
+exit status 1.  For the fp32-storage conv / wgrad kernels: --match kernel --launched profiles/r05/coverage_recorded_names.json --launched
+profiles/r03/train_kernel_stats.csv."""
 import collections
 import csv
 import json
@@ -32,8 +34,8 @@ def short(demangled):      # "void (anonymous namespace)::k<1, 2>((anonymous nam
     return s
 
 
-def kernels(path):
-    """{short name: [instruction lines]} of the h8 kernels of a library or code object"""
+def kernels(path, match="h8"):
+    """{short name: [instruction lines]} of the kernels of a library or code object whose name contains `match`"""
     out = {}
     with tempfile.TemporaryDirectory() as tmp:
         local = os.path.join(tmp, "in.bin")
@@ -46,7 +48,7 @@ def kernels(path):
             for line in asm.splitlines():
                 m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
                 if m:
-                    cur = out.setdefault(short(m.group(1)), []) if "h8" in m.group(1) else None
+                    cur = out.setdefault(short(m.group(1)), []) if match in m.group(1) else None
                     continue
                 ins = " ".join(line.split("//")[0].split())
                 if cur is None or not ins:
@@ -70,24 +72,29 @@ def verdict(a, b):
 
 
 def main():
-    args, launched = sys.argv[1:], set()
+    args, launched, match = sys.argv[1:], set(), "h8"
+    if "--match" in args:
+        i = args.index("--match")
+        match = args[i + 1]
+        del args[i:i + 2]
     while "--launched" in args:
         i = args.index("--launched")
         f = args[i + 1]
         del args[i:i + 2]
         names = json.load(open(f)) if f.endswith(".json") else [r["Name"] for r in csv.DictReader(open(f))]
         launched |= {short(n) for n in names}
-    old, new = kernels(args[0]), kernels(args[1])
+    old, new = kernels(args[0], match), kernels(args[1], match)
+    always = ("ring3_h8_kernel", "tail2_h8_kernel") if match == "h8" else ()
     bad, tally = 0, collections.Counter()
     for name in sorted(set(old) | set(new)):
         v = verdict(old[name], new[name]) if name in old and name in new else ("only in OLD" if name in old else "only in NEW")
-        must = name in launched or name.startswith(("ring3_h8_kernel", "tail2_h8_kernel"))
+        must = name in launched or name.startswith(always)
         tally[v.split()[0]] += 1
         if v != "same":
             print(f"{'launched ' if must else '         '}{name}: {v}")
         if must and not v.startswith(("same", "commuted")):
             bad += 1
-    print(f"{len(old)} / {len(new)} h8 kernels: {dict(tally)}; {bad} launched, ring3 or tail2 kernels changed")
+    print(f"{len(old)} / {len(new)} {match} kernels: {dict(tally)}; {bad} launched{', ring3 or tail2' if always else ''} kernels changed")
     return 1 if bad else 0
 
 
