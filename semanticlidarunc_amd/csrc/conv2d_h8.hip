@@ -1070,40 +1070,63 @@ __global__ __launch_bounds__(256) void h8_to_nchw_kernel(const uint4* __restrict
   }
 }
 
-// AvgPool2d(3, stride 2, pad 1, count_include_pad) of x * scale[n, c]; x may hold `in_batch` images shared by all n
+// AvgPool2d(3, stride 2, pad 1, count_include_pad) of x * scale[n, c]; x may hold `in_batch` images shared by all n.
+// One thread per output record.  Grid: x = (block g, 256 output columns), y = output row, z = image, so the only division of a thread
+// is the uniform blockIdx.x / tiles; y and z stride where a launch has more rows or images than a grid dimension holds.  Each output is
+// the parent form's arithmetic: acc = +0, the nine taps added rows -1 .. 1 outside and columns -1 .. 1 inside, a tap outside the image
+// adding +0 (which leaves acc as it is), then acc * s / 9.  An output whose nine taps all lie inside the image takes the path without
+// selects; a wave of such outputs -- all but the first of a row, and the rows 0 and (H odd) OH - 1 -- never runs the other one.
 __global__ __launch_bounds__(256) void avgpool3s2_h8_kernel(const uint4* __restrict__ x, const float* __restrict__ scale, uint4* __restrict__ y,
-                                                            int N, int G, int H, int W, int OH, int OW, int in_batch) {
-  const size_t total = (size_t)N * G * OH * OW;
-  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-    const int ox = (int)(e % OW);
-    size_t r = e / OW;
-    const int oy = (int)(r % OH);
-    r /= OH;
-    const int g = (int)(r % G);
-    const size_t n = r / G;
-    const size_t ni = in_batch ? n % in_batch : n;
-    const uint4* p = x + (ni * G + g) * (size_t)H * W;
-    float acc[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) acc[k] = 0.0f;
-#pragma unroll
-    for (int i = -1; i <= 1; ++i) {
-      const int iy = 2 * oy + i;
-#pragma unroll
-      for (int j = -1; j <= 1; ++j) {
-        const int ix = 2 * ox + j;
-        const bool ok = iy >= 0 && iy < H && ix >= 0 && ix < W;
-        const half8 h = __builtin_bit_cast(half8, p[ok ? (size_t)iy * W + ix : 0]);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) acc[k] += ok ? (float)h[k] : 0.0f;
-      }
-    }
+                                                            int N, int G, int H, int W, int OH, int OW, int in_batch, int tiles) {
+  const int g = (int)(blockIdx.x / (unsigned)tiles);
+  const int ox = (int)(blockIdx.x - (unsigned)g * (unsigned)tiles) * 256 + (int)threadIdx.x;
+  if (ox >= OW) return;
+  const int ix = 2 * ox - 1;
+  const bool xin = ox >= 1 && ix + 2 < W;
+  for (int n = (int)blockIdx.z; n < N; n += (int)gridDim.z) {
+    const size_t ni = in_batch ? (size_t)(n % in_batch) : (size_t)n;
+    const uint4* img = x + (ni * G + g) * (size_t)H * W;
     float s[8];
+    if (scale) {                                         // uniform: the eight multipliers of (n, g) as two 16-byte loads
+      const float4 s0 = *reinterpret_cast<const float4*>(scale + ((size_t)n * G + g) * 8);
+      const float4 s1 = *reinterpret_cast<const float4*>(scale + ((size_t)n * G + g) * 8 + 4);
+      s[0] = s0.x; s[1] = s0.y; s[2] = s0.z; s[3] = s0.w;
+      s[4] = s1.x; s[5] = s1.y; s[6] = s1.z; s[7] = s1.w;
+    } else {
 #pragma unroll
-    for (int k = 0; k < 8; ++k) s[k] = scale ? scale[(n * G + g) * 8 + k] : 1.0f;
+      for (int k = 0; k < 8; ++k) s[k] = 1.0f;
+    }
+    for (int oy = (int)blockIdx.y; oy < OH; oy += (int)gridDim.y) {
+      const int iy = 2 * oy - 1;
+      float acc[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) acc[k] = acc[k] * s[k] / 9.0f;
-    y[e] = make_uint4(pack2(acc[0], acc[1]), pack2(acc[2], acc[3]), pack2(acc[4], acc[5]), pack2(acc[6], acc[7]));
+      for (int k = 0; k < 8; ++k) acc[k] = 0.0f;
+      if (xin && oy >= 1 && iy + 2 < H) {
+        const uint4* p = img + (size_t)iy * W + ix;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+          for (int j = 0; j < 3; ++j) {
+            const half8 h = __builtin_bit_cast(half8, p[(size_t)i * W + j]);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) acc[k] += (float)h[k];
+          }
+      } else {
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+          for (int j = 0; j < 3; ++j) {
+            const bool ok = iy + i >= 0 && iy + i < H && ix + j >= 0 && ix + j < W;
+            const half8 h = __builtin_bit_cast(half8, img[ok ? (size_t)(iy + i) * W + (ix + j) : 0]);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) acc[k] += ok ? (float)h[k] : 0.0f;
+          }
+      }
+#pragma unroll
+      for (int k = 0; k < 8; ++k) acc[k] = acc[k] * s[k] / 9.0f;
+      y[(((size_t)n * G + g) * OH + oy) * OW + ox] =
+          make_uint4(pack2(acc[0], acc[1]), pack2(acc[2], acc[3]), pack2(acc[4], acc[5]), pack2(acc[6], acc[7]));
+    }
   }
 }
 
@@ -1778,11 +1801,13 @@ extern "C" int slu_h8_to_nchw(const void* x, float* y, int N, int C, int H, int 
 }
 
 extern "C" int slu_avgpool3s2_h8(const void* x, const float* scale, void* y, int N, int in_batch, int G, int H, int W, slu_stream_t stream) {
-  if (!x || !y || N <= 0 || in_batch < 0 || G <= 0 || H <= 0 || W <= 0 || (((uintptr_t)x | (uintptr_t)y) & 15)) return SLU_EINVAL;
+  if (!x || !y || N <= 0 || in_batch < 0 || G <= 0 || H <= 0 || W <= 0 || (((uintptr_t)x | (uintptr_t)y | (uintptr_t)scale) & 15)) return SLU_EINVAL;
   const int OH = (H + 1) / 2, OW = (W + 1) / 2;
-  const size_t total = (size_t)N * G * OH * OW;
-  hipLaunchKernelGGL(avgpool3s2_h8_kernel, dim3(grid_for(total)), dim3(256), 0, slu_stream(stream), reinterpret_cast<const uint4*>(x), scale,
-                     reinterpret_cast<uint4*>(y), N, G, H, W, OH, OW, in_batch);
+  const int tiles = (OW + 255) / 256;                    // 256 output columns per workgroup
+  if ((long long)tiles * G > 0x7fffffffLL) return SLU_EUNSUPPORTED;
+  const dim3 grid((unsigned)(tiles * G), (unsigned)(OH < 65535 ? OH : 65535), (unsigned)(N < 65535 ? N : 65535));
+  hipLaunchKernelGGL(avgpool3s2_h8_kernel, grid, dim3(256), 0, slu_stream(stream), reinterpret_cast<const uint4*>(x), scale,
+                     reinterpret_cast<uint4*>(y), N, G, H, W, OH, OW, in_batch, tiles);
   SLU_CHECK_LAUNCH();
 }
 

@@ -391,7 +391,7 @@ def head_mc_h8(x: torch.Tensor, wpack: torch.Tensor, bias: Optional[torch.Tensor
     nbytes = n * h * w * (2.0 * 8 * g + 4.0 * classes) + 2.0 * classes * 8 * g
     # what the fused kernel must move: the decoder output of every pass in, p_bar / H / MI / argmax of every scan out
     min_bytes = n * h * w * 2.0 * 8 * g + batch * h * w * (4.0 * classes + 16.0) + 2.0 * classes * 8 * g
-    ops.TIMING.append((f"head_mc_h8_kernel<{g // 2}>", flops, nbytes, e0, e1, min_bytes))
+    ops.TIMING.append((f"head_mc_h8_kernel<{g // 2}, {(classes + 7) // 8}>", flops, nbytes, e0, e1, min_bytes))
     ops.TIMING_TAGS.append(f"N{n} {8 * g}->{classes} k1 head + MC reduce T={passes} {h}x{w}")
     return p_bar, hn, mi, preds
 
