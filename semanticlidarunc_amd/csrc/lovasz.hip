@@ -16,6 +16,12 @@
 // After the sort one kernel scans the fg bits, forms J_k in fp32 exactly like the reference
 // (1 - inter/union, both exact integers in fp32), accumulates loss_c in fp64 and scatters
 // d loss / d p_c,i = (J_k - J_{k-1}) * (fg ? -1 : +1) back to pixel order (0 where err == 0).
+// The radix passes are stable, so equal errors keep their pixel order: the gradient is the same run to run, and over a group
+// of equal errors it sums to J(after the group) - J(before the group) whatever the order inside the group.
+//
+// Unlike the reference, keygen_kernel clamps err to [0, 1] (the key transform needs that range) and fminf/fmaxf map a NaN
+// error to 0: a NaN or out-of-range probability gives a finite loss and a zero gradient at that pixel where the reference
+// would propagate it.
 //
 // HBM-bound: ~ 4 passes x (8 B read for the histogram + 8 B read + 8 B written by the scatter) per key.
 #include "slu_common.h"

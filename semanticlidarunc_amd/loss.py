@@ -82,8 +82,12 @@ class SalsaNextLossFn(torch.autograd.Function):
         nll = (nll_sum / n).to(torch.float32)
         ctx.save_for_backward(probs, lab, grad_ls)
         ctx.cfg = (float(w_nll), float(w_ls), n)
-        total = w_nll * nll + w_ls * ls
-        return total.reshape(()), nll.reshape(()), ls.reshape(())
+        total = (w_nll * nll + w_ls * ls).reshape(())
+        nll, ls = nll.reshape(()), ls.reshape(())
+        # the two terms are returned for logging only: the backward below is that of `total`, so differentiating through
+        # either of them raises instead of silently returning zeros
+        ctx.mark_non_differentiable(nll, ls)
+        return total, nll, ls
 
     @staticmethod
     def backward(ctx, g, _g_nll, _g_ls):
@@ -94,5 +98,6 @@ class SalsaNextLossFn(torch.autograd.Function):
 
 
 def salsanext_loss(logits, labels, w_nll: float = 1.0, w_ls: float = 1.0, lovasz_ignore=0):
-    """(loss, nll, lovasz) of the reference's "SalsaNext" loss branch, differentiable w.r.t. logits."""
+    """(loss, nll, lovasz) of the reference's "SalsaNext" loss branch; `loss` is differentiable w.r.t. logits, the two terms are
+    values only (marked non-differentiable)."""
     return SalsaNextLossFn.apply(logits, labels, w_nll, w_ls, lovasz_ignore)

@@ -2,8 +2,11 @@
 ``forward(outputs, labels, model_act)`` contract, ``ValueError`` on an unknown ``model_act``.
 
 The arithmetic is the batched device radix sort + Jaccard scan of ``csrc/lovasz.hip``; the value equals the
-reference's to fp32 rounding and the gradient w.r.t. the probabilities is exact wherever the sorted errors
-are distinct (ties make the reference's own sub-gradient order-dependent).
+reference's to fp32 rounding.  The gradient w.r.t. the probabilities is a sub-gradient: over every group of
+pixels with equal error it sums to the Jaccard step across the group, J(after) - J(before), to fp32 rounding,
+which for distinct errors is the reference's gradient element by element.  Inside a group the split follows
+the pixel order (the sort is stable), so it is the same run to run; the reference's own split there depends
+on its sort.  Pixels with zero error, ignored pixels and classes that are not summed get exactly 0.
 """
 from __future__ import annotations
 
