@@ -8,8 +8,16 @@ one of the kernels' untracked (inline-asm) register loads before a vmcnt wait ha
 vector-memory operations are tracked in issue order and `vmcnt(N)` retires all but the N youngest, so a compiler-inserted move or spill of such
 a register behind a counted wait with N > 0 is caught too.  The scan is linear over the disassembly (not branch-aware).
 
-    python tools/check_counted_waits.py [path/to/libslu_hip.so]
+    python tools/check_counted_waits.py [path/to/libslu_hip.so] [--kernels REGEX]
+
+--kernels REGEX scans the kernels whose (mangled) name matches REGEX as well.  gemm1x1_h8_kernel (conv2d_h8.hip; not its A/B form
+gemm1x1_h8_kernel_v1) has rules of its own: its residual epilogue must not wait in full, so every `vmcnt(0)` has to be, by what follows it
+within three instructions, one of the set-up (a `ds_write` of an epilogue constant: the tile loops fill LDS by DMA alone), the chunk wait of a
+ring of depth 2 (D = 2: `vmcnt(0)`, `lgkmcnt(0)`, `s_barrier`) or the exit's (`s_endpgm`, or the branch to it from the first of the kernel's
+two tile loops); it holds no FLAT operation (they count in lgkmcnt as well) and no scratch access; the untracked-load rule applies as above.
+The A/B form is listed and not judged.
 """
+import argparse
 import os
 import re
 import shutil
@@ -18,9 +26,13 @@ import sys
 import tempfile
 
 LLVM = "/opt/rocm/lib/llvm/bin"
-so = os.path.abspath(sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
-                                                                         "semanticlidarunc_amd", "libslu_hip.so"))
-KERNELS = re.compile(r"^(\S*(tail2_h8_kernel|ring3_h8_kernel)\S*)>?:$")
+ap = argparse.ArgumentParser()
+ap.add_argument("so", nargs="?", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "semanticlidarunc_amd", "libslu_hip.so"))
+ap.add_argument("--kernels", default=None, help="regular expression: scan these kernels too")
+args = ap.parse_args()
+so = os.path.abspath(args.so)
+EXTRA = re.compile(args.kernels) if args.kernels else None
+GEMM = re.compile(r"gemm1x1_h8_kernelILi(\d+)ELi(\d+)ELi(\d+)E")      # <MB, KC, D>; the _v1 form's mangled name continues with "_v1"
 bad = 0
 with tempfile.TemporaryDirectory() as tmp:
     local = os.path.join(tmp, "lib.so")
@@ -31,6 +43,7 @@ with tempfile.TemporaryDirectory() as tmp:
             continue
         asm = subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", os.path.join(tmp, f)], check=True, capture_output=True, text=True).stdout
         name, waits, nbar = None, [], 0
+        gemm, recent, unexplained, forbidden = None, [], [], 0      # the GEMM's rules
         vm_ops = []        # vector-memory operations issued so far in program order: the destination registers of an untracked register
                            # load, or an empty set for anything else that counts in vmcnt (stores, LDS-DMA, tracked loads, atomics)
         def pending_regs():
@@ -39,8 +52,22 @@ with tempfile.TemporaryDirectory() as tmp:
                 r |= regs
             return r
         def flush():
-            global bad
+            global bad, forbidden
             if name is None:
+                return
+            if "gemm1x1_h8_kernel_v1" in name:      # the A/B form keeps the full waits of its residual loads: reported, not judged
+                print(f"{name[:90]:90s} barriers {nbar:2d}  counted {sorted(set(w for w in waits if w > 0))}  vmcnt(0) x{sum(1 for w in waits if w == 0)}   (A/B form)")
+                return
+            if gemm:
+                for u in unexplained:
+                    if u is not None:      # never followed by a barrier or the end of the program
+                        forbidden += 1
+                        print(f"{name[:90]}: {u}   <-- a full wait that is neither the set-up's, a D = 2 chunk wait nor the exit's")
+                counted = sorted(set(w for w in waits if w > 0))
+                flag = "" if not forbidden else f"   <-- {forbidden} full wait(s) / FLAT / scratch operation(s) in the GEMM"
+                if flag:
+                    bad += 1
+                print(f"{name[:90]:90s} barriers {nbar:2d}  counted {counted}  vmcnt(0) x{sum(1 for w in waits if w == 0)}{flag}")
                 return
             inner = [w for w in waits]
             zeros = sum(1 for w in inner if w == 0)
@@ -56,12 +83,30 @@ with tempfile.TemporaryDirectory() as tmp:
             if m:
                 flush()
                 name = m.group(1) if ("tail2_h8_kernel" in m.group(1) or "ring3_h8_kernel" in m.group(1)) else None
+                if name is None and EXTRA and EXTRA.search(m.group(1)):
+                    name = m.group(1)
+                gemm = GEMM.search(name) if name and EXTRA else None
+                recent, unexplained, forbidden = [], [], 0
                 waits, nbar = [], 0
                 vm_ops.clear()
                 continue
             if name is None:
                 continue
             ins = line.split("//")[0]
+            if gemm and ins.strip():
+                op = ins.split()[0]
+                if op.startswith(("flat_", "scratch_")):
+                    forbidden += 1
+                    print(f"{name[:90]}: {ins.strip()[:80]}   <-- FLAT / scratch operation in the GEMM")
+                # a full wait stays "unexplained" until, within the next three instructions, a ds_write, an s_barrier (D = 2 only), s_endpgm
+                # or a branch follows
+                if op.startswith(("ds_write", "s_endpgm", "s_branch", "s_cbranch")) or (op == "s_barrier" and int(gemm.group(3)) == 2):
+                    for u in recent:
+                        unexplained[u[1]] = None
+                recent = [(n - 1, k) for n, k in recent if n > 1]
+                if re.search(r"s_waitcnt\s+vmcnt\(0\)", ins):
+                    unexplained.append(ins.strip())
+                    recent.append((3, len(unexplained) - 1))
             w = re.search(r"s_waitcnt\s+vmcnt\((\d+)\)", ins)
             if w:
                 n = int(w.group(1))

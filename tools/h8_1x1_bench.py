@@ -12,7 +12,10 @@ n = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 dev = torch.device("cuda:0")
 LAYERS = [([256, 256, 256], 256, 16, 512, True), ([256, 256, 256], 256, 8, 256, True), ([256, 256, 256], 256, 4, 128, True),
           ([128, 128, 128], 128, 32, 1024, True), ([128, 128, 128], 128, 16, 512, True), ([64], 128, 32, 1024, False), ([128], 256, 16, 512, False),
-          ([256], 256, 8, 256, False)]
+          ([256], 256, 8, 256, False),
+          # the residual layers again without their residual: the difference is what the residual costs the epilogue
+          ([256, 256, 256], 256, 16, 512, False), ([256, 256, 256], 256, 8, 256, False), ([256, 256, 256], 256, 4, 128, False),
+          ([128, 128, 128], 128, 32, 1024, False), ([128, 128, 128], 128, 16, 512, False)]
 for li, (parts, cout, H, W, res) in enumerate(LAYERS):
     g = torch.Generator(device=dev).manual_seed(li)
     srcs = [h8.H8Source(torch.randn(n, c // 8, H, W, 8, device=dev, generator=g).half()) for c in parts]
@@ -39,4 +42,4 @@ for li, (parts, cout, H, W, res) in enumerate(LAYERS):
     ms = sorted(ts)[2]
     by = n * H * W * 2.0 * (cin + cout * (2 if res else 1))
     fl = 2.0 * cin * cout * n * H * W
-    print(f"L{li} {parts}->{cout} {H}x{W}: {ms*1e3:8.1f} us  {by/ms/1e6:7.1f} GB/s(incl resid)  {fl/ms/1e9:7.1f} TF/s  {name}", flush=True)
+    print(f"L{li} {parts}->{cout} {H}x{W} {'+res' if res else '    '}: {ms*1e3:8.1f} us  (min {min(ts)*1e3:.1f} max {max(ts)*1e3:.1f})  {by/ms/1e6:7.1f} GB/s(incl resid)  {fl/ms/1e9:7.1f} TF/s  {name}", flush=True)

@@ -19,7 +19,8 @@ PREFIXES = ("v_exp_f32", "v_log_f32", "v_cndmask", "s_and_saveexec", "s_cbranch"
 def kernel_body(path, key):
     lines = open(path).read().split("\n")
     start = next(i for i, l in enumerate(lines) if re.match(r"^_Z\S*%s\S*:" % re.escape(key), l))
-    end = next(i for i in range(start, len(lines)) if lines[i].strip().startswith("s_endpgm"))
+    # up to the function's end label: a kernel may hold an early-exit s_endpgm, or two whole loops with one each (gemm1x1_h8_kernel)
+    end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end")) - 1
     return lines[start:end + 1]
 
 
