@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SLU_ABI_VERSION 33
+#define SLU_ABI_VERSION 34
 
 #define SLU_OK            0
 #define SLU_EINVAL       -1   /* null pointer / non-positive size / inconsistent descriptor   */
@@ -298,6 +298,18 @@ int slu_bilinear_upsample(const float* x, float* y, int N, int C, int H, int W, 
 int slu_groupnorm_fwd(const float* x, const float* gamma, const float* beta, int N, int C, int HW, int groups, float eps, int relu, float* mean,
                       float* rstd, float* y, slu_stream_t stream);
 int slu_spatial_softmax_gate(const float* x, const float* score, float* stats, float* out, int N, int C, int HW, slu_stream_t stream);
+/* the statistics launch of slu_groupnorm_fwd alone: mean / rstd fp32 [N*groups], the same numbers */
+int slu_groupnorm_stats(const float* x, int N, int C, int HW, int groups, float eps, float* mean, float* rstd, slu_stream_t stream);
+
+/* GroupNorm apply [+ ReLU] + 1x1 segmentation head + MC-dropout reduction in one pass, exact fp32 (semanticFCN_opt.py:286-296 +
+ * trainer.py:1143-1154): x fp32 [T*B][Cin][HW], pass-major (image t*B + b = pass t of scan b);
+ * v = (x - mean[n*groups + c/(Cin/groups)]) * rstd[..] * gamma[c] + beta[c] (mean / rstd from slu_groupnorm_stats, [T*B*groups] each; both NULL:
+ * v = x; gamma / beta [Cin] or NULL), max(v, 0) if relu; logits = w v + bias with w [C][Cin] row-major (the Conv2d weight as stored), bias [C] or
+ * NULL.  Outputs as slu_mc_reduce: p_bar fp32 [B][C][HW], h_norm / mi_norm fp32 [B][HW], preds int64 [B][HW].  1 <= C <= 32 (SLU_EINVAL
+ * otherwise); Cin <= 128 (SLU_EUNSUPPORTED above); any HW (16-byte accesses when HW % 4 == 0 and every base is 16-byte aligned). */
+int slu_head_mc_f32(const float* x, int T, int B, int Cin, int HW, const float* gn_mean, const float* gn_rstd, const float* gn_gamma,
+                    const float* gn_beta, int groups, int relu, const float* w, const float* bias, int C, float eps, float* p_bar, float* h_norm,
+                    float* mi_norm, int64_t* preds, slu_stream_t stream);
 
 /* ---- fp16 channel-blocked ("h8") inference path: BASELINE.json configs[2],[4] (half-precision storage, fp32 accumulate) -------
  * Activation layout: x[N][G = ceil(C/8)][H][W][8] fp16, pad channels = 0, base pointers 16-byte aligned.

@@ -314,6 +314,14 @@ extern "C" int slu_groupnorm_fwd(const float* x, const float* gamma, const float
   SLU_CHECK_LAUNCH();
 }
 
+extern "C" int slu_groupnorm_stats(const float* x, int N, int C, int HW, int groups, float eps, float* mean, float* rstd, slu_stream_t stream) {
+  if (!x || !mean || !rstd || N <= 0 || C <= 0 || HW <= 0 || groups <= 0 || C % groups || !(eps >= 0.0f)) return SLU_EINVAL;
+  if ((long long)N * groups > 0x7fffffffLL) return SLU_EUNSUPPORTED;
+  hipLaunchKernelGGL(groupnorm_stats_kernel, dim3((unsigned)(N * groups)), dim3(1024), 0, slu_stream(stream), x, (size_t)(C / groups) * HW, eps, mean,
+                     rstd);
+  SLU_CHECK_LAUNCH();
+}
+
 extern "C" int slu_spatial_softmax_gate(const float* x, const float* score, float* stats, float* out, int N, int C, int HW, slu_stream_t stream) {
   if (!x || !score || !stats || !out || N <= 0 || C <= 0 || HW <= 0) return SLU_EINVAL;
   hipStream_t st = slu_stream(stream);

@@ -222,7 +222,7 @@ class SemanticNetworkWithFPN(nn.Module):
             b = b + conv_b.detach() * a
         return conv_w.detach() * a.view(-1, 1, 1, 1), b
 
-    def _conv(self, name, conv: nn.Conv2d, bn, srcs, act="relu", resid=None, late=False, tail_first: int = 0):
+    def _conv(self, name, conv: nn.Conv2d, bn, srcs, act="relu", resid=None, late=False, tail_first: int = 0, n_out: Optional[int] = None):
         """tail_first = m > 0: the sources are given as (last m input channels, the rest) -- the packed weight's input channels are rotated
         to match (a channel prefix `cuse` is only honoured on the LAST source of a fused conv)."""
         def make():
@@ -233,7 +233,7 @@ class SemanticNetworkWithFPN(nn.Module):
         p = self._prep(name, make,
                        conv.weight, conv.bias, *(() if bn is None else (bn.weight, bn.bias, bn.running_mean, bn.running_var)))
         return ops.conv2d_fused(srcs, p.wpack, p.cout, p.k, p.dil, p.pad, bias=p.bias, resid=resid, precision=p.precision,
-                                act=act, act_after_resid=late)
+                                act=act, act_after_resid=late, n_out=n_out)
 
     def _conv_s2(self, name, conv: nn.Conv2d, bn, s2d, cin, act="relu"):
         """3x3 / stride 2 / pad 1 conv of the tensor whose space-to-depth image is `s2d` ([N, 4*cin, H/2, W/2])."""

@@ -323,10 +323,9 @@ class SemanticNetworkWithFPN(_FPNBase):
         finally:
             _ag.nbt_scope_exit()
 
-    def _forward(self, x, meta_channel, drop_scale):
-        x, meta = self._check_inputs(x, meta_channel)
-        if self._wants_autograd(x, meta):
-            return self._forward_train_opt(x, meta, drop_scale)
+    def _pyramid(self, x, meta):
+        """The part of the inference forward no dropout can reach: encoder, FPN blocks, attention, UpsampleBlocks -> (f1, u2, u34), the three
+        sources of the first decoder conv (cat([x1, x2, x3, x4]) with x3 and x4 sharing a buffer)."""
         if self.is_effnet:
             x1, x2, x3, x4 = self._encode_effnet(x, meta)
         else:
@@ -341,16 +340,78 @@ class SemanticNetworkWithFPN(_FPNBase):
         u4 = self._upsample_block("up4", self.upsample_layer_x4, f4)
         u3 = self._upsample_block("up3", self.upsample_layer_x3, f3)
         u2 = self._upsample_block("up2", self.upsample_layer_x2, f2)
-        # cat([x1, x2, x3, x4]) -> dropout_pyramid -> decoder conv: three sources (x1 | x2 | x3 + x4 share a buffer), multipliers per source
-        n = f1.shape[0]
-        c1, c2, c3, c4 = f1.shape[1], u2.shape[1], u3.shape[1], u4.shape[1]
-        s = self._pyramid_dropout(n, c1 + c2 + c3 + c4, f1.device, drop_scale)
-        u34 = torch.cat([u3, u4], dim=1)              # the fused conv takes up to three sources
+        return f1, u2, torch.cat([u3, u4], dim=1)              # the fused conv takes up to three sources
+
+    def _decoder(self, f1, u2, u34, s, passes: int = 0, raw_head_input: bool = False):
+        """dropout_pyramid multipliers s ([N, C_pyramid] or None) -> decoder_semantic.  passes = T > 0: the pyramid holds B images and the
+        decoder runs T * B stacked passes, its first conv reading image n % B in place.  raw_head_input: stop at the UpsampleBlock's raw conv
+        output (what slu_head_mc_f32 normalises itself)."""
+        b = f1.shape[0]
+        c1, c2 = f1.shape[1], u2.shape[1]
         sc = (None, None, None) if s is None else (s[:, :c1].contiguous(), s[:, c1:c1 + c2].contiguous(), s[:, c1 + c2:].contiguous())
         d = self.decoder_semantic
-        y = self._conv("dec0", d[0], None, [ConvSource(f1, sc[0]), ConvSource(u2, sc[1]), ConvSource(u34, sc[2])], act="none")
+        if passes:
+            y = self._conv("dec0", d[0], None, [ConvSource(f1, sc[0], False, b), ConvSource(u2, sc[1], False, b), ConvSource(u34, sc[2], False, b)],
+                           act="none", n_out=passes * b)
+        else:
+            y = self._conv("dec0", d[0], None, [ConvSource(f1, sc[0]), ConvSource(u2, sc[1]), ConvSource(u34, sc[2])], act="none")
         y = ops.groupnorm(y, d[1].num_groups, d[1].weight.detach(), d[1].bias.detach(), d[1].eps, relu=True, inplace=True)
         y = self._conv("dec1", d[3], None, [ConvSource(y)], act="none")
         y = ops.groupnorm(y, d[4].num_groups, d[4].weight.detach(), d[4].bias.detach(), d[4].eps, relu=True, inplace=True)
+        if raw_head_input:
+            up = d[6]
+            if up.mode != "bilinear":
+                raise NotImplementedError("UpsampleBlock: only mode='bilinear' (what the reference constructs) runs on the HIP path")
+            return self._conv("dec_up", up.block[0], None, [ConvSource(ops.bilinear_upsample(y, up.scale))], act="none")
         y = self._upsample_block("dec_up", d[6], y)
         return self._conv("dec_out", d[7], None, [ConvSource(y)], act="none")
+
+    def _forward(self, x, meta_channel, drop_scale):
+        x, meta = self._check_inputs(x, meta_channel)
+        if self._wants_autograd(x, meta):
+            return self._forward_train_opt(x, meta, drop_scale)
+        f1, u2, u34 = self._pyramid(x, meta)
+        # cat([x1, x2, x3, x4]) -> dropout_pyramid -> decoder conv: three sources (x1 | x2 | x3 + x4 share a buffer), multipliers per source
+        s = self._pyramid_dropout(f1.shape[0], f1.shape[1] + u2.shape[1] + u34.shape[1], f1.device, drop_scale)
+        return self._decoder(f1, u2, u34, s)
+
+    # ---------------- MC dropout with the pyramid computed once (utils.mc_dropout, share_prefix=True) ----------------
+    def _mc_shared(self, x, meta_channel, T: int, scale, raw_head_input: bool):
+        if self.training:
+            raise RuntimeError("forward_mc needs the model in eval mode (use utils.mc_dropout.mc_forward)")
+        x, meta = self._check_inputs(x, meta_channel)
+        if self._wants_autograd(x, meta):
+            raise RuntimeError("forward_mc is inference only: no train-mode BatchNorm and no gradients")
+        t = int(T)
+        if t < 1:
+            raise RuntimeError("forward_mc: T must be at least 1")
+        f1, u2, u34 = self._pyramid(x, meta)
+        s = self._pyramid_dropout(t * f1.shape[0], f1.shape[1] + u2.shape[1] + u34.shape[1], f1.device, scale)
+        return self._decoder(f1, u2, u34, s, passes=t, raw_head_input=raw_head_input)
+
+    @torch.no_grad()
+    def forward_mc(self, x, meta_channel, T: int, scale: Optional[torch.Tensor] = None):
+        """T stochastic passes of a batch -> logits [T*B, num_classes, H, W] (pass-major).  dropout_pyramid is the model's only dropout and sits
+        behind the encoder, the FPN blocks, the attentions and the UpsampleBlocks, so all of that runs ONCE at N = B; only decoder_semantic runs
+        at N = T*B, its first conv reading the B pyramid images in place.  The multipliers are one draw of the real dropout_pyramid child on
+        ones(T*B, C_pyramid, 1, 1) -- the draw the stacked forward makes, so the same seed gives the same passes -- unless `scale`
+        ([T*B, C_pyramid]) gives them.  Equals forward() on the inputs repeated T times.  Inference only."""
+        return self._mc_shared(x, meta_channel, T, scale, False)
+
+    def mc_fused_ok(self, x, meta_channel, T: int) -> bool:
+        """slu_head_mc_f32 covers this model's head: eval-mode inference on fp32 GPU inputs, at most 32 classes and 128 head input channels."""
+        if self.training or not all(isinstance(t, torch.Tensor) and t.dim() == 4 and t.is_cuda and t.dtype == torch.float32 for t in (x, meta_channel)):
+            return False
+        head = self.decoder_semantic[7]
+        return int(T) >= 1 and head.out_channels <= 32 and head.in_channels <= 128 and not self._wants_autograd(x, meta_channel)
+
+    @torch.no_grad()
+    def mc_predict_fused(self, x, meta_channel, T: int, eps: float = 1e-12, scale: Optional[torch.Tensor] = None):
+        """(p_bar, H_norm, MI_norm, preds) of T stochastic passes: the shared pyramid and the decoder up to the last UpsampleBlock's raw conv
+        output, then its GroupNorm statistics, then GroupNorm apply + ReLU + the 1x1 head + the MC reduction in one launch
+        (csrc/head_mc_f32.hip): neither the normalised tensor nor the T*B logit maps are written.  Call under utils.mc_dropout.dropout_sampling."""
+        y = self._mc_shared(x, meta_channel, T, scale, True)
+        gn, head = self.decoder_semantic[6].block[1], self.decoder_semantic[7]
+        stats = ops.groupnorm_stats(y, gn.num_groups, gn.eps)
+        return ops.head_mc_f32(y, head.weight.detach(), None if head.bias is None else head.bias.detach(), int(T), y.shape[0] // int(T), eps,
+                               gn_stats=stats, gn_groups=gn.num_groups, gn_gamma=gn.weight.detach(), gn_beta=gn.bias.detach(), relu=True)

@@ -153,9 +153,10 @@ def conv2d_fused(srcs: Sequence[ConvSource], wpack: torch.Tensor, cout: int, ksi
                  bn_a: Optional[torch.Tensor] = None, bn_b: Optional[torch.Tensor] = None,
                  resid: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
                  precision: str = "fp32", act: Optional[str] = None, act_after_resid: bool = False,
-                 stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 stats: Optional[torch.Tensor] = None, n_out: Optional[int] = None) -> torch.Tensor:
     """out = resid + bn_a * leaky(conv(cat(srcs)) + bias) + bn_b   (see slu_conv2d_fwd).
-    precision 'fp32' (exact, wpack from pack_conv_weight) or 'f16x3' (split-fp16, wpack from pack_conv_weight_f16x3)."""
+    precision 'fp32' (exact, wpack from pack_conv_weight) or 'f16x3' (split-fp16, wpack from pack_conv_weight_f16x3).
+    n_out: the output batch, for a conv whose sources are all batch-broadcast (`ConvSource.nbatch`); otherwise it is the first source's."""
     if precision not in PRECISIONS:
         raise ValueError(f"unknown conv precision {precision!r}")
     lib = _lib.load()
@@ -163,6 +164,10 @@ def conv2d_fused(srcs: Sequence[ConvSource], wpack: torch.Tensor, cout: int, ksi
         raise RuntimeError(f"conv2d_fused: 1..{_lib.MAX_SRC} sources supported, got {len(srcs)}")
     d = ConvDesc()
     n = h = w = None
+    if n_out is not None:
+        n = int(n_out)
+        if n < 1:
+            raise RuntimeError("conv2d_fused: n_out must be positive")
     cin = 0
     keep = []
     for i, s in enumerate(srcs):
@@ -181,12 +186,12 @@ def conv2d_fused(srcs: Sequence[ConvSource], wpack: torch.Tensor, cout: int, ksi
         else:
             contributed = sc
         if s.nbatch:
-            if i == 0 or sn != s.nbatch or n % sn:
-                raise RuntimeError(f"src[{i}]: a batch-broadcast source must follow a full-batch source and divide N")
+            if n is None or sn != s.nbatch or n % sn:
+                raise RuntimeError(f"src[{i}]: a batch-broadcast source must follow a full-batch source (or n_out be given) and divide N")
             sn = n
-        if n is None:
-            n, h, w = sn, sh, sw
-        elif (sn, sh, sw) != (n, h, w):
+        if h is None:
+            n, h, w = sn if n is None else n, sh, sw
+        if (sn, sh, sw) != (n, h, w):
             raise RuntimeError(f"src[{i}]: spatial/batch size {(sn, sh, sw)} != {(n, h, w)}")
         if s.scale is not None:
             _req(s.scale, f"src[{i}].scale")
@@ -894,6 +899,106 @@ def groupnorm(x: torch.Tensor, groups: int, gamma: Optional[torch.Tensor], beta:
     check(_lib.load().slu_groupnorm_fwd(x.data_ptr(), _ptr(gamma), _ptr(beta), n, c, h * w, int(groups), float(eps), 1 if relu else 0, stats[0].data_ptr(),
                                         stats[1].data_ptr(), y.data_ptr(), _stream()), "slu_groupnorm_fwd")
     return (y, stats) if return_stats else y
+
+
+def groupnorm_stats(x: torch.Tensor, groups: int, eps: float = 1e-5) -> torch.Tensor:
+    """[2, N * groups] (mean, rstd) of nn.GroupNorm(groups, C, eps) over NCHW x: the statistics launch of `groupnorm` alone."""
+    _req(x, "x")
+    if x.dim() != 4 or int(groups) < 1 or x.shape[1] % int(groups):
+        raise RuntimeError(f"groupnorm_stats: NCHW input with C divisible by groups={groups} expected, got {tuple(x.shape)}")
+    n, c, h, w = x.shape
+    stats = torch.empty((2, n * int(groups)), dtype=torch.float32, device=x.device)
+    args = (x.data_ptr(), n, c, h * w, int(groups), float(eps), stats[0].data_ptr(), stats[1].data_ptr(), _stream())
+    if TIMING is None:
+        check(_lib.load().slu_groupnorm_stats(*args), "slu_groupnorm_stats")
+        return stats
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    check(_lib.load().slu_groupnorm_stats(*args), "slu_groupnorm_stats")
+    e1.record()
+    nbytes = 4.0 * n * c * h * w
+    TIMING.append(("groupnorm_stats_kernel", 3.0 * n * c * h * w, nbytes, e0, e1, nbytes))
+    TIMING_TAGS.append(f"N{n} GroupNorm({groups}, {c}) statistics {h}x{w}")
+    return stats
+
+
+def head_mc_f32(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], passes: int, batch: int, eps: float = 1e-12,
+                gn_stats: Optional[torch.Tensor] = None, gn_groups: int = 0, gn_gamma: Optional[torch.Tensor] = None,
+                gn_beta: Optional[torch.Tensor] = None, relu: bool = False):
+    """x fp32 [T*B, Cin, H, W] (pass-major) -> (p_bar [B,C,H,W], H_norm [B,H,W], MI_norm [B,H,W], preds int64 [B,H,W]): GroupNorm apply
+    (gn_stats = groupnorm_stats(x, gn_groups); None: x is used as it is) [+ ReLU], the 1x1 head `weight` [C, Cin(, 1, 1)] + bias and the
+    MC-dropout reduction of trainer.py:1143-1154 in one launch (slu_head_mc_f32); neither the normalised tensor nor logits are written."""
+    _req(x, "x")
+    if x.dim() != 4:
+        raise RuntimeError(f"head_mc_f32: expected [T*B, Cin, H, W], got {tuple(x.shape)}")
+    n, cin, h, w = x.shape
+    passes, batch = int(passes), int(batch)
+    if passes < 1 or batch < 1 or n != passes * batch:
+        raise RuntimeError(f"head_mc_f32: {n} images != T * B = {passes} * {batch}")
+    _req(weight, "weight")
+    if weight.dim() not in (2, 4) or weight.shape[1] != cin or weight.numel() != weight.shape[0] * cin:
+        raise RuntimeError(f"weight: expected [C, {cin}] or [C, {cin}, 1, 1], got {tuple(weight.shape)}")
+    classes = weight.shape[0]
+    if not 1 <= classes <= 32 or cin > 128:
+        raise RuntimeError(f"head_mc_f32: covers 1..32 classes and up to 128 input channels, got {classes} and {cin}")
+    if bias is not None:
+        _req(bias, "bias")
+        if bias.numel() != classes:
+            raise RuntimeError(f"bias: expected {classes} elements, got {bias.numel()}")
+    mean = rstd = None
+    groups = 0
+    if gn_stats is not None:
+        groups = int(gn_groups)
+        if groups < 1 or cin % groups:
+            raise RuntimeError(f"head_mc_f32: gn_groups={gn_groups} must divide Cin={cin}")
+        _req(gn_stats, "gn_stats")
+        if tuple(gn_stats.shape) != (2, n * groups):
+            raise RuntimeError(f"gn_stats: expected {(2, n * groups)}, got {tuple(gn_stats.shape)}")
+        mean, rstd = gn_stats[0], gn_stats[1]
+        for t, nme in ((gn_gamma, "gn_gamma"), (gn_beta, "gn_beta")):
+            if t is not None:
+                _req(t, nme)
+                if t.numel() != cin:
+                    raise RuntimeError(f"{nme}: expected {cin} elements")
+    elif gn_gamma is not None or gn_beta is not None:
+        raise RuntimeError("head_mc_f32: gn_gamma / gn_beta need gn_stats")
+    dev = x.device
+    p_bar = torch.empty((batch, classes, h, w), dtype=torch.float32, device=dev)
+    hn = torch.empty((batch, h, w), dtype=torch.float32, device=dev)
+    mi = torch.empty((batch, h, w), dtype=torch.float32, device=dev)
+    preds = torch.empty((batch, h, w), dtype=torch.int64, device=dev)
+    head_mc_f32_out(x, weight, bias, passes, batch, eps, mean, rstd, groups, gn_gamma if mean is not None else None,
+                    gn_beta if mean is not None else None, relu, p_bar, hn, mi, preds)
+    return p_bar, hn, mi, preds
+
+
+def head_mc_f32_out(x, weight, bias, passes, batch, eps, mean, rstd, groups, gamma, beta, relu, p_bar, hn, mi, preds) -> None:
+    """The launch of `head_mc_f32` into caller-owned outputs (shapes as `head_mc_f32` returns them; checked here)."""
+    n, cin, h, w = x.shape
+    classes = weight.shape[0]
+    for t, nme, shape, dt in ((p_bar, "p_bar", (batch, classes, h, w), torch.float32), (hn, "h_norm", (batch, h, w), torch.float32),
+                              (mi, "mi_norm", (batch, h, w), torch.float32), (preds, "preds", (batch, h, w), torch.int64)):
+        _req(t, nme, dt)
+        if tuple(t.shape) != shape:
+            raise RuntimeError(f"{nme}: expected {shape}, got {tuple(t.shape)}")
+    lib = _lib.load()
+    args = (x.data_ptr(), passes, batch, cin, h * w, _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta), int(groups), 1 if relu else 0,
+            weight.data_ptr(), _ptr(bias), classes, float(eps), p_bar.data_ptr(), hn.data_ptr(), mi.data_ptr(), preds.data_ptr(), _stream())
+    if TIMING is None:
+        check(lib.slu_head_mc_f32(*args), "slu_head_mc_f32")
+        return
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    check(lib.slu_head_mc_f32(*args), "slu_head_mc_f32")
+    e1.record()
+    px = float(n * h * w)
+    flops = 2.0 * cin * classes * px
+    # layer-granular accounting of what it replaces: GroupNorm apply (read + write), the head conv (read, write logits), the reduction (read them)
+    nbytes = px * 4.0 * (3 * cin + 2 * classes) + batch * h * w * (4.0 * classes + 16.0)
+    # what the fused kernel must move: the conv output of every pass in, p_bar / H / MI / argmax of every scan out
+    min_bytes = px * 4.0 * cin + batch * h * w * (4.0 * classes + 16.0) + 4.0 * classes * cin
+    TIMING.append((f"head_mc_f32_kernel<{(classes + 7) // 8}>", flops, nbytes, e0, e1, min_bytes))
+    TIMING_TAGS.append(f"N{n} {cin}->{classes} GroupNorm apply + 1x1 head + MC reduce T={passes} {h}x{w}")
 
 
 def spatial_softmax_gate(x: torch.Tensor, score: torch.Tensor, return_stats: bool = False):

@@ -46,11 +46,11 @@ def _stacked_passes(model, inputs, T: int, share_prefix: bool = False):
     inputs = list(inputs)
     b = inputs[0].shape[0]
     done = 0
-    shared = share_prefix and len(inputs) == 1 and hasattr(model, "forward_mc")
+    shared = share_prefix and hasattr(model, "forward_mc")
     while done < T:
         t = min(MAX_STACK, T - done)
         if shared:
-            out = model.forward_mc(inputs[0], t)
+            out = model.forward_mc(*inputs, t)
             yield out.reshape(t, b, *out.shape[1:])
             done += t
             continue
@@ -67,8 +67,8 @@ def _stacked_passes(model, inputs, T: int, share_prefix: bool = False):
 @torch.no_grad()
 def mc_forward(model: nn.Module, inputs, T: int = 30, share_prefix: bool = False):
     """[T,B,C,H,W] raw model outputs of T stochastic passes (reference mc_dropout.py:98-119).
-    share_prefix=True lets a model that implements `forward_mc` compute the layers no active dropout can reach
-    once instead of T times (identical results; see SalsaNext.forward_mc)."""
+    share_prefix=True lets a model that implements `forward_mc(*inputs, T)` compute the layers no active dropout can reach
+    once instead of T times (identical results; see SalsaNext.forward_mc, fpn_opt.SemanticNetworkWithFPN.forward_mc)."""
     model.eval()
     with dropout_sampling(model, enable=True):
         parts = list(_stacked_passes(model, inputs, T, share_prefix))
@@ -112,6 +112,11 @@ def mc_predict(model: nn.Module, inputs, T: int = 30, eps: float = 1e-12, share_
         if model.mc_fused_ok(xs[0], T):                 # half-precision SalsaNext: head conv + reduction in one launch, no logit maps
             with dropout_sampling(model, enable=True):
                 return model.mc_predict_fused(xs[0], T, eps, share_prefix)
+    elif len(xs) > 1 and share_prefix and T <= MAX_STACK and hasattr(model, "mc_predict_fused") and hasattr(model, "mc_fused_ok"):
+        model.eval()
+        if model.mc_fused_ok(*xs, T):                   # semanticFCN_opt: pyramid once, GroupNorm apply + head + reduction in one launch
+            with dropout_sampling(model, enable=True):
+                return model.mc_predict_fused(*xs, T, eps)
     return ops.mc_reduce(mc_forward(model, inputs, T, share_prefix).contiguous(), eps)
 
 

@@ -1,6 +1,8 @@
 #!/usr/bin/env python
 """Single-pass FPN inference timing at the reference's own self-benchmark shape (src/models/semanticFCN.py:381-395:
-1 x (2 + 6) x 128 x 2048, median of CUDA-event timings).  python tools/fpn_bench.py [--backbone resnet18] [--batch 1]"""
+1 x (2 + 6) x 128 x 2048, median of CUDA-event timings).  python tools/fpn_bench.py [--backbone resnet18] [--batch 1]
+--model opt --mc T: the MC-dropout evaluation step (utils.mc_dropout.mc_predict, T passes) of `semanticFCN_opt` at B x (2 + 6) x 64 x 2048,
+three ways: stacked (every pass runs the whole network), shared (pyramid once, fpn_opt.forward_mc) and shared + fused (slu_head_mc_f32)."""
 import argparse
 import json
 import os
@@ -18,9 +20,45 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--backbone", default="resnet18")
 ap.add_argument("--batch", type=int, default=1)
 ap.add_argument("--iters", type=int, default=100)
+ap.add_argument("--model", default="fpn", choices=["fpn", "opt"])
+ap.add_argument("--mc", type=int, default=0, help="with --model opt: MC-dropout passes T")
+ap.add_argument("--precision", default="fp32", choices=["fp32", "f16x3"], help="with --model opt: conv precision")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 torch.manual_seed(0)
+
+
+def _median_ms(fn, iters, warmup=5):
+    for _ in range(warmup):
+        fn()
+    ts = []
+    for _ in range(iters):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        ts.append(e0.elapsed_time(e1))
+    return statistics.median(ts)
+
+
+if a.model == "opt":
+    from semanticlidarunc_amd import ops  # noqa: E402
+    from semanticlidarunc_amd.fpn_opt import SemanticNetworkWithFPN as OptFPN  # noqa: E402
+    from semanticlidarunc_amd.utils.mc_dropout import mc_forward, mc_predict  # noqa: E402
+    if a.mc < 1:
+        ap.error("--model opt needs --mc T")
+    model = randomize_bn_(OptFPN(a.backbone, 2, 6, num_classes=20), 3).eval().to(dev)
+    x, meta = torch.randn(a.batch, 2, 64, 2048, device=dev), torch.randn(a.batch, 6, 64, 2048, device=dev)
+    sn.set_conv_precision(a.precision)
+    ways = {"stacked": lambda: mc_predict(model, [x, meta], T=a.mc, share_prefix=False),
+            "shared": lambda: ops.mc_reduce(mc_forward(model, [x, meta], T=a.mc, share_prefix=True).contiguous()),
+            "shared_fused": lambda: mc_predict(model, [x, meta], T=a.mc, share_prefix=True)}
+    ms = {k: round(_median_ms(f, a.iters), 3) for k, f in ways.items()}
+    print(json.dumps({"model": f"semanticFCN_opt/{a.backbone}", "shape": [a.batch, 8, 64, 2048], "T": a.mc, "precision": a.precision, "median_ms": ms,
+                      "speedup_shared": round(ms["stacked"] / ms["shared"], 3), "speedup_shared_fused": round(ms["stacked"] / ms["shared_fused"], 3)}))
+    sys.exit(0)
+
 model = randomize_bn_(SemanticNetworkWithFPN(a.backbone, 2, 6, num_classes=20), 3).eval().to(dev)
 x, meta = torch.randn(a.batch, 2, 128, 2048, device=dev), torch.randn(a.batch, 6, 128, 2048, device=dev)
 out = {}
