@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SLU_ABI_VERSION 34
+#define SLU_ABI_VERSION 35
 
 #define SLU_OK            0
 #define SLU_EINVAL       -1   /* null pointer / non-positive size / inconsistent descriptor   */
@@ -351,13 +351,18 @@ typedef struct slu_conv_h8_desc {   /* HOST struct */
   const void* resid;     /* h8 [N][ceil(Cout/8)][H][W][8] or NULL                                                    */
   void* out;             /* h8 [N][ceil(Cout/8)][H][W][8], or fp32 [N][Cout][H][W] when out_f32_nchw                  */
   int32_t out_f32_nchw;  /* 1: the logits head (SalsaNext.py:213) keeps the reference's fp32 NCHW output; 1x1 convs only */
+  int32_t act_after_resid; /* 1: out = act(conv + bias + resid), the tail of a torchvision BasicBlock with its BatchNorm folded
+                            (semanticFCN.py:145-153 builds on it; out = relu(bn2(conv2(.)) + identity)).  Needs resid, has_act and
+                            no bn_a; (k,dil,pad) = (3,1,1), h8 output, no scale, no shuffled source (conv_h8_late_kernel).
+                            Anything else with the flag set is SLU_EUNSUPPORTED: it is never ignored.  0: the order above      */
 } slu_conv_h8_desc;
 
 size_t slu_packed_weight_bytes_h8(int cout, int cin, int ksize);
 /* w: OIHW fp32 [cout][cin][k][k] (cin = real channels of the concatenated input; only the LAST source may be padded) */
 int slu_pack_conv_weight_h8(const float* w, int cout, int cin, int ksize, void* out, slu_stream_t stream);
 /* out = [resid +] bn_a * act(conv(cat(src * scale)) + bias) + bn_b, rounded to fp16 once.
- * Families: (k,dil,pad) = (1,1,0), (3,1,1), (3,2,2), (2,2,1) as in slu_conv2d_fwd. */
+ * Families: (k,dil,pad) = (1,1,0), (3,1,1), (3,2,2), (2,2,1) as in slu_conv2d_fwd, and (2,1,1) without scales: taps at offsets -1 and 0,
+ * which is a 3x3 / stride 2 / pad 1 conv (the first conv of a ResNet stage) over slu_space_to_depth2_h8 of its input. */
 int slu_conv2d_h8_fwd(const slu_conv_h8_desc* desc, slu_stream_t stream);
 /* name of the kernel instantiation the call above launches (as rocprofv3 prints it), by the same rules as slu_conv2d_kernel_name
  * (96 bytes hold every name) */
@@ -371,6 +376,33 @@ int slu_avgpool3s2_h8(const void* x, const float* scale, void* y, int N, int in_
  * x: h8 with Gin blocks at HxW; y: h8 with ceil(2 Gin / 8) blocks at 2Hx2W; scales fp32 [N][8 Gin] / [N][2 Gin] or NULL */
 int slu_pixel_shuffle_h8(const void* x, const float* scale_in, const float* scale_out, void* y, int N, int Gin, int H, int W,
                          slu_stream_t stream);
+
+/* ---- h8 data movement of the ResNet-FPN model (models/semanticFCN.py): fpn_h8.hip ------------------------------------------ */
+/* MaxPool2d(3, 2, 1) (the stem's backbone.maxpool, semanticFCN.py:149): x h8 [N][G][H][W][8] -> y h8 [N][G][ceil(H/2)][ceil(W/2)][8];
+ * taps outside the image are -inf (never chosen), pad channels stay 0 */
+int slu_maxpool3s2_h8(const void* x, void* y, int N, int G, int H, int W, slu_stream_t stream);
+/* Space-to-depth by 2 ahead of a stage's stride-2 convs (semanticFCN.py:309-313 + torchvision BasicBlock.conv1 / downsample[0]):
+ * x h8 [N][G][H][W][8] (H, W even) -> y h8 [N][4 G][H/2][W/2][8], phase-major: channel (2 p + q) 8 G + c = x[c][2 y + p][2 x + q], so the
+ * 3x3 / stride 2 / pad 1 conv is the (2,1,1) conv of y, and y00 (h8 [N][G][H/2][W/2][8] or NULL) = phase (0, 0) on its own, which the
+ * 1x1 / stride 2 downsample conv reads as a plain 1x1.  meta != NULL: channels C - m .. C - 1 of x are replaced on the way by
+ * meta[n][.][f (2 y + p)][f (2 x + q)] rounded to fp16 -- torch.cat([x[:, :-m], F.interpolate(meta, scale_factor=1/f, mode="nearest")], 1)
+ * (semanticFCN.py:283-285) -- with meta fp32 [N][m][f H][f W], f in {1, 2, 4, 8}, 0 < m <= C, 8 (G - 1) < C <= 8 G */
+int slu_space_to_depth2_h8(const void* x, const float* meta, int m, int C, int f, void* y, void* y00, int N, int G, int H, int W,
+                           slu_stream_t stream);
+/* The tail of AttentionModule.forward (semanticFCN.py:25-40) in one launch: tv = h8 [N][2 C / 8][H][W][8], the output of ONE 1x1 conv with
+ * the stacked weights [W_q + W_k ; W_v] (channels 0 .. C - 1 = t = q + k, C .. 2 C - 1 = v).  Per image row:
+ * s[w] = b_a[0] + sum_c w_a[c] tanh(t[c][w]) in fp32, p = softmax_w(s), out[c][w] = v[c][w] p[w] rounded to fp16 once.
+ * w_a fp32 [C], b_a fp32 [1] (device memory); out h8 [N][C / 8][H][W][8]; C % 8 == 0, W <= 4096 */
+int slu_attention_row_h8(const void* tv, const float* w_a, const float* b_a, void* out, int N, int C, int H, int W, slu_stream_t stream);
+/* ConvTranspose2d(kernel = stride = s) (upsample_layer_x2 / x3 / x4, semanticFCN.py:230-232) after its 1x1 conv: y = h8
+ * [N][s s Cout / 8][H][W][8] with channels ordered (i, j, cout), Cout % 8 == 0, so every output record is a whole input record:
+ * out[n][g_off + g][s h + i][s w + j] = y[n][(i s + j) Cout / 8 + g][h][w], out = h8 [N][Gtot][s H][s W][8] (a block slice of the
+ * concatenated up-sampled maps that decoder_semantic reads); s in {2, 4, 8} */
+int slu_depth_to_space_h8(const void* y, void* out, int N, int Cout, int s, int H, int W, int Gtot, int g_off, slu_stream_t stream);
+/* The end of decoder_semantic (ConvTranspose2d(k 4, s 2, p 1) + ELU, semanticFCN.py:244-245, and the + 1 of forward's return) after its 3x3 conv to
+ * 4 `classes` sub-pixel channels ordered (class, i, j): out[n][c][2 h + i][2 w + j] = elu(y[n][4 c + 2 i + j][h][w]) + 1;
+ * y = h8 [N][ceil(4 classes / 8)][H][W][8], out fp32 NCHW [N][classes][2 H][2 W] */
+int slu_depth_to_space2_elu_h8(const void* y, float* out, int N, int classes, int H, int W, slu_stream_t stream);
 
 /* Fused tail of a SalsaNext block on the h8 path (ResBlock.conv4 + conv5, SalsaNext.py:59-68; UpBlock.conv3 + conv4, :157-167):
  *   a3  = bnA_a * actA(conv2x2_dil2_pad1(a2) + biasA) + bnA_b          (kept on chip, rounded to fp16 like the stored tensor would be)

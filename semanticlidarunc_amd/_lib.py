@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-ABI_VERSION = 34
+ABI_VERSION = 35
 MAX_SRC = 3
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libslu_hip.so")
@@ -58,6 +58,7 @@ class ConvH8Desc(C.Structure):
         ("bn_a", C.c_void_p), ("bn_b", C.c_void_p),
         ("resid", C.c_void_p), ("out", C.c_void_p),
         ("out_f32_nchw", C.c_int32),
+        ("act_after_resid", C.c_int32),
     ]
 
 
@@ -164,6 +165,12 @@ SIGNATURES = {
     "slu_h8_to_nchw": (C.c_int, [C.c_void_p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_stream]),
     "slu_avgpool3s2_h8": (C.c_int, [C.c_void_p, c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_stream]),
     "slu_pixel_shuffle_h8": (C.c_int, [C.c_void_p, c_f32p, c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_stream]),
+    "slu_maxpool3s2_h8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_stream]),
+    "slu_space_to_depth2_h8": (C.c_int, [C.c_void_p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         c_stream]),
+    "slu_attention_row_h8": (C.c_int, [C.c_void_p, c_f32p, c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_stream]),
+    "slu_depth_to_space_h8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_stream]),
+    "slu_depth_to_space2_elu_h8": (C.c_int, [C.c_void_p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_stream]),
     "slu_dirichlet_head": (C.c_int, [c_f32p, C.c_longlong, c_f32p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, c_f32p,
                                      c_f32p, c_f32p, c_f32p, c_i64p, c_stream]),
     "slu_dirichlet_uncertainty": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_float, c_f32p, c_f32p, c_f32p, c_i64p, c_stream]),

@@ -1,4 +1,4 @@
-// Device vocabulary shared by the half-precision ("h8") kernels: conv2d_h8.hip, conv_tail_h8.hip, ctx_block_h8.hip, head_mc_h8.hip.
+// Device vocabulary shared by the half-precision ("h8") kernels: conv2d_h8.hip, conv_tail_h8.hip, ctx_block_h8.hip, head_mc_h8.hip, fpn_h8.hip.
 // Every helper is forced inline, and its form (what comes by value, by reference, as a macro) is the one with which the kernels compile
 // to the instruction streams of the hand-written copies they replace: check a change here with tools/h8_isa_diff.py (profiles/r07).
 #pragma once
@@ -92,6 +92,12 @@ __device__ __forceinline__ uint4 h8_swap16(unsigned h0, unsigned h1, unsigned h2
   const auto s0 = __builtin_amdgcn_permlane32_swap(h0, h2, false, false);
   const auto s1 = __builtin_amdgcn_permlane32_swap(h1, h3, false, false);
   return make_uint4(s0[0], s1[0], s0[1], s1[1]);
+}
+
+// LeakyReLU in place, as max(t, slope t) like h8_bias_leaky (the late activation of conv_h8_late_kernel: after the residual add)
+__device__ __forceinline__ void h8_leaky(H8Quad& t, float2v sl) {
+  t.t0 = __builtin_elementwise_max(t.t0, t.t0 * sl);
+  t.t1 = __builtin_elementwise_max(t.t1, t.t1 * sl);
 }
 
 // 8 fp32 multipliers (Dropout2d) of one channel block, rounded to fp16 first: B fragments take them as packed multiplies

@@ -17,6 +17,12 @@ How the layers map onto kernels (inference; BatchNorm folded into the preceding 
                                   softmax over azimuth fused with the multiply into the value map
   ConvTranspose2d k = s ......... 1x1 conv to Cout*s*s channels + depth-to-space
   ConvTranspose2d k4 s2 p1 ...... 3x3 conv to 4*classes sub-pixel channels + depth-to-space fused with ELU + 1
+
+Conv precision "f16" (resnet18 / resnet34, inference): the same layers on the half-precision storage path (h8.py) -- activations stay
+[N, G, H, W, 8] fp16 from the stem's input to the last conv's output (`_forward_h8`).  What differs from the list above: the space-to-depth
+kernel reads the meta channels from the full-resolution tensor itself (no down-sampled copies) and also writes phase (0,0) as a tensor of its
+own for the 1x1/s2 conv; an attention module is ONE 1x1 conv with the stacked weights [W_q + W_k ; W_v] + one row kernel (tanh, score,
+softmax, multiply); the k = s transposed convs order their channels (i, j, cout) so that depth-to-space copies whole 16-byte records.
 """
 from __future__ import annotations
 
@@ -25,6 +31,7 @@ from typing import Dict, List, Optional
 import torch
 import torch.nn as nn
 
+from . import h8 as _h8
 from . import ops
 from . import salsanext as _sn
 from .ops import ConvSource
@@ -108,7 +115,7 @@ class AttentionModule(nn.Module):
 
 # ----------------------------------------------------------------------------------------------------------------
 class _Packed:
-    __slots__ = ("key", "wpack", "bias", "cout", "k", "dil", "pad", "precision")
+    __slots__ = ("key", "wpack", "bias", "cout", "cin", "k", "dil", "pad", "precision")
 
 
 def _key(*ts):
@@ -201,10 +208,13 @@ class SemanticNetworkWithFPN(nn.Module):
         if p is None or p.key != k:
             w, b, ksz, dil, pad = maker()
             p = _Packed()
-            p.key, p.cout, p.k, p.dil, p.pad = k, w.shape[0], ksz, dil, pad
+            p.key, p.cout, p.cin, p.k, p.dil, p.pad = k, w.shape[0], w.shape[1], ksz, dil, pad
             p.precision = _sn.get_conv_precision()
             w = w.detach().float().contiguous()
-            p.wpack = ops.pack_conv_weight_f16x3(w) if p.precision == "f16x3" else ops.pack_conv_weight(w)
+            if p.precision == "f16":
+                p.wpack = _h8.pack_conv_weight_h8(w)
+            else:
+                p.wpack = ops.pack_conv_weight_f16x3(w) if p.precision == "f16x3" else ops.pack_conv_weight(w)
             p.bias = None if b is None else b.detach().float().contiguous()
             cache[name] = p
         return p
@@ -222,21 +232,24 @@ class SemanticNetworkWithFPN(nn.Module):
             b = b + conv_b.detach() * a
         return conv_w.detach() * a.view(-1, 1, 1, 1), b
 
-    def _conv(self, name, conv: nn.Conv2d, bn, srcs, act="relu", resid=None, late=False, tail_first: int = 0, n_out: Optional[int] = None):
-        """tail_first = m > 0: the sources are given as (last m input channels, the rest) -- the packed weight's input channels are rotated
-        to match (a channel prefix `cuse` is only honoured on the LAST source of a fused conv)."""
+    def _p_conv(self, name, conv: nn.Conv2d, bn, tail_first: int = 0) -> _Packed:
+        """The packed conv with its BatchNorm folded in.  tail_first = m > 0: the sources are given as (last m input channels, the rest) -- the
+        packed weight's input channels are rotated to match (a channel prefix `cuse` is only honoured on the LAST source of a fused conv)."""
         def make():
             w, b = self._fold(conv.weight, conv.bias, bn)
             if tail_first:
                 w = torch.cat([w[:, -tail_first:], w[:, :-tail_first]], 1)
             return w, b, conv.kernel_size[0], conv.dilation[0], conv.padding[0]
-        p = self._prep(name, make,
-                       conv.weight, conv.bias, *(() if bn is None else (bn.weight, bn.bias, bn.running_mean, bn.running_var)))
+        return self._prep(name, make,
+                          conv.weight, conv.bias, *(() if bn is None else (bn.weight, bn.bias, bn.running_mean, bn.running_var)))
+
+    def _conv(self, name, conv: nn.Conv2d, bn, srcs, act="relu", resid=None, late=False, tail_first: int = 0, n_out: Optional[int] = None):
+        p = self._p_conv(name, conv, bn, tail_first)
         return ops.conv2d_fused(srcs, p.wpack, p.cout, p.k, p.dil, p.pad, bias=p.bias, resid=resid, precision=p.precision,
                                 act=act, act_after_resid=late, n_out=n_out)
 
-    def _conv_s2(self, name, conv: nn.Conv2d, bn, s2d, cin, act="relu"):
-        """3x3 / stride 2 / pad 1 conv of the tensor whose space-to-depth image is `s2d` ([N, 4*cin, H/2, W/2])."""
+    def _p_conv_s2(self, name, conv: nn.Conv2d, bn, cin) -> _Packed:
+        """The 3x3 / stride 2 / pad 1 conv as the 2x2 / pad 1 conv (taps at -1 and 0) over the space-to-depth image of its input."""
         def make():
             w, b = self._fold(conv.weight, conv.bias, bn)
             cout = w.shape[0]
@@ -246,7 +259,11 @@ class SemanticNetworkWithFPN(nn.Module):
                 for j, (q, bb) in tap.items():
                     w2[:, 2 * p + q, :, a, bb] = w[:, :, i, j]
             return w2.reshape(cout, 4 * cin, 2, 2), b, 2, 1, 1
-        p = self._prep(name, make, conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var)
+        return self._prep(name, make, conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var)
+
+    def _conv_s2(self, name, conv: nn.Conv2d, bn, s2d, cin, act="relu"):
+        """3x3 / stride 2 / pad 1 conv of the tensor whose space-to-depth image is `s2d` ([N, 4*cin, H/2, W/2])."""
+        p = self._p_conv_s2(name, conv, bn, cin)
         return ops.conv2d_fused([ConvSource(s2d)], p.wpack, p.cout, 2, 1, 1, bias=p.bias, precision=p.precision, act=act)
 
     def _convT_eq_stride(self, name, ct: nn.ConvTranspose2d, x, out=None, c_off=0):
@@ -262,7 +279,8 @@ class SemanticNetworkWithFPN(nn.Module):
         y = ops.conv2d_fused([ConvSource(x)], p.wpack, p.cout, 1, 1, 0, bias=p.bias, precision=p.precision, act="none")
         return ops.depth_to_space(y, s, False, out, c_off)
 
-    def _convT_k4s2p1(self, name, ct: nn.ConvTranspose2d, x, elu_plus_one):
+    def _p_convT_k4s2p1(self, name, ct: nn.ConvTranspose2d) -> _Packed:
+        """ConvTranspose2d(4, 2, 1) as a 3x3 conv to 4 * Cout sub-pixel channels ordered (cout, i, j)."""
         def make():
             w = ct.weight.detach()                               # [Cin, Cout, 4, 4]
             cin, cout = w.shape[0], w.shape[1]
@@ -275,7 +293,10 @@ class SemanticNetworkWithFPN(nn.Module):
                             wf[:, py, px, :, dy + 1, dx + 1] = w[:, :, i, j].t()
             b = None if ct.bias is None else ct.bias.detach().repeat_interleave(4)
             return wf.reshape(cout * 4, cin, 3, 3), b, 3, 1, 1
-        p = self._prep(name, make, ct.weight, ct.bias)
+        return self._prep(name, make, ct.weight, ct.bias)
+
+    def _convT_k4s2p1(self, name, ct: nn.ConvTranspose2d, x, elu_plus_one):
+        p = self._p_convT_k4s2p1(name, ct)
         y = ops.conv2d_fused([ConvSource(x)], p.wpack, p.cout, 3, 1, 1, bias=p.bias, precision=p.precision, act="none")
         return ops.depth_to_space(y, 2, elu_plus_one)
 
@@ -329,6 +350,76 @@ class SemanticNetworkWithFPN(nn.Module):
         score = self._conv(name + ".score", att.attention_conv, None, [ConvSource(t)], act="none")
         value = self._conv(name + ".value", att.value_conv, None, [ConvSource(x)], act="none")
         return ops.row_softmax_mul(score, value)
+
+    # ---------------- half-precision storage path (conv precision "f16"): h8 tensors [N, G, H, W, 8] fp16 throughout ----------------
+    @staticmethod
+    def _run_h8(p: _Packed, srcs, relu=True, resid=None, late=False):
+        """One h8 conv launch: relu(conv + bias) [+ resid], or with `late` relu(conv + bias + resid).  ReLU is LeakyReLU with slope 0."""
+        return _h8.conv2d_h8([_h8.H8Source(t) for t in srcs], p.wpack, p.cin, p.cout, p.k, p.dil, p.pad, bias=p.bias,
+                             slope=0.0 if relu else None, resid=resid, act_after_resid=late)
+
+    def _stage_h8(self, lname: str, layer: nn.Sequential, x, meta, factor: int):
+        """One BasicBlock stage.  meta (full resolution, fp32 NCHW) or None: its nearest 1 / factor down-sampling overwrites the last m channels
+        of x on the way into the stage, inside the space-to-depth kernel."""
+        for bi, blk in enumerate(layer):
+            n = f"{lname}.{bi}"
+            if bi == 0 and blk.stride == 2:
+                c = 8 * x.shape[1]
+                s2d, x00 = _h8.space_to_depth2_h8(x, meta, c, factor)
+                o1 = self._run_h8(self._p_conv_s2(n + ".conv1", blk.conv1, blk.bn1, c), [s2d])
+                idn = self._run_h8(self._p_conv(n + ".down", blk.downsample[0], blk.downsample[1]), [x00], relu=False)     # phase (0,0) == stride 2
+            else:
+                o1 = self._run_h8(self._p_conv(n + ".conv1", blk.conv1, blk.bn1), [x])
+                idn = x
+            x = self._run_h8(self._p_conv(n + ".conv2", blk.conv2, blk.bn2), [o1], resid=idn, late=True)
+        return x
+
+    def _attend_h8(self, name, att: AttentionModule, x):
+        q, k, v = att.query_conv, att.key_conv, att.value_conv
+
+        def make():      # tanh(q + k) needs only q + k: ONE conv C -> 2 C gives (q + k, v)
+            return (torch.cat([q.weight.detach() + k.weight.detach(), v.weight.detach()], 0),
+                    torch.cat([q.bias.detach() + k.bias.detach(), v.bias.detach()], 0), 1, 1, 0)
+        p = self._prep(name + ".tv", make, q.weight, k.weight, v.weight, q.bias, k.bias, v.bias)
+        ac = att.attention_conv
+        return _h8.attention_row_h8(self._run_h8(p, [x], relu=False), ac.weight.detach().reshape(-1), ac.bias.detach())
+
+    def _up_h8(self, name, ct: nn.ConvTranspose2d, x, ups, g_off):
+        """ConvTranspose2d(k = s) into blocks [g_off, g_off + Cout / 8) of `ups`: 1x1 conv to s s Cout channels ordered (i, j, cout), then
+        depth-to-space as a copy of whole records."""
+        s = ct.stride[0]
+
+        def make():
+            w = ct.weight.detach()                               # [Cin, Cout, s, s]
+            cin, cout = w.shape[0], w.shape[1]
+            return w.permute(2, 3, 1, 0).reshape(s * s * cout, cin, 1, 1), None if ct.bias is None else ct.bias.detach().repeat(s * s), 1, 1, 0
+        p = self._prep(name + ".ijc", make, ct.weight, ct.bias)
+        _h8.depth_to_space_h8(self._run_h8(p, [x], relu=False), s, ups, g_off)
+
+    def _forward_h8(self, x, meta):
+        xs = self._run_h8(self._p_conv("stem", self.backbone.conv1, None), [_h8.to_h8(torch.cat([x, meta], 1))])      # bn1 is skipped by the reference stem
+        mm = meta if self.multi_scale_meta else None
+        x1 = self._stage_h8("layer1", self.layer1, _h8.maxpool3s2_h8(xs), None, 1)
+        x2 = self._stage_h8("layer2", self.layer2, x1, mm, 2)
+        x3 = self._stage_h8("layer3", self.layer3, x2, mm, 4)
+        x4 = self._stage_h8("layer4", self.layer4, x3, mm, 8)
+        f4 = self._run_h8(self._p_conv("fpn4", self.fpn_block4[0], self.fpn_block4[1]), [x4])
+        f3 = self._run_h8(self._p_conv("fpn3", self.fpn_block3[0], self.fpn_block3[1]), [x3])
+        f2 = self._run_h8(self._p_conv("fpn2", self.fpn_block2[0], self.fpn_block2[1]), [x2])
+        f1 = self._run_h8(self._p_conv("fpn1", self.fpn_block1[0], self.fpn_block1[1]), [x1])
+        if self.attention:
+            f4, f3 = self._attend_h8("att4", self.attention4, f4), self._attend_h8("att3", self.attention3, f3)
+            f2, f1 = self._attend_h8("att2", self.attention2, f2), self._attend_h8("att1", self.attention1, f1)
+        c2, c3, c4 = (m.out_channels for m in (self.upsample_layer_x2, self.upsample_layer_x3, self.upsample_layer_x4))
+        ups = torch.empty((f1.shape[0], (c2 + c3 + c4) // 8, f1.shape[2], f1.shape[3], 8), dtype=torch.float16, device=f1.device)
+        self._up_h8("up2", self.upsample_layer_x2, f2, ups, 0)
+        self._up_h8("up3", self.upsample_layer_x3, f3, ups, c2 // 8)
+        self._up_h8("up4", self.upsample_layer_x4, f4, ups, (c2 + c3) // 8)
+        d = self.decoder_semantic
+        y = self._run_h8(self._p_conv("dec0", d[0], d[1]), [f1, ups])
+        y = self._run_h8(self._p_conv("dec1", d[3], d[4]), [y])
+        y = self._run_h8(self._p_convT_k4s2p1("dec_out", d[6]), [y], relu=False)
+        return _h8.depth_to_space_h8(y, 2, elu_plus_one=True, classes=self.num_classes)
 
     # ---------------- training path: one autograd node per layer (fpn_autograd.py) ----------------
     def _dg(self, name: str) -> dict:
@@ -452,6 +543,11 @@ class SemanticNetworkWithFPN(nn.Module):
         if self.backbone_name == "resnet50" and _sn.get_conv_precision() == "f16x3":
             raise RuntimeError("models/semanticFCN with the resnet50 backbone does not run with conv precision 'f16x3': split-fp16 products miss the "
                                "1e-3 parity bar on the 50-layer stack without GroupNorm (4e-3 of the output scale); use set_conv_precision('fp32')")
+        if _sn.get_conv_precision() == "f16":
+            if self.backbone_name == "resnet50":
+                raise RuntimeError("models/semanticFCN with the resnet50 backbone does not run with conv precision 'f16': the half-precision "
+                                   "storage path covers the BasicBlock backbones (resnet18 / resnet34) only; use set_conv_precision('fp32')")
+            return self._forward_h8(x, meta)
         x1, x2, x3, x4 = self._encode(x, meta)
         f4 = self._conv("fpn4", self.fpn_block4[0], self.fpn_block4[1], [ConvSource(x4)])
         f3 = self._conv("fpn3", self.fpn_block3[0], self.fpn_block3[1], [ConvSource(x3)])

@@ -131,9 +131,11 @@ def pack_conv_weight_h8(weight: torch.Tensor) -> torch.Tensor:
 def conv2d_h8(srcs: Sequence[H8Source], wpack: torch.Tensor, cin: int, cout: int, ksize: int, dil: int, pad: int,
               bias: Optional[torch.Tensor] = None, slope: Optional[float] = None,
               bn_a: Optional[torch.Tensor] = None, bn_b: Optional[torch.Tensor] = None,
-              resid: Optional[torch.Tensor] = None, out_f32_nchw: bool = False) -> torch.Tensor:
+              resid: Optional[torch.Tensor] = None, out_f32_nchw: bool = False, act_after_resid: bool = False) -> torch.Tensor:
     """out = [resid +] bn_a * leaky(conv(cat(srcs * scale)) + bias) + bn_b  (slu_conv2d_h8_fwd).
-    `cin` = real input channels the weight was packed with (only the last source may carry pad channels)."""
+    `cin` = real input channels the weight was packed with (only the last source may carry pad channels).
+    act_after_resid: out = leaky(conv + bias + resid) instead (a BasicBlock's second conv): 3x3 / dil 1 / pad 1 with a residual and a slope
+    only; any other layer raises (SLU_EUNSUPPORTED)."""
     lib = _lib.load()
     if not 1 <= len(srcs) <= _lib.MAX_SRC:
         raise RuntimeError(f"conv2d_h8: 1..{_lib.MAX_SRC} sources supported, got {len(srcs)}")
@@ -195,6 +197,7 @@ def conv2d_h8(srcs: Sequence[H8Source], wpack: torch.Tensor, cin: int, cout: int
     d.has_act, d.slope = (0, 0.0) if slope is None else (1, float(slope))
     d.bn_a, d.bn_b, d.resid, d.out = _ptr(bn_a), _ptr(bn_b), _ptr(resid), out.data_ptr()
     d.out_f32_nchw = 1 if out_f32_nchw else 0
+    d.act_after_resid = 1 if act_after_resid else 0
     if ops.TIMING is None:
         check(lib.slu_conv2d_h8_fwd(C.byref(d), _stream()), "slu_conv2d_h8_fwd")
         return out
@@ -426,3 +429,85 @@ def pixel_shuffle_h8(x: torch.Tensor, scale_in: Optional[torch.Tensor] = None, s
     check(_lib.load().slu_pixel_shuffle_h8(x.data_ptr(), _ptr(scale_in), _ptr(scale_out), y.data_ptr(), n, g, h, w, _stream()),
           "slu_pixel_shuffle_h8")
     return y
+
+
+def maxpool3s2_h8(x: torch.Tensor) -> torch.Tensor:
+    """nn.MaxPool2d(3, 2, 1) (slu_maxpool3s2_h8): padding is -inf, pad channels stay 0."""
+    _req_h8(x, "x")
+    n, g, h, w, _ = x.shape
+    y = torch.empty((n, g, (h + 1) // 2, (w + 1) // 2, 8), dtype=torch.float16, device=x.device)
+    check(_lib.load().slu_maxpool3s2_h8(x.data_ptr(), y.data_ptr(), n, g, h, w, _stream()), "slu_maxpool3s2_h8")
+    return y
+
+
+def space_to_depth2_h8(x: torch.Tensor, meta: Optional[torch.Tensor] = None, channels: Optional[int] = None, factor: int = 1,
+                       phase00: bool = True):
+    """(y, y00) = slu_space_to_depth2_h8: y [N, 4 G, H/2, W/2, 8] phase-major (channel (2 p + q) 8 G + c = x[c, 2 y + p, 2 x + q]) and, with
+    phase00, y00 [N, G, H/2, W/2, 8] = phase (0, 0) alone (else None).  meta: fp32 [N, m, factor H, factor W] whose nearest 1 / factor
+    down-sampling replaces the last m of x's `channels` (default 8 G) real channels on the way."""
+    _req_h8(x, "x")
+    n, g, h, w, _ = x.shape
+    if h % 2 or w % 2:
+        raise RuntimeError(f"space_to_depth2_h8: H and W must be even, got {(h, w)}")
+    c = 8 * g if channels is None else int(channels)
+    m = 0
+    if meta is not None:
+        _req(meta, "meta")
+        if factor not in (1, 2, 4, 8):
+            raise RuntimeError(f"space_to_depth2_h8: factor {factor} is not one of 1, 2, 4, 8")
+        if meta.dim() != 4 or (meta.shape[0], meta.shape[2], meta.shape[3]) != (n, factor * h, factor * w):
+            raise RuntimeError(f"meta: expected [{n}, m, {factor * h}, {factor * w}], got {tuple(meta.shape)}")
+        m = meta.shape[1]
+        if not (8 * (g - 1) < c <= 8 * g and 0 < m <= c):
+            raise RuntimeError(f"space_to_depth2_h8: {m} meta channels / {c} channels do not fit {g} blocks")
+    y = torch.empty((n, 4 * g, h // 2, w // 2, 8), dtype=torch.float16, device=x.device)
+    y00 = torch.empty((n, g, h // 2, w // 2, 8), dtype=torch.float16, device=x.device) if phase00 else None
+    check(_lib.load().slu_space_to_depth2_h8(x.data_ptr(), _ptr(meta), m, c, int(factor), y.data_ptr(), _ptr(y00), n, g, h, w, _stream()),
+          "slu_space_to_depth2_h8")
+    return y, y00
+
+
+def attention_row_h8(tv: torch.Tensor, w_a: torch.Tensor, b_a: torch.Tensor) -> torch.Tensor:
+    """out = v * softmax_W(b_a + sum_c w_a[c] tanh(t[c])) with (t, v) = the two channel halves of tv [N, 2 C / 8, H, W, 8]
+    (slu_attention_row_h8); w_a fp32 [C], b_a fp32 [1]."""
+    _req_h8(tv, "tv")
+    n, g2, h, w, _ = tv.shape
+    if g2 % 2:
+        raise RuntimeError(f"attention_row_h8: {g2} blocks are not two equal halves")
+    c = 4 * g2
+    _req(w_a, "w_a")
+    _req(b_a, "b_a")
+    if w_a.numel() != c or b_a.numel() != 1:
+        raise RuntimeError(f"attention_row_h8: expected w_a of {c} and b_a of 1 element, got {w_a.numel()} and {b_a.numel()}")
+    out = torch.empty((n, g2 // 2, h, w, 8), dtype=torch.float16, device=tv.device)
+    check(_lib.load().slu_attention_row_h8(tv.data_ptr(), w_a.data_ptr(), b_a.data_ptr(), out.data_ptr(), n, c, h, w, _stream()),
+          "slu_attention_row_h8")
+    return out
+
+
+def depth_to_space_h8(y: torch.Tensor, s: int, out: Optional[torch.Tensor] = None, g_off: int = 0, elu_plus_one: bool = False,
+                      classes: Optional[int] = None) -> torch.Tensor:
+    """Two forms.  Plain (slu_depth_to_space_h8): y [N, s s Cout / 8, H, W, 8] with channels ordered (i, j, cout), Cout % 8 == 0, s in 2 / 4 / 8
+    -> blocks [g_off, g_off + Cout / 8) of `out` [N, Gtot, s H, s W, 8] (allocated with exactly Cout / 8 blocks when None).
+    elu_plus_one (slu_depth_to_space2_elu_h8, s = 2): y [N, ceil(4 classes / 8), H, W, 8] with channels ordered (class, i, j) -> fp32 NCHW
+    [N, classes, 2 H, 2 W] = elu(pixel_shuffle(y)) + 1."""
+    _req_h8(y, "y")
+    n, g, h, w, _ = y.shape
+    lib = _lib.load()
+    if elu_plus_one:
+        if s != 2 or classes is None or (4 * classes + 7) // 8 != g or out is not None:
+            raise RuntimeError(f"depth_to_space_h8: the ELU + 1 form takes s = 2 and `classes` matching the {g} blocks of y")
+        res = torch.empty((n, classes, 2 * h, 2 * w), dtype=torch.float32, device=y.device)
+        check(lib.slu_depth_to_space2_elu_h8(y.data_ptr(), res.data_ptr(), n, int(classes), h, w, _stream()), "slu_depth_to_space2_elu_h8")
+        return res
+    if s not in (2, 4, 8) or g % (s * s):
+        raise RuntimeError(f"depth_to_space_h8: {g} blocks are not s * s = {s * s} whole groups (s in 2, 4, 8)")
+    go = g // (s * s)
+    if out is None:
+        out = torch.empty((n, go, s * h, s * w, 8), dtype=torch.float16, device=y.device)
+    _req_h8(out, "out")
+    if (out.shape[0], out.shape[2], out.shape[3]) != (n, s * h, s * w) or g_off < 0 or g_off + go > out.shape[1]:
+        raise RuntimeError(f"out: blocks [{g_off}, {g_off + go}) of {tuple(out.shape)} do not take {(n, go, s * h, s * w, 8)}")
+    check(lib.slu_depth_to_space_h8(y.data_ptr(), out.data_ptr(), n, 8 * go, int(s), h, w, out.shape[1], int(g_off), _stream()),
+          "slu_depth_to_space_h8")
+    return out

@@ -62,7 +62,7 @@ if a.model == "opt":
 model = randomize_bn_(SemanticNetworkWithFPN(a.backbone, 2, 6, num_classes=20), 3).eval().to(dev)
 x, meta = torch.randn(a.batch, 2, 128, 2048, device=dev), torch.randn(a.batch, 6, 128, 2048, device=dev)
 out = {}
-for prec in ("fp32", "f16x3"):
+for prec in ("fp32", "f16x3", "f16"):      # "f16": fp16 storage (the h8 path)
     sn.set_conv_precision(prec)
     with torch.no_grad():
         for _ in range(10):
