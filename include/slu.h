@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SLU_ABI_VERSION 35
+#define SLU_ABI_VERSION 36
 
 #define SLU_OK            0
 #define SLU_EINVAL       -1   /* null pointer / non-positive size / inconsistent descriptor   */
@@ -403,6 +403,30 @@ int slu_depth_to_space_h8(const void* y, void* out, int N, int Cout, int s, int 
  * 4 `classes` sub-pixel channels ordered (class, i, j): out[n][c][2 h + i][2 w + j] = elu(y[n][4 c + 2 i + j][h][w]) + 1;
  * y = h8 [N][ceil(4 classes / 8)][H][W][8], out fp32 NCHW [N][classes][2 H][2 W] */
 int slu_depth_to_space2_elu_h8(const void* y, float* out, int N, int classes, int H, int W, slu_stream_t stream);
+
+/* ---- h8 forms of what `semanticFCN_opt` puts between its convs (baselines/Reichert/semanticFCN_opt.py): fpn_opt_h8.hip -------------
+ * All tensors h8 [N][G][H][W][8] fp16 with zero pad channels and 16-byte aligned bases; fp32 arithmetic (fp64 sums in GroupNorm), every
+ * stored value rounded to fp16 once; no float atomics: two runs of a call give the same bits.
+ * slu_bilinear_upsample_h8: F.interpolate(x, scale_factor = s, mode = 'bilinear', align_corners = False) (UpsampleBlock :24-27):
+ *   x [N][G][H][W][8] -> y [N][G][s H][s W][8]; source coordinate (dst + 0.5) / s - 0.5 clamped at 0, upper neighbour clamped at H - 1 /
+ *   W - 1; s in {2, 4, 8} (SLU_EINVAL otherwise).
+ * slu_groupnorm_stats_h8: mean and 1 / sqrt(var + eps) (biased variance) per (image, group) of the STORED fp16 values of x [N][ceil(C/8)][HW][8]
+ *   -> mean / rstd fp32 [N groups].  The values and their squares are summed exactly in fp64 (per-workgroup partials in `workspace`,
+ *   slu_groupnorm_stats_h8_workspace_bytes(N, C, HW) bytes, 8-byte aligned; then one wave per group in a fixed order), so the variance
+ *   survives |mean| >> std.  C / groups in {1, 2, 4, 8}: a group lies inside one record (every GroupNorm resnet18 / resnet34 build is 1, 2
+ *   or 4 wide); anything else is SLU_EUNSUPPORTED.
+ * slu_groupnorm_apply_h8: out[n][g_off + g] = (x - mean) * rstd * gamma[c] + beta[c], max(., 0) if relu, into blocks [g_off, g_off + ceil(C/8))
+ *   of out [N][Gtot][HW][8] (the three UpsampleBlocks share one buffer, as slu_depth_to_space_h8's callers); gamma / beta fp32 [C] or NULL;
+ *   pad channels of the last block are written 0; out == x is allowed when Gtot == ceil(C/8) and g_off == 0 (SLU_EINVAL otherwise).
+ * slu_spatial_softmax_gate_h8: SpatialAttention's gate (:80-85): w = softmax(score[n] over H W) in fp32, out = x w + x.  score fp32 [N][HW]
+ *   (the fp32 NCHW output of the `score` conv); stats fp32 [2 N] scratch (max, 1 / sum), reduced by one workgroup per image. */
+int slu_bilinear_upsample_h8(const void* x, void* y, int N, int G, int H, int W, int s, slu_stream_t stream);
+size_t slu_groupnorm_stats_h8_workspace_bytes(int N, int C, int HW);
+int slu_groupnorm_stats_h8(const void* x, int N, int C, int HW, int groups, float eps, float* mean, float* rstd, void* workspace,
+                           slu_stream_t stream);
+int slu_groupnorm_apply_h8(const void* x, const float* mean, const float* rstd, const float* gamma, const float* beta, int relu, void* out, int N,
+                           int C, int HW, int groups, int Gtot, int g_off, slu_stream_t stream);
+int slu_spatial_softmax_gate_h8(const void* x, const float* score, float* stats, void* out, int N, int C, int HW, slu_stream_t stream);
 
 /* Fused tail of a SalsaNext block on the h8 path (ResBlock.conv4 + conv5, SalsaNext.py:59-68; UpBlock.conv3 + conv4, :157-167):
  *   a3  = bnA_a * actA(conv2x2_dil2_pad1(a2) + biasA) + bnA_b          (kept on chip, rounded to fp16 like the stored tensor would be)

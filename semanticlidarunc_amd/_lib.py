@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-ABI_VERSION = 35
+ABI_VERSION = 36
 MAX_SRC = 3
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libslu_hip.so")
@@ -171,6 +171,12 @@ SIGNATURES = {
     "slu_attention_row_h8": (C.c_int, [C.c_void_p, c_f32p, c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_stream]),
     "slu_depth_to_space_h8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_stream]),
     "slu_depth_to_space2_elu_h8": (C.c_int, [C.c_void_p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_stream]),
+    "slu_bilinear_upsample_h8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_stream]),
+    "slu_groupnorm_stats_h8_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "slu_groupnorm_stats_h8": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, c_f32p, c_f32p, C.c_void_p, c_stream]),
+    "slu_groupnorm_apply_h8": (C.c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, c_stream]),
+    "slu_spatial_softmax_gate_h8": (C.c_int, [C.c_void_p, c_f32p, c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, c_stream]),
     "slu_dirichlet_head": (C.c_int, [c_f32p, C.c_longlong, c_f32p, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, c_f32p,
                                      c_f32p, c_f32p, c_f32p, c_i64p, c_stream]),
     "slu_dirichlet_uncertainty": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_float, c_f32p, c_f32p, c_f32p, c_i64p, c_stream]),

@@ -396,13 +396,18 @@ class SemanticNetworkWithFPN(nn.Module):
         p = self._prep(name + ".ijc", make, ct.weight, ct.bias)
         _h8.depth_to_space_h8(self._run_h8(p, [x], relu=False), s, ups, g_off)
 
-    def _forward_h8(self, x, meta):
+    def _encode_h8(self, x, meta):
+        """(x1, x2, x3, x4) as h8: stem + the four BasicBlock stages with the multi-scale meta injection (`_encode` on the h8 path)."""
         xs = self._run_h8(self._p_conv("stem", self.backbone.conv1, None), [_h8.to_h8(torch.cat([x, meta], 1))])      # bn1 is skipped by the reference stem
         mm = meta if self.multi_scale_meta else None
         x1 = self._stage_h8("layer1", self.layer1, _h8.maxpool3s2_h8(xs), None, 1)
         x2 = self._stage_h8("layer2", self.layer2, x1, mm, 2)
         x3 = self._stage_h8("layer3", self.layer3, x2, mm, 4)
         x4 = self._stage_h8("layer4", self.layer4, x3, mm, 8)
+        return x1, x2, x3, x4
+
+    def _forward_h8(self, x, meta):
+        x1, x2, x3, x4 = self._encode_h8(x, meta)
         f4 = self._run_h8(self._p_conv("fpn4", self.fpn_block4[0], self.fpn_block4[1]), [x4])
         f3 = self._run_h8(self._p_conv("fpn3", self.fpn_block3[0], self.fpn_block3[1]), [x3])
         f2 = self._run_h8(self._p_conv("fpn2", self.fpn_block2[0], self.fpn_block2[1]), [x2])

@@ -13,6 +13,8 @@ Same encoder as `fpn.SemanticNetworkWithFPN` (shared code); the head differs:
 Contract kept: constructor keywords, `forward(x, meta) -> logits [B,num_classes,H,W]`, `state_dict` keys / shapes of the reference
 class (checked against it in tools/gen_golden_r02.py), genuine `nn.Dropout2d` / `nn.GroupNorm` children.  Inference: folded launches
 (`_forward`); training / any gradient: one autograd node per layer (`_forward_train_opt`), ResNet and EfficientNetV2 encoders alike.
+Conv precision "f16" (resnet18 / resnet34, inference): fp16 storage throughout -- h8 convs with `slu_bilinear_upsample_h8`,
+`slu_groupnorm_stats_h8` / `slu_groupnorm_apply_h8` and `slu_spatial_softmax_gate_h8` between them (`_pyramid_h8`, `_decoder_h8`).
 """
 from __future__ import annotations
 
@@ -23,10 +25,17 @@ import torch
 import torch.nn as nn
 
 from . import effnet as _eff
+from . import h8 as _h8
 from . import ops
+from . import salsanext as _sn
 from .fpn import SemanticNetworkWithFPN as _FPNBase
 from .fpn import _RESNETS
 from .ops import ConvSource
+
+
+def _head_mc_h8_fits(blocks: int, classes: int, hw: int) -> bool:
+    """What slu_head_mc_h8 takes (include/slu.h): 16 / 32 / 64 head input channels, at most 32 classes, H W a multiple of 32."""
+    return blocks in (2, 4, 8) and classes <= 32 and hw % 32 == 0
 
 
 class UpsampleBlock(nn.Module):
@@ -366,10 +375,89 @@ class SemanticNetworkWithFPN(_FPNBase):
         y = self._upsample_block("dec_up", d[6], y)
         return self._conv("dec_out", d[7], None, [ConvSource(y)], act="none")
 
+    # ---------------- half-precision storage path (conv precision "f16"): h8 tensors [N, G, H, W, 8] fp16 throughout ----------------
+    def _use_h8(self) -> bool:
+        """Conv precision "f16" selects the h8 route; it covers the BasicBlock encoders only."""
+        if _sn.get_conv_precision() != "f16":
+            return False
+        if self.is_effnet or self.backbone_name == "resnet50":
+            raise RuntimeError(f"semanticFCN_opt with the {self.backbone_name} backbone does not run with conv precision 'f16': the half-precision "
+                               "storage path covers the BasicBlock backbones (resnet18 / resnet34) only; use set_conv_precision('fp32')")
+        return True
+
+    @staticmethod
+    def _gn_h8(y, gn: nn.GroupNorm, out=None, g_off=0):
+        """GroupNorm + ReLU of an h8 tensor: statistics, then apply in place (or into blocks [g_off, ...) of `out`)."""
+        stats = _h8.groupnorm_stats_h8(y, gn.num_channels, gn.num_groups, gn.eps)
+        return _h8.groupnorm_apply_h8(y, gn.num_channels, gn.num_groups, stats, gn.weight.detach(), gn.bias.detach(), True,
+                                      y if out is None else out, g_off)
+
+    def _head_h8(self, name, conv: nn.Conv2d, x):
+        """A 1x1 conv of an h8 tensor with fp32 NCHW output and no activation (the `score` conv of an attention, the logits head)."""
+        p = self._p_conv(name, conv, None)
+        return _h8.conv2d_h8([_h8.H8Source(x)], p.wpack, p.cin, p.cout, p.k, p.dil, p.pad, bias=p.bias, out_f32_nchw=True)
+
+    def _spatial_attention_h8(self, name, att: SpatialAttention, x):
+        hid = self._run_h8(self._p_conv(name + ".proj", att.proj, None), [x])
+        return _h8.spatial_softmax_gate_h8(x, self._head_h8(name + ".score", att.score, hid))
+
+    def _upsample_conv_h8(self, name, up: UpsampleBlock, x):
+        """UpsampleBlock up to its raw conv output: bilinear kernel, then the 3x3 conv with no bias and no activation."""
+        if up.mode != "bilinear":
+            raise NotImplementedError("UpsampleBlock: only mode='bilinear' (what the reference constructs) runs on the HIP path")
+        return self._run_h8(self._p_conv(name, up.block[0], None), [_h8.bilinear_upsample_h8(x, up.scale)], relu=False)
+
+    def _pyramid_h8(self, x, meta):
+        """`_pyramid` on the h8 path -> (f1, ups): the two sources of the first decoder conv, the three UpsampleBlocks in block slices of one
+        buffer (cat([x2, x3, x4]) of the reference's forward)."""
+        x1, x2, x3, x4 = self._encode_h8(x, meta)
+        f4 = self._run_h8(self._p_conv("fpn4", self.fpn_block4[0], self.fpn_block4[1]), [x4])
+        f3 = self._run_h8(self._p_conv("fpn3", self.fpn_block3[0], self.fpn_block3[1]), [x3])
+        f2 = self._run_h8(self._p_conv("fpn2", self.fpn_block2[0], self.fpn_block2[1]), [x2])
+        f1 = self._run_h8(self._p_conv("fpn1", self.fpn_block1[0], self.fpn_block1[1]), [x1])
+        if self.attention:
+            f4, f3 = self._spatial_attention_h8("att4", self.attention4, f4), self._spatial_attention_h8("att3", self.attention3, f3)
+            f2, f1 = self._spatial_attention_h8("att2", self.attention2, f2), self._spatial_attention_h8("att1", self.attention1, f1)
+        blocks = (("up2", self.upsample_layer_x2, f2), ("up3", self.upsample_layer_x3, f3), ("up4", self.upsample_layer_x4, f4))
+        chans = [up.block[0].out_channels for _, up, _ in blocks]
+        if any(c % 8 for c in chans):
+            raise RuntimeError(f"semanticFCN_opt on the h8 path: UpsampleBlock widths {chans} are not whole blocks of 8 channels")
+        ups = torch.empty((f1.shape[0], sum(chans) // 8, f1.shape[2], f1.shape[3], 8), dtype=torch.float16, device=f1.device)
+        g_off = 0
+        for (name, up, f), c in zip(blocks, chans):
+            self._gn_h8(self._upsample_conv_h8(name, up, f), up.block[1], ups, g_off)
+            g_off += c // 8
+        return f1, ups
+
+    def _decoder_h8(self, f1, ups, s, passes: int = 0, raw_head_input: bool = False):
+        """`_decoder` on the h8 path: the dropout multipliers are the first conv's per-source scales (each rounded to fp16, the product rounded
+        once: slu.h); passes = T > 0: both sources are batch-broadcast and the conv writes T * B images.  Returns fp32 NCHW logits, or with
+        raw_head_input the h8 output of the last UpsampleBlock's conv (before its GroupNorm)."""
+        b = f1.shape[0]
+        c1 = 8 * f1.shape[1]
+        d = self.decoder_semantic
+        if c1 + 8 * ups.shape[1] != d[0].in_channels:
+            raise RuntimeError("semanticFCN_opt on the h8 path: the pyramid's channels are not whole blocks of 8")
+        sc = (None, None) if s is None else (s[:, :c1].contiguous(), s[:, c1:].contiguous())
+        nb = b if passes else 0
+        p = self._p_conv("dec0", d[0], None)
+        y = _h8.conv2d_h8([_h8.H8Source(f1, sc[0], nb), _h8.H8Source(ups, sc[1], nb)], p.wpack, p.cin, p.cout, p.k, p.dil, p.pad, bias=p.bias,
+                          n_out=passes * b if passes else None)
+        y = self._gn_h8(y, d[1])
+        y = self._gn_h8(self._run_h8(self._p_conv("dec1", d[3], None), [y], relu=False), d[4])
+        y = self._upsample_conv_h8("dec_up", d[6], y)
+        if raw_head_input:
+            return y
+        return self._head_h8("dec_out", d[7], self._gn_h8(y, d[6].block[1]))
+
     def _forward(self, x, meta_channel, drop_scale):
         x, meta = self._check_inputs(x, meta_channel)
         if self._wants_autograd(x, meta):
             return self._forward_train_opt(x, meta, drop_scale)
+        if self._use_h8():
+            f1, ups = self._pyramid_h8(x, meta)
+            s = self._pyramid_dropout(f1.shape[0], self.decoder_semantic[0].in_channels, f1.device, drop_scale)
+            return self._decoder_h8(f1, ups, s)
         f1, u2, u34 = self._pyramid(x, meta)
         # cat([x1, x2, x3, x4]) -> dropout_pyramid -> decoder conv: three sources (x1 | x2 | x3 + x4 share a buffer), multipliers per source
         s = self._pyramid_dropout(f1.shape[0], f1.shape[1] + u2.shape[1] + u34.shape[1], f1.device, drop_scale)
@@ -385,6 +473,10 @@ class SemanticNetworkWithFPN(_FPNBase):
         t = int(T)
         if t < 1:
             raise RuntimeError("forward_mc: T must be at least 1")
+        if self._use_h8():
+            f1, ups = self._pyramid_h8(x, meta)
+            s = self._pyramid_dropout(t * f1.shape[0], self.decoder_semantic[0].in_channels, f1.device, scale)
+            return self._decoder_h8(f1, ups, s, passes=t, raw_head_input=raw_head_input)
         f1, u2, u34 = self._pyramid(x, meta)
         s = self._pyramid_dropout(t * f1.shape[0], f1.shape[1] + u2.shape[1] + u34.shape[1], f1.device, scale)
         return self._decoder(f1, u2, u34, s, passes=t, raw_head_input=raw_head_input)
@@ -399,7 +491,8 @@ class SemanticNetworkWithFPN(_FPNBase):
         return self._mc_shared(x, meta_channel, T, scale, False)
 
     def mc_fused_ok(self, x, meta_channel, T: int) -> bool:
-        """slu_head_mc_f32 covers this model's head: eval-mode inference on fp32 GPU inputs, at most 32 classes and 128 head input channels."""
+        """slu_head_mc_f32 covers this model's head: eval-mode inference on fp32 GPU inputs, at most 32 classes and 128 head input channels
+        (under conv precision "f16" mc_predict_fused takes slu_head_mc_h8 or, where that does not fit, the unfused reduction)."""
         if self.training or not all(isinstance(t, torch.Tensor) and t.dim() == 4 and t.is_cuda and t.dtype == torch.float32 for t in (x, meta_channel)):
             return False
         head = self.decoder_semantic[7]
@@ -409,9 +502,20 @@ class SemanticNetworkWithFPN(_FPNBase):
     def mc_predict_fused(self, x, meta_channel, T: int, eps: float = 1e-12, scale: Optional[torch.Tensor] = None):
         """(p_bar, H_norm, MI_norm, preds) of T stochastic passes: the shared pyramid and the decoder up to the last UpsampleBlock's raw conv
         output, then its GroupNorm statistics, then GroupNorm apply + ReLU + the 1x1 head + the MC reduction in one launch
-        (csrc/head_mc_f32.hip): neither the normalised tensor nor the T*B logit maps are written.  Call under utils.mc_dropout.dropout_sampling."""
+        (csrc/head_mc_f32.hip): neither the normalised tensor nor the T*B logit maps are written.  Under conv precision "f16": GroupNorm + ReLU in
+        place on the h8 tensor, then head + reduction in one launch (csrc/head_mc_h8.hip).  Call under utils.mc_dropout.dropout_sampling."""
         y = self._mc_shared(x, meta_channel, T, scale, True)
         gn, head = self.decoder_semantic[6].block[1], self.decoder_semantic[7]
+        if y.dtype == torch.float16:
+            # the h8 route: GroupNorm + ReLU in place, then the 1x1 head + the MC reduction in one launch (slu_head_mc_h8: 16 / 32 / 64 input
+            # channels, H W a multiple of 32); any other shape: the head conv's fp32 logits through the reduction kernel
+            y = self._gn_h8(y, gn)
+            t = int(T)
+            if _head_mc_h8_fits(y.shape[1], head.out_channels, y.shape[2] * y.shape[3]):
+                p = self._p_conv("dec_out", head, None)
+                return _h8.head_mc_h8(y, p.wpack, p.bias, head.out_channels, t, y.shape[0] // t, eps)
+            logits = self._head_h8("dec_out", head, y)
+            return ops.mc_reduce(logits.view(t, logits.shape[0] // t, *logits.shape[1:]), eps)
         stats = ops.groupnorm_stats(y, gn.num_groups, gn.eps)
         return ops.head_mc_f32(y, head.weight.detach(), None if head.bias is None else head.bias.detach(), int(T), y.shape[0] // int(T), eps,
                                gn_stats=stats, gn_groups=gn.num_groups, gn_gamma=gn.weight.detach(), gn_beta=gn.bias.detach(), relu=True)

@@ -131,16 +131,22 @@ def pack_conv_weight_h8(weight: torch.Tensor) -> torch.Tensor:
 def conv2d_h8(srcs: Sequence[H8Source], wpack: torch.Tensor, cin: int, cout: int, ksize: int, dil: int, pad: int,
               bias: Optional[torch.Tensor] = None, slope: Optional[float] = None,
               bn_a: Optional[torch.Tensor] = None, bn_b: Optional[torch.Tensor] = None,
-              resid: Optional[torch.Tensor] = None, out_f32_nchw: bool = False, act_after_resid: bool = False) -> torch.Tensor:
+              resid: Optional[torch.Tensor] = None, out_f32_nchw: bool = False, act_after_resid: bool = False,
+              n_out: Optional[int] = None) -> torch.Tensor:
     """out = [resid +] bn_a * leaky(conv(cat(srcs * scale)) + bias) + bn_b  (slu_conv2d_h8_fwd).
     `cin` = real input channels the weight was packed with (only the last source may carry pad channels).
     act_after_resid: out = leaky(conv + bias + resid) instead (a BasicBlock's second conv): 3x3 / dil 1 / pad 1 with a residual and a slope
-    only; any other layer raises (SLU_EUNSUPPORTED)."""
+    only; any other layer raises (SLU_EUNSUPPORTED).
+    n_out: the number of output images, so that EVERY source may be batch-broadcast (nbatch): the stacked passes of an MC-dropout
+    evaluation read one shared set of images.  Default: the batch of the first source, which then must hold it in full."""
     lib = _lib.load()
     if not 1 <= len(srcs) <= _lib.MAX_SRC:
         raise RuntimeError(f"conv2d_h8: 1..{_lib.MAX_SRC} sources supported, got {len(srcs)}")
     d = ConvH8Desc()
-    n = h = w = None
+    n = None if n_out is None else int(n_out)
+    if n is not None and n <= 0:
+        raise RuntimeError(f"conv2d_h8: n_out={n_out} is not a positive number of images")
+    h = w = None
     gin = 0
     keep = []
     for i, s in enumerate(srcs):
@@ -152,12 +158,14 @@ def conv2d_h8(srcs: Sequence[H8Source], wpack: torch.Tensor, cin: int, cout: int
                 raise RuntimeError("src[0] only may be read through PixelShuffle in place, with whole groups of 64 stored channels")
             sg, sh, sw = sg // 4, 2 * sh, 2 * sw
         if s.nbatch:
-            if i == 0 or sn != s.nbatch or n % sn:
-                raise RuntimeError(f"src[{i}]: a batch-broadcast source must follow a full-batch source and divide N")
+            if n is None or sn != s.nbatch or n % sn:
+                raise RuntimeError(f"src[{i}]: a batch-broadcast source must follow a full-batch source (or n_out be given) and divide N")
             sn = n
         if n is None:
-            n, h, w = sn, sh, sw
-        elif (sn, sh, sw) != (n, h, w):
+            n = sn
+        if h is None:
+            h, w = sh, sw
+        if (sn, sh, sw) != (n, h, w):
             raise RuntimeError(f"src[{i}]: spatial/batch size {(sn, sh, sw)} != {(n, h, w)}")
         if s.scale is not None:
             _req(s.scale, f"src[{i}].scale")
@@ -510,4 +518,95 @@ def depth_to_space_h8(y: torch.Tensor, s: int, out: Optional[torch.Tensor] = Non
         raise RuntimeError(f"out: blocks [{g_off}, {g_off + go}) of {tuple(out.shape)} do not take {(n, go, s * h, s * w, 8)}")
     check(lib.slu_depth_to_space_h8(y.data_ptr(), out.data_ptr(), n, 8 * go, int(s), h, w, out.shape[1], int(g_off), _stream()),
           "slu_depth_to_space_h8")
+    return out
+
+
+# ---- what `semanticFCN_opt` puts between its convs (csrc/fpn_opt_h8.hip) ----
+def _timed(name: str, tag: str, flops: float, nbytes: float, launch) -> None:
+    """Run one launch; in measurement mode (ops.TIMING) between HIP events, recorded like the convs."""
+    if ops.TIMING is None:
+        launch()
+        return
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    launch()
+    e1.record()
+    ops.TIMING.append((name, flops, nbytes, e0, e1, nbytes))
+    ops.TIMING_TAGS.append(tag)
+
+
+def bilinear_upsample_h8(x: torch.Tensor, s: int) -> torch.Tensor:
+    """F.interpolate(scale_factor=s, mode='bilinear', align_corners=False) of an h8 tensor, s in 2 / 4 / 8 (slu_bilinear_upsample_h8)."""
+    _req_h8(x, "x")
+    n, g, h, w, _ = x.shape
+    s = int(s)
+    y = torch.empty((n, g, s * h, s * w, 8), dtype=torch.float16, device=x.device)
+    _timed("bilinear_up_h8_kernel", f"N{n} bilinear x{s} {8 * g}ch {h}x{w}", 7.0 * y.numel(), 2.0 * (x.numel() + y.numel()),
+           lambda: check(_lib.load().slu_bilinear_upsample_h8(x.data_ptr(), y.data_ptr(), n, g, h, w, s, _stream()), "slu_bilinear_upsample_h8"))
+    return y
+
+
+def _req_gn(x: torch.Tensor, channels: int, groups: int, what: str):
+    _req_h8(x, "x")
+    n, g, h, w, _ = x.shape
+    c, groups = int(channels), int(groups)
+    if not 8 * (g - 1) < c <= 8 * g or groups < 1 or c % groups:
+        raise RuntimeError(f"{what}: {c} channels in {groups} groups do not fit the {g} blocks of x")
+    return n, g, h, w, c, groups
+
+
+def groupnorm_stats_h8(x: torch.Tensor, channels: int, groups: int, eps: float = 1e-5) -> torch.Tensor:
+    """[2, N * groups] fp32 (mean, rstd) of nn.GroupNorm(groups, channels, eps) over the stored values of an h8 tensor
+    (slu_groupnorm_stats_h8; groups 1, 2, 4 or 8 channels wide, anything else raises)."""
+    n, g, h, w, c, groups = _req_gn(x, channels, groups, "groupnorm_stats_h8")
+    lib = _lib.load()
+    stats = torch.empty((2, n * groups), dtype=torch.float32, device=x.device)
+    ws = torch.empty(max(1, lib.slu_groupnorm_stats_h8_workspace_bytes(n, c, h * w) // 8), dtype=torch.float64, device=x.device)
+    _timed("groupnorm_partial_h8_kernel", f"N{n} GroupNorm({groups}, {c}) statistics {h}x{w}", 3.0 * x.numel(), 2.0 * x.numel(),
+           lambda: check(lib.slu_groupnorm_stats_h8(x.data_ptr(), n, c, h * w, groups, float(eps), stats[0].data_ptr(), stats[1].data_ptr(),
+                                                    ws.data_ptr(), _stream()), "slu_groupnorm_stats_h8"))
+    return stats
+
+
+def groupnorm_apply_h8(x: torch.Tensor, channels: int, groups: int, stats: torch.Tensor, gamma: Optional[torch.Tensor],
+                       beta: Optional[torch.Tensor], relu: bool = False, out: Optional[torch.Tensor] = None, g_off: int = 0) -> torch.Tensor:
+    """(x - mean) * rstd * gamma + beta [-> ReLU] with stats = groupnorm_stats_h8(x, channels, groups), into blocks [g_off, g_off + G) of `out`
+    ([N, Gtot, H, W, 8]; a new tensor of G blocks when None; `out is x`: in place).  slu_groupnorm_apply_h8."""
+    n, g, h, w, c, groups = _req_gn(x, channels, groups, "groupnorm_apply_h8")
+    _req(stats, "stats")
+    if tuple(stats.shape) != (2, n * groups):
+        raise RuntimeError(f"stats: expected {(2, n * groups)}, got {tuple(stats.shape)}")
+    for t, nme in ((gamma, "gamma"), (beta, "beta")):
+        if t is not None:
+            _req(t, nme)
+            if t.numel() != c:
+                raise RuntimeError(f"{nme}: expected {c} elements, got {t.numel()}")
+    if out is None:
+        out = torch.empty_like(x)
+    _req_h8(out, "out")
+    g_off = int(g_off)
+    if (out.shape[0], out.shape[2], out.shape[3]) != (n, h, w) or g_off < 0 or g_off + g > out.shape[1]:
+        raise RuntimeError(f"out: blocks [{g_off}, {g_off + g}) of {tuple(out.shape)} do not take {(n, g, h, w, 8)}")
+    if out.data_ptr() == x.data_ptr() and (out.shape[1] != g or g_off):
+        raise RuntimeError("groupnorm_apply_h8: in place only as the whole tensor")
+    _timed("groupnorm_apply_h8_kernel", f"N{n} GroupNorm({groups}, {c}) apply{' + ReLU' if relu else ''} {h}x{w}", 3.0 * x.numel(), 4.0 * x.numel(),
+           lambda: check(_lib.load().slu_groupnorm_apply_h8(x.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(), _ptr(gamma), _ptr(beta),
+                                                            1 if relu else 0, out.data_ptr(), n, c, h * w, groups, out.shape[1], g_off, _stream()),
+                         "slu_groupnorm_apply_h8"))
+    return out
+
+
+def spatial_softmax_gate_h8(x: torch.Tensor, score: torch.Tensor) -> torch.Tensor:
+    """x * softmax(score over H * W) + x (SpatialAttention of semanticFCN_opt): x h8 [N, G, H, W, 8], score fp32 [N, 1, H, W]
+    (slu_spatial_softmax_gate_h8)."""
+    _req_h8(x, "x")
+    _req(score, "score")
+    n, g, h, w, _ = x.shape
+    if tuple(score.shape) != (n, 1, h, w):
+        raise RuntimeError(f"spatial_softmax_gate_h8: score [N, 1, H, W] = {(n, 1, h, w)} expected, got {tuple(score.shape)}")
+    stats = torch.empty(2 * n, dtype=torch.float32, device=x.device)
+    out = torch.empty_like(x)
+    _timed("spatial_gate_h8_kernel", f"N{n} softmax(H W) gate {8 * g}ch {h}x{w}", 2.0 * x.numel(), 4.0 * x.numel() + 8.0 * score.numel(),
+           lambda: check(_lib.load().slu_spatial_softmax_gate_h8(x.data_ptr(), score.data_ptr(), stats.data_ptr(), out.data_ptr(), n, 8 * g, h * w,
+                                                                 _stream()), "slu_spatial_softmax_gate_h8"))
     return out

@@ -1,8 +1,10 @@
 #!/usr/bin/env python
 """Single-pass FPN inference timing at the reference's own self-benchmark shape (src/models/semanticFCN.py:381-395:
 1 x (2 + 6) x 128 x 2048, median of CUDA-event timings).  python tools/fpn_bench.py [--backbone resnet18] [--batch 1]
+--model opt [--precision fp32|f16x3|f16]: one forward of `semanticFCN_opt` at the same shape, eager and replayed from a HIP graph.
 --model opt --mc T: the MC-dropout evaluation step (utils.mc_dropout.mc_predict, T passes) of `semanticFCN_opt` at B x (2 + 6) x 64 x 2048,
-three ways: stacked (every pass runs the whole network), shared (pyramid once, fpn_opt.forward_mc) and shared + fused (slu_head_mc_f32)."""
+three ways: stacked (every pass runs the whole network), shared (pyramid once, fpn_opt.forward_mc) and shared + fused (slu_head_mc_f32, or
+slu_head_mc_h8 with --precision f16)."""
 import argparse
 import json
 import os
@@ -22,7 +24,7 @@ ap.add_argument("--batch", type=int, default=1)
 ap.add_argument("--iters", type=int, default=100)
 ap.add_argument("--model", default="fpn", choices=["fpn", "opt"])
 ap.add_argument("--mc", type=int, default=0, help="with --model opt: MC-dropout passes T")
-ap.add_argument("--precision", default="fp32", choices=["fp32", "f16x3"], help="with --model opt: conv precision")
+ap.add_argument("--precision", default="fp32", choices=["fp32", "f16x3", "f16"], help="with --model opt: conv precision (f16: fp16 storage, the h8 path)")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 torch.manual_seed(0)
@@ -46,9 +48,29 @@ if a.model == "opt":
     from semanticlidarunc_amd import ops  # noqa: E402
     from semanticlidarunc_amd.fpn_opt import SemanticNetworkWithFPN as OptFPN  # noqa: E402
     from semanticlidarunc_amd.utils.mc_dropout import mc_forward, mc_predict  # noqa: E402
-    if a.mc < 1:
-        ap.error("--model opt needs --mc T")
     model = randomize_bn_(OptFPN(a.backbone, 2, 6, num_classes=20), 3).eval().to(dev)
+    if a.mc < 1:                                   # one forward at the reference's self-benchmark shape
+        x, meta = torch.randn(a.batch, 2, 128, 2048, device=dev), torch.randn(a.batch, 6, 128, 2048, device=dev)
+        sn.set_conv_precision(a.precision)
+        with torch.no_grad():
+            ms = _median_ms(lambda: model(x, meta), a.iters, warmup=10)
+            s_ = torch.cuda.Stream()
+            s_.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(s_):
+                for _ in range(3):
+                    model(x, meta)
+            torch.cuda.current_stream().wait_stream(s_)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                y_static = model(x, meta)
+            eager = model(x, meta)
+            graph.replay()
+            torch.cuda.synchronize()
+            assert torch.equal(eager, y_static), "graph replay differs from the eager forward"
+            gms = _median_ms(graph.replay, a.iters)
+        print(json.dumps({"model": f"semanticFCN_opt/{a.backbone}", "shape": [a.batch, 8, 128, 2048], "precision": a.precision,
+                          "median_ms": round(ms, 3), "scans_per_s": round(a.batch * 1e3 / ms, 1), "hipgraph_median_ms": round(gms, 3)}))
+        sys.exit(0)
     x, meta = torch.randn(a.batch, 2, 64, 2048, device=dev), torch.randn(a.batch, 6, 64, 2048, device=dev)
     sn.set_conv_precision(a.precision)
     ways = {"stacked": lambda: mc_predict(model, [x, meta], T=a.mc, share_prefix=False),
