@@ -311,7 +311,7 @@ int slu_head_mc_f32(const float* x, int T, int B, int Cin, int HW, const float* 
                     const float* gn_beta, int groups, int relu, const float* w, const float* bias, int C, float eps, float* p_bar, float* h_norm,
                     float* mi_norm, int64_t* preds, slu_stream_t stream);
 
-/* ---- fp16 channel-blocked ("h8") inference path: BASELINE.json configs[2],[4] (half-precision storage, fp32 accumulate) -------
+/* ---- fp16 channel-blocked ("h8") inference path: BASELINE.json configs[2],[4] (half-precision storage, fp32 accumulate): conv2d_h8.hip ----
  * Activation layout: x[N][G = ceil(C/8)][H][W][8] fp16, pad channels = 0, base pointers 16-byte aligned.
  * Replaces the same reference arithmetic as slu_conv2d_fwd (SalsaNext.py:25-39,73-109,142-170,197-215) with fp16 operands. */
 typedef struct slu_h8_src {
@@ -367,6 +367,7 @@ int slu_conv2d_h8_fwd(const slu_conv_h8_desc* desc, slu_stream_t stream);
 /* name of the kernel instantiation the call above launches (as rocprofv3 prints it), by the same rules as slu_conv2d_kernel_name
  * (96 bytes hold every name) */
 int slu_conv2d_h8_kernel_name(const slu_conv_h8_desc* desc, char* buf, size_t n);
+/* ---- h8 layout and pooling around the convs: layout_h8.hip ---------------------------------------------------------------------- */
 /* fp32 NCHW <-> h8 (set_model_inputs' tensor on the way in, utils/inputs.py:4-34; scale [N][C] optional) */
 int slu_nchw_to_h8(const float* x, const float* scale, void* y, int N, int C, int H, int W, slu_stream_t stream);
 int slu_h8_to_nchw(const void* x, float* y, int N, int C, int H, int W, slu_stream_t stream);

@@ -11,12 +11,12 @@
 
 namespace {
 
-// One thread per output record, as avgpool3s2_h8_kernel: grid x = (block g, 256 output columns), y = output row, z = image; y and z stride.
+// One thread per output record, as avgpool3s2_h8_kernel (layout_h8.hip): the row walk of h8_common.h over the output image.
 // fp16 max is exact, so the nine taps are compared as packed halves; a tap outside the image is -inf.
 __global__ __launch_bounds__(256) void maxpool3s2_h8_kernel(const uint4* __restrict__ x, uint4* __restrict__ y, int N, int G, int H, int W, int OH,
                                                             int OW, int tiles) {
-  const int g = (int)(blockIdx.x / (unsigned)tiles);
-  const int ox = (int)(blockIdx.x - (unsigned)g * (unsigned)tiles) * 256 + (int)threadIdx.x;
+  const H8Col col = h8_row_col(tiles);
+  const int g = col.g, ox = col.x;
   if (ox >= OW) return;
   const int ix = 2 * ox - 1;
   half8 ninf;
@@ -48,8 +48,8 @@ __global__ __launch_bounds__(256) void space_to_depth2_h8_kernel(const uint4* __
                                                                  uint4* __restrict__ y, uint4* __restrict__ y00, int N, int G, int H, int W,
                                                                  int tiles) {
   const int OH = H >> 1, OW = W >> 1;
-  const int g = (int)(blockIdx.x / (unsigned)tiles);
-  const int ox = (int)(blockIdx.x - (unsigned)g * (unsigned)tiles) * 256 + (int)threadIdx.x;
+  const H8Col col = h8_row_col(tiles);
+  const int g = col.g, ox = col.x;
   if (ox >= OW) return;
   const int c_first = C - m;                                    // first replaced channel
   const bool inject = meta != nullptr && 8 * g + 7 >= c_first && 8 * g < C;
@@ -138,8 +138,10 @@ __global__ __launch_bounds__(256) void attention_row_h8_kernel(const uint4* __re
     const int g = i / W, w = i - g * W;
     const half8 v = __builtin_bit_cast(half8, vrow[(size_t)g * HW + w]);
     const float p = s_p[w] * inv;
-    orow[(size_t)g * HW + w] = make_uint4(pack2((float)v[0] * p, (float)v[1] * p), pack2((float)v[2] * p, (float)v[3] * p),
-                                          pack2((float)v[4] * p, (float)v[5] * p), pack2((float)v[6] * p, (float)v[7] * p));
+    float r[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) r[k] = (float)v[k] * p;
+    orow[(size_t)g * HW + w] = h8_pack8(r);
   }
 }
 
@@ -148,8 +150,8 @@ __global__ __launch_bounds__(256) void attention_row_h8_kernel(const uint4* __re
 __global__ __launch_bounds__(256) void depth_to_space_h8_kernel(const uint4* __restrict__ y, uint4* __restrict__ out, int N, int Go, int s, int H, int W,
                                                                 int Gtot, int g_off, int tiles) {
   const int OH = s * H, OW = s * W;
-  const int g = (int)(blockIdx.x / (unsigned)tiles);
-  const int ox = (int)(blockIdx.x - (unsigned)g * (unsigned)tiles) * 256 + (int)threadIdx.x;
+  const H8Col col = h8_row_col(tiles);
+  const int g = col.g, ox = col.x;
   if (ox >= OW) return;
   const int w = ox / s, j = ox - w * s;
   for (int n = (int)blockIdx.z; n < N; n += (int)gridDim.z)
@@ -165,8 +167,8 @@ __device__ __forceinline__ float elu_plus_one(float v) { return (v > 0.0f ? v : 
 // on consecutive columns, so a wave writes 512 contiguous bytes of each of its four output rows.  Grid as above over the INPUT image.
 __global__ __launch_bounds__(256) void depth_to_space2_elu_h8_kernel(const uint4* __restrict__ y, float* __restrict__ out, int N, int classes, int G, int H,
                                                                      int W, int tiles) {
-  const int g = (int)(blockIdx.x / (unsigned)tiles);
-  const int w = (int)(blockIdx.x - (unsigned)g * (unsigned)tiles) * 256 + (int)threadIdx.x;
+  const H8Col col = h8_row_col(tiles);
+  const int g = col.g, w = col.x;
   if (w >= W) return;
   const size_t OW = 2 * (size_t)W, OH = 2 * (size_t)H;
   for (int n = (int)blockIdx.z; n < N; n += (int)gridDim.z)
@@ -184,26 +186,14 @@ __global__ __launch_bounds__(256) void depth_to_space2_elu_h8_kernel(const uint4
     }
 }
 
-inline bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr) {
-  return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
-}
-
-// grid of the per-record kernels: x = blocks * ceil(cols / 256), y = rows, z = images (both capped at what a grid dimension holds)
-inline bool row_grid(int blocks, int cols, int rows, int n, dim3& grid, int& tiles) {
-  tiles = (cols + 255) / 256;
-  if ((long long)tiles * blocks > 0x7fffffffLL) return false;
-  grid = dim3((unsigned)(tiles * blocks), (unsigned)(rows < 65535 ? rows : 65535), (unsigned)(n < 65535 ? n : 65535));
-  return true;
-}
-
 }  // namespace
 
 extern "C" int slu_maxpool3s2_h8(const void* x, void* y, int N, int G, int H, int W, slu_stream_t stream) {
-  if (!x || !y || N <= 0 || G <= 0 || H <= 0 || W <= 0 || !aligned16(x, y)) return SLU_EINVAL;
+  if (!x || !y || N <= 0 || G <= 0 || H <= 0 || W <= 0 || !h8_aligned16(x, y)) return SLU_EINVAL;
   const int OH = (H + 1) / 2, OW = (W + 1) / 2;
   dim3 grid;
   int tiles;
-  if (!row_grid(G, OW, OH, N, grid, tiles)) return SLU_EUNSUPPORTED;
+  if (!h8_row_grid(G, OW, OH, N, grid, tiles)) return SLU_EUNSUPPORTED;
   hipLaunchKernelGGL(maxpool3s2_h8_kernel, grid, dim3(256), 0, slu_stream(stream), reinterpret_cast<const uint4*>(x), reinterpret_cast<uint4*>(y), N, G,
                      H, W, OH, OW, tiles);
   SLU_CHECK_LAUNCH();
@@ -211,18 +201,18 @@ extern "C" int slu_maxpool3s2_h8(const void* x, void* y, int N, int G, int H, in
 
 extern "C" int slu_space_to_depth2_h8(const void* x, const float* meta, int m, int C, int f, void* y, void* y00, int N, int G, int H, int W,
                                       slu_stream_t stream) {
-  if (!x || !y || N <= 0 || G <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1) || !aligned16(x, y, y00)) return SLU_EINVAL;
+  if (!x || !y || N <= 0 || G <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1) || !h8_aligned16(x, y, y00)) return SLU_EINVAL;
   if (meta && (m <= 0 || m > C || C <= 8 * (G - 1) || C > 8 * G || (f != 1 && f != 2 && f != 4 && f != 8))) return SLU_EINVAL;
   dim3 grid;
   int tiles;
-  if (!row_grid(G, W / 2, H / 2, N, grid, tiles)) return SLU_EUNSUPPORTED;
+  if (!h8_row_grid(G, W / 2, H / 2, N, grid, tiles)) return SLU_EUNSUPPORTED;
   hipLaunchKernelGGL(space_to_depth2_h8_kernel, grid, dim3(256), 0, slu_stream(stream), reinterpret_cast<const uint4*>(x), meta, meta ? m : 0,
                      meta ? C : 0, meta ? f : 1, reinterpret_cast<uint4*>(y), reinterpret_cast<uint4*>(y00), N, G, H, W, tiles);
   SLU_CHECK_LAUNCH();
 }
 
 extern "C" int slu_attention_row_h8(const void* tv, const float* w_a, const float* b_a, void* out, int N, int C, int H, int W, slu_stream_t stream) {
-  if (!tv || !w_a || !b_a || !out || N <= 0 || C <= 0 || (C & 7) || H <= 0 || W <= 0 || !aligned16(tv, out)) return SLU_EINVAL;
+  if (!tv || !w_a || !b_a || !out || N <= 0 || C <= 0 || (C & 7) || H <= 0 || W <= 0 || !h8_aligned16(tv, out)) return SLU_EINVAL;
   if (C > 512 || W > ATT_MAX_W || (long long)N * H > 0x7fffffffLL) return SLU_EUNSUPPORTED;
   hipLaunchKernelGGL(attention_row_h8_kernel, dim3((unsigned)(N * H)), dim3(256), 0, slu_stream(stream), reinterpret_cast<const uint4*>(tv), w_a, b_a,
                      reinterpret_cast<uint4*>(out), C / 8, H, W);
@@ -230,23 +220,23 @@ extern "C" int slu_attention_row_h8(const void* tv, const float* w_a, const floa
 }
 
 extern "C" int slu_depth_to_space_h8(const void* y, void* out, int N, int Cout, int s, int H, int W, int Gtot, int g_off, slu_stream_t stream) {
-  if (!y || !out || N <= 0 || Cout <= 0 || (Cout & 7) || H <= 0 || W <= 0 || !aligned16(y, out)) return SLU_EINVAL;
+  if (!y || !out || N <= 0 || Cout <= 0 || (Cout & 7) || H <= 0 || W <= 0 || !h8_aligned16(y, out)) return SLU_EINVAL;
   if ((s != 2 && s != 4 && s != 8) || g_off < 0 || g_off + Cout / 8 > Gtot) return SLU_EINVAL;
   if ((long long)s * H > 0x7fffffffLL || (long long)s * W > 0x7fffffffLL) return SLU_EUNSUPPORTED;
   dim3 grid;
   int tiles;
-  if (!row_grid(Cout / 8, s * W, s * H, N, grid, tiles)) return SLU_EUNSUPPORTED;
+  if (!h8_row_grid(Cout / 8, s * W, s * H, N, grid, tiles)) return SLU_EUNSUPPORTED;
   hipLaunchKernelGGL(depth_to_space_h8_kernel, grid, dim3(256), 0, slu_stream(stream), reinterpret_cast<const uint4*>(y), reinterpret_cast<uint4*>(out), N,
                      Cout / 8, s, H, W, Gtot, g_off, tiles);
   SLU_CHECK_LAUNCH();
 }
 
 extern "C" int slu_depth_to_space2_elu_h8(const void* y, float* out, int N, int classes, int H, int W, slu_stream_t stream) {
-  if (!y || !out || N <= 0 || classes <= 0 || H <= 0 || W <= 0 || !aligned16(y) || ((uintptr_t)out & 7)) return SLU_EINVAL;
+  if (!y || !out || N <= 0 || classes <= 0 || H <= 0 || W <= 0 || !h8_aligned16(y) || ((uintptr_t)out & 7)) return SLU_EINVAL;
   const int G = (4 * classes + 7) / 8;
   dim3 grid;
   int tiles;
-  if (!row_grid(G, W, H, N, grid, tiles)) return SLU_EUNSUPPORTED;
+  if (!h8_row_grid(G, W, H, N, grid, tiles)) return SLU_EUNSUPPORTED;
   hipLaunchKernelGGL(depth_to_space2_elu_h8_kernel, grid, dim3(256), 0, slu_stream(stream), reinterpret_cast<const uint4*>(y), out, N, classes, G, H, W,
                      tiles);
   SLU_CHECK_LAUNCH();

@@ -22,10 +22,6 @@ __device__ __forceinline__ void bilinear_taps(int dst, float inv_s, int n_in, in
   l0 = 1.0f - l1;
 }
 
-__device__ __forceinline__ uint4 pack8(const float (&r)[8]) {
-  return make_uint4(pack2(r[0], r[1]), pack2(r[2], r[3]), pack2(r[4], r[5]), pack2(r[6], r[7]));
-}
-
 // One thread per output record, as depth_to_space_h8_kernel: grid x = (block g, 256 output columns), y = output row, z = image; y and z
 // stride.  The four source records of a pixel are whole records too; s consecutive lanes share them.  The sum is written as
 // bilinear_up_kernel (fpn_ops.hip) writes it, without contraction, so the fp32 value is the one the fp32 path stores.
@@ -33,8 +29,8 @@ __global__ __launch_bounds__(256) void bilinear_up_h8_kernel(const uint4* __rest
                                                              int tiles) {
 #pragma clang fp contract(off)
   const int OH = s * H, OW = s * W;
-  const int g = (int)(blockIdx.x / (unsigned)tiles);
-  const int ox = (int)(blockIdx.x - (unsigned)g * (unsigned)tiles) * 256 + (int)threadIdx.x;
+  const H8Col col = h8_row_col(tiles);
+  const int g = col.g, ox = col.x;
   if (ox >= OW) return;
   const float inv_s = 1.0f / (float)s;
   int x0, x1;
@@ -51,7 +47,7 @@ __global__ __launch_bounds__(256) void bilinear_up_h8_kernel(const uint4* __rest
       float r[8];
 #pragma unroll
       for (int k = 0; k < 8; ++k) r[k] = hl0 * (wl0 * (float)a[k] + wl1 * (float)b[k]) + hl1 * (wl0 * (float)c[k] + wl1 * (float)d[k]);
-      y[(((size_t)n * G + g) * OH + oy) * OW + ox] = pack8(r);
+      y[(((size_t)n * G + g) * OH + oy) * OW + ox] = h8_pack8(r);
     }
   }
 }
@@ -149,7 +145,7 @@ __global__ __launch_bounds__(256) void groupnorm_apply_h8_kernel(const uint4* x,
         r[k] = ((float)v[k] - mu[k]) * sa[k] + sb[k];
         r[k] = relu ? fmaxf(r[k], 0.0f) : r[k];
       }
-      dst[i] = pack8(r);
+      dst[i] = h8_pack8(r);
     }
   }
 }
@@ -215,13 +211,11 @@ __global__ __launch_bounds__(256) void spatial_gate_h8_kernel(const uint4* __res
         float r[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) r[k] = fmaf((float)v[k], w, (float)v[k]);
-        out[at] = pack8(r);
+        out[at] = h8_pack8(r);
       }
     }
   }
 }
-
-inline bool aligned16(const void* a, const void* b = nullptr) { return (((uintptr_t)a | (uintptr_t)b) & 15) == 0; }
 
 // parts of a plane for the GroupNorm sums: at least 1024 records each, and about 2048 workgroups over all planes (N = 1, C = 16 at
 // 128 x 2048 is 2 planes of 4 MB: 256 parts each)
@@ -236,12 +230,12 @@ inline unsigned capped(size_t v, unsigned cap) { return (unsigned)(v > cap ? cap
 }  // namespace
 
 extern "C" int slu_bilinear_upsample_h8(const void* x, void* y, int N, int G, int H, int W, int s, slu_stream_t stream) {
-  if (!x || !y || N <= 0 || G <= 0 || H <= 0 || W <= 0 || !aligned16(x, y)) return SLU_EINVAL;
+  if (!x || !y || N <= 0 || G <= 0 || H <= 0 || W <= 0 || !h8_aligned16(x, y)) return SLU_EINVAL;
   if (s != 2 && s != 4 && s != 8) return SLU_EINVAL;
   if ((long long)s * H > 0x7fffffffLL || (long long)s * W > 0x7fffffffLL) return SLU_EUNSUPPORTED;
-  const int OH = s * H, OW = s * W, tiles = (OW + 255) / 256;
-  if ((long long)tiles * G > 0x7fffffffLL) return SLU_EUNSUPPORTED;
-  const dim3 grid((unsigned)(tiles * G), capped((size_t)OH, 65535), capped((size_t)N, 65535));
+  dim3 grid;
+  int tiles;
+  if (!h8_row_grid(G, s * W, s * H, N, grid, tiles)) return SLU_EUNSUPPORTED;
   hipLaunchKernelGGL(bilinear_up_h8_kernel, grid, dim3(256), 0, slu_stream(stream), reinterpret_cast<const uint4*>(x), reinterpret_cast<uint4*>(y), N, G, H,
                      W, s, tiles);
   SLU_CHECK_LAUNCH();
@@ -256,7 +250,7 @@ extern "C" size_t slu_groupnorm_stats_h8_workspace_bytes(int N, int C, int HW) {
 extern "C" int slu_groupnorm_stats_h8(const void* x, int N, int C, int HW, int groups, float eps, float* mean, float* rstd, void* workspace,
                                       slu_stream_t stream) {
   if (!x || !mean || !rstd || !workspace || N <= 0 || C <= 0 || HW <= 0 || groups <= 0 || C % groups || !(eps >= 0.0f)) return SLU_EINVAL;
-  if (!aligned16(x) || ((uintptr_t)workspace & 7)) return SLU_EINVAL;
+  if (!h8_aligned16(x) || ((uintptr_t)workspace & 7)) return SLU_EINVAL;
   const int cpg = C / groups, G = (C + 7) / 8;
   if (cpg != 1 && cpg != 2 && cpg != 4 && cpg != 8) return SLU_EUNSUPPORTED;      // a group must lie inside one record
   const long long planes = (long long)N * G;
@@ -273,7 +267,7 @@ extern "C" int slu_groupnorm_stats_h8(const void* x, int N, int C, int HW, int g
 
 extern "C" int slu_groupnorm_apply_h8(const void* x, const float* mean, const float* rstd, const float* gamma, const float* beta, int relu, void* out, int N,
                                       int C, int HW, int groups, int Gtot, int g_off, slu_stream_t stream) {
-  if (!x || !mean || !rstd || !out || N <= 0 || C <= 0 || HW <= 0 || groups <= 0 || C % groups || !aligned16(x, out)) return SLU_EINVAL;
+  if (!x || !mean || !rstd || !out || N <= 0 || C <= 0 || HW <= 0 || groups <= 0 || C % groups || !h8_aligned16(x, out)) return SLU_EINVAL;
   const int G = (C + 7) / 8;
   if (g_off < 0 || g_off + G > Gtot) return SLU_EINVAL;
   if (x == out && (Gtot != G || g_off != 0)) return SLU_EINVAL;                   // in place only as the whole tensor
@@ -285,10 +279,10 @@ extern "C" int slu_groupnorm_apply_h8(const void* x, const float* mean, const fl
 }
 
 extern "C" int slu_spatial_softmax_gate_h8(const void* x, const float* score, float* stats, void* out, int N, int C, int HW, slu_stream_t stream) {
-  if (!x || !score || !stats || !out || N <= 0 || C <= 0 || HW <= 0 || !aligned16(x, out) || ((uintptr_t)score & 3)) return SLU_EINVAL;
+  if (!x || !score || !stats || !out || N <= 0 || C <= 0 || HW <= 0 || !h8_aligned16(x, out) || ((uintptr_t)score & 3)) return SLU_EINVAL;
   const int G = (C + 7) / 8;
   hipStream_t st = slu_stream(stream);
-  if ((HW & 3) == 0 && aligned16(score))
+  if ((HW & 3) == 0 && h8_aligned16(score))
     hipLaunchKernelGGL(spatial_softmax_stats_h8_kernel<true>, dim3((unsigned)N), dim3(1024), 0, st, score, (size_t)HW, stats);
   else
     hipLaunchKernelGGL(spatial_softmax_stats_h8_kernel<false>, dim3((unsigned)N), dim3(1024), 0, st, score, (size_t)HW, stats);

@@ -1,4 +1,5 @@
-// Device vocabulary shared by the half-precision ("h8") kernels: conv2d_h8.hip, conv_tail_h8.hip, ctx_block_h8.hip, head_mc_h8.hip, fpn_h8.hip.
+// Vocabulary shared by the half-precision ("h8") kernels and their launchers: conv2d_h8.hip, conv_tail_h8.hip, ctx_block_h8.hip, head_mc_h8.hip,
+// layout_h8.hip, fpn_h8.hip, fpn_opt_h8.hip.
 // Every helper is forced inline, and its form (what comes by value, by reference, as a macro) is the one with which the kernels compile
 // to the instruction streams of the hand-written copies they replace: check a change here with tools/h8_isa_diff.py (profiles/r07).
 #pragma once
@@ -50,6 +51,10 @@ __device__ __forceinline__ unsigned pack2(float x, float y) {
 __device__ __forceinline__ unsigned pack2(float2v t) { return __builtin_bit_cast(unsigned, __builtin_convertvector(t, half2v)); }
 __device__ __forceinline__ float2v unpack2(unsigned u) { return __builtin_convertvector(__builtin_bit_cast(half2v, u), float2v); }
 __device__ __forceinline__ float2v round_f16(float2v t) { return __builtin_convertvector(__builtin_convertvector(t, half2v), float2v); }
+// 8 fp32 values -> one 16-byte record, each rounded to fp16 once
+__device__ __forceinline__ uint4 h8_pack8(const float (&r)[8]) {
+  return make_uint4(pack2(r[0], r[1]), pack2(r[2], r[3]), pack2(r[4], r[5]), pack2(r[6], r[7]));
+}
 
 // 4 channels (8 q + 4 hh + 0..3 of a 32-block) of one pixel: the share of accumulator group q that a lane holds
 struct H8Quad {
@@ -159,6 +164,27 @@ template <int N>
 __device__ __forceinline__ void h8_chunk_landed() {
   h8_vmcnt<N>();
   h8_lds_barrier();
+}
+
+// The row walk of the one-thread-per-record kernels (pooling, space <-> depth, bilinear): grid x = (channel block g, tile of 256 columns),
+// y = row, z = image, so a thread's only division is the uniform blockIdx.x / tiles; y and z stride where a launch has more rows or images
+// than a grid dimension holds.  The kernel returns where x is past its last column.  By value as a struct, like H8Run.
+struct H8Col { int g, x; };
+__device__ __forceinline__ H8Col h8_row_col(int tiles) {
+  const int g = (int)(blockIdx.x / (unsigned)tiles);
+  return H8Col{g, (int)(blockIdx.x - (unsigned)g * (unsigned)tiles) * 256 + (int)threadIdx.x};
+}
+// ... and its grid for `blocks` channel blocks of rows x cols records in n images; false where grid x would not fit
+inline bool h8_row_grid(int blocks, int cols, int rows, int n, dim3& grid, int& tiles) {
+  tiles = (cols + 255) / 256;
+  if ((long long)tiles * blocks > 0x7fffffffLL) return false;
+  grid = dim3((unsigned)(tiles * blocks), (unsigned)(rows < 65535 ? rows : 65535), (unsigned)(n < 65535 ? n : 65535));
+  return true;
+}
+// every pointer on a 16-byte boundary (a null pointer counts as aligned: optional arguments)
+template <class... P>
+inline bool h8_aligned16(const P*... p) {
+  return ((... | (uintptr_t)p) & 15) == 0;
 }
 
 }  // namespace

@@ -1,4 +1,4 @@
-"""GPU: avgpool3s2_h8 (csrc/conv2d_h8.hip) bit for bit against a CPU emulation of the kernel's own fp32 sequence on zero-padded
+"""GPU: avgpool3s2_h8 (csrc/layout_h8.hip) bit for bit against a CPU emulation of the kernel's own fp32 sequence on zero-padded
 tensors: acc = +0.0, the nine taps added one after the other (rows -1 .. 1 outside, columns -1 .. 1 inside; a tap outside the image
 is the pad's +0.0, which leaves acc as it is), then acc * s, then the true division by 9, then round to fp16.  Every step is one IEEE
 fp32 operation (no contraction is possible between a multiply and a divide), so the emulation has one answer;

@@ -51,7 +51,7 @@ def kernels(path, match="h8"):
                     cur = out.setdefault(short(m.group(1)), []) if match in m.group(1) else None
                     continue
                 ins = " ".join(line.split("//")[0].split())
-                if cur is None or not ins:
+                if cur is None or not ins or ins == "...":      # "...": objdump's mark for the zero padding between two symbols, not an instruction
                     continue
                 if ins.startswith("s_getpc_b64"):
                     pcrel = 2
