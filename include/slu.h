@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SLU_ABI_VERSION 36
+#define SLU_ABI_VERSION 37
 
 #define SLU_OK            0
 #define SLU_EINVAL       -1   /* null pointer / non-positive size / inconsistent descriptor   */
@@ -516,6 +516,24 @@ int slu_auroc_scores(const float* preds, const int64_t* labels, const float* sco
 size_t slu_auroc_workspace_bytes(long long n);
 int slu_auroc_compute(const float* scores, const uint8_t* is_error, long long n, void* workspace, size_t workspace_bytes, double* out3,
                       float* sorted_scores, uint8_t* sorted_is_error, slu_stream_t stream);
+
+/* ---- AURC / E-AURC of selective prediction (metrics/aurc.py:7-45, :60-120) ----------------------------------------
+ * slu_aurc_samples: per pixel, prediction = first argmax of probs [B,C,H,W] as given (no renormalisation), C <= 32; conf = the max
+ *   probability (use_max_prob_confidence), else 1 - clamp(ent_mc, 0, 1) when ent_mc [B,H,W] is given, else
+ *   1 - clamp(H / log C, 0, 1) with H = -sum max(p, 1e-12) log max(p, 1e-12); flags[pix] = 0 correct / 1 error / 2 label == ignore_index.
+ * slu_aurc_compute: `n` samples (conf, is_error in {0,1}) sorted ascending by conf, stable (equal confidences keep their sample order;
+ *   -0.0 == +0.0).  A curve point sits at the first element of every group of equal confidences among positions 0..n-2 (s_1 < ... < s_m):
+ *   R_0 = E/n, R_k = (E - e_{s_k}) / (n-1-s_k), cov_k = (n-1-s_k)/n, AURC = trapezoid over the points with weights (s_k - s_{k-1})/n plus
+ *   the tail R_m (n-2-s_m)/n, AURC_opt = (1/n) sum_{j<=E} j / (n-E+j).  out6 = {AURC, EAURC, AURC_opt, E, m, s_m} (s_m = -1 when m = 0);
+ *   recalls[j] = e_{m_j - 1} / max(E, 1), m_j = max(1, int(n ks[j] / 100)), ks a HOST array of nks <= 16 percentages; optionally the
+ *   curve points 0..m (curve_cov / curve_risk, fp64, room for n entries, both or neither) and the samples in sorted order.  Every sum is
+ *   fp64 in a fixed order: the result is the same bits run to run.  n < 2^31. */
+int slu_aurc_samples(const float* probs, const int64_t* labels, const float* ent_mc, int B, int C, int HW, int64_t ignore_index,
+                     int use_max_prob_confidence, float* conf, uint8_t* flags, slu_stream_t stream);
+size_t slu_aurc_workspace_bytes(long long n);
+int slu_aurc_compute(const float* confids, const uint8_t* is_error, long long n, void* workspace, size_t workspace_bytes,
+                     const double* ks, int nks, double* out6, double* recalls, double* curve_cov, double* curve_risk,
+                     float* sorted_confids, uint8_t* sorted_is_error, slu_stream_t stream);
 
 /* ---- accuracy vs uncertainty bins (models/evaluator.py:640-749 UncertaintyAccuracyAggregator) ---------------------
  * slu_ua_samples: u_out = clamp(uncertainty, 0, 1); flags = 1 label == pred / 0 otherwise / 2 label in ignore_ids (:659-673).

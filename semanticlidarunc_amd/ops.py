@@ -1195,6 +1195,73 @@ def auroc_from_samples(scores: torch.Tensor, is_error: torch.Tensor, want_sorted
 
 
 # ------------------------------------------------------------------------------------------------
+# AURC / E-AURC of selective prediction (metrics/aurc.py of the reference)
+# ------------------------------------------------------------------------------------------------
+AURC_KS = (1, 2, 5, 10, 20, 30, 40, 50)
+AURC_MAX_KS = 16
+
+
+class AurcResult(NamedTuple):
+    aurc: float
+    eaurc: float
+    aurc_opt: float
+    num_errors: int                               # E
+    num_points: int                               # m: curve points after point 0, before the tail
+    last_start: int                               # s_m (-1 when m == 0)
+    recalls: "list[float]"                        # e_{m_k - 1} / max(E, 1) per entry of ks
+    coverages: Optional[torch.Tensor] = None      # fp64 [m + 1] on the device (want_curve): points 0..m, the tail is the caller's
+    rc_risks: Optional[torch.Tensor] = None
+    sorted_confids: Optional[torch.Tensor] = None     # ascending, stable (want_sorted)
+    sorted_is_error: Optional[torch.Tensor] = None
+
+
+def aurc_samples(probs: torch.Tensor, labels: torch.Tensor, ignore_index: int, ent_mc: Optional[torch.Tensor] = None,
+                 use_max_prob_confidence: bool = False):
+    """(conf[B,H,W] fp32, flag[B,H,W] uint8: 0 correct / 1 error / 2 ignored) -- slu_aurc_samples."""
+    _req(probs, "probs")
+    _req(labels, "labels", torch.int64)
+    if probs.dim() != 4 or tuple(labels.shape) != (probs.shape[0], probs.shape[2], probs.shape[3]) or probs.numel() == 0:
+        raise RuntimeError(f"aurc_samples: probs [B,C,H,W] / labels [B,H,W] expected, got {tuple(probs.shape)} / {tuple(labels.shape)}")
+    b, c, h, w = probs.shape
+    if ent_mc is not None:
+        _req(ent_mc, "ent_mc")
+        if tuple(ent_mc.shape) != (b, h, w):
+            raise RuntimeError(f"ent_mc: expected {(b, h, w)}, got {tuple(ent_mc.shape)}")
+    conf = torch.empty((b, h, w), dtype=torch.float32, device=probs.device)
+    flag = torch.empty((b, h, w), dtype=torch.uint8, device=probs.device)
+    check(_lib.load().slu_aurc_samples(probs.data_ptr(), labels.data_ptr(), _ptr(ent_mc), b, c, h * w, int(ignore_index),
+                                       1 if use_max_prob_confidence else 0, conf.data_ptr(), flag.data_ptr(), _stream()), "slu_aurc_samples")
+    return conf, flag
+
+
+def aurc_from_samples(confids: torch.Tensor, is_error: torch.Tensor, ks: Sequence[float] = AURC_KS, want_curve: bool = False,
+                      want_sorted: bool = False) -> AurcResult:
+    """AURC / E-AURC / top-k% error recall of 1-D device samples (conf fp32, is_error uint8 in {0,1}) -- slu_aurc_compute."""
+    _req(confids, "confids")
+    _req(is_error, "is_error", torch.uint8)
+    if confids.dim() != 1 or confids.shape != is_error.shape or confids.numel() == 0:
+        raise RuntimeError("aurc_from_samples: two equally long, non-empty 1-D tensors expected")
+    ks = [float(k) for k in ks]
+    if len(ks) > AURC_MAX_KS or any(not k >= 0.0 for k in ks):
+        raise RuntimeError(f"aurc_from_samples: at most {AURC_MAX_KS} non-negative percentages expected, got {ks}")
+    lib = _lib.load()
+    n, dev = confids.numel(), confids.device
+    ws = torch.empty(lib.slu_aurc_workspace_bytes(n), dtype=torch.uint8, device=dev)
+    out = torch.empty(6 + len(ks), dtype=torch.float64, device=dev)            # out6, then the recalls
+    cov = torch.empty(n, dtype=torch.float64, device=dev) if want_curve else None
+    risk = torch.empty(n, dtype=torch.float64, device=dev) if want_curve else None
+    ss = torch.empty_like(confids) if want_sorted else None
+    se = torch.empty_like(is_error) if want_sorted else None
+    ks_host = (C.c_double * max(len(ks), 1))(*ks)
+    check(lib.slu_aurc_compute(confids.data_ptr(), is_error.data_ptr(), n, ws.data_ptr(), ws.numel(), C.addressof(ks_host), len(ks), out.data_ptr(),
+                               out.data_ptr() + 6 * 8, _ptr(cov), _ptr(risk), _ptr(ss), _ptr(se), _stream()), "slu_aurc_compute")
+    host = out.cpu().tolist()
+    m = int(host[4])
+    return AurcResult(host[0], host[1], host[2], int(host[3]), m, int(host[5]), host[6:],
+                      cov[:m + 1] if want_curve else None, risk[:m + 1] if want_curve else None, ss, se)
+
+
+# ------------------------------------------------------------------------------------------------
 # accuracy vs uncertainty bins (models/evaluator.py UncertaintyAccuracyAggregator)
 # ------------------------------------------------------------------------------------------------
 def ua_samples(labels: torch.Tensor, preds: torch.Tensor, uncertainty: torch.Tensor, ignore_ids=()):
