@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SLU_ABI_VERSION 37
+#define SLU_ABI_VERSION 38
 
 #define SLU_OK            0
 #define SLU_EINVAL       -1   /* null pointer / non-positive size / inconsistent descriptor   */
@@ -704,6 +704,40 @@ int slu_dwconv3x3_fwd(const float* x, const float* w, const float* bias, float* 
 int slu_global_avgpool(const float* x, float* out, int N, int C, int HW, slu_stream_t stream);
 int slu_se_gate(const float* avg, const float* w1, const float* b1, const float* w2, const float* b2, float* scale, int N, int C, int S,
                 slu_stream_t stream);
+
+/* ---- ShuffleNetV2 unit tail (models/semanticFCN.py:181-190 and baselines/Reichert/semanticFCN_opt.py:227-236 build torchvision's
+ * shufflenet_v2_x{0_5,1_0,1_5,2_0}; the unit is torchvision's InvertedResidual) ---------------------------------------------------------
+ * slu_shuffle_tail_fwd: depthwise 3x3 (pad 1, stride 1 or 2) -> pointwise 1x1 -> ReLU with both eval BatchNorms folded in, stored through the
+ * unit's concat + channel_shuffle(., 2), and optionally the copy of the pass-through half, in one launch:
+ *
+ *   y[n,j]               = relu( bpw[j] + sum_c wpw[j,c] * ( bdw[c] + sum_{a,b} wdw[c,3a+b] * src[n,c, s*oy-1+a, s*ox-1+b] ) )       j < Co
+ *   out[n, 2j + parity]  = y[n,j]
+ *   out[n, 2j]           = pass[n,j]       when pass != NULL (parity must then be 1)
+ *
+ * src is the channel concatenation  src0[:, coff0 : coff0 + c0]  (+)  src1[:, :c1]  of dense NCHW fp32 tensors with ct0 / ct1 stored channels at
+ * H x W (src1 NULL, c1 = 0: one source); C = c0 + c1.  out is [N][2 Co][Ho][Wo], Ho = ceil(H / stride), Wo likewise; the channels of the other
+ * parity are left untouched when pass is NULL.  pass is [N][pass_ct][Ho][Wo] and its first Co channels are copied.  The depthwise result stays
+ * on chip.  The pointwise product is exact fp32 (v_mfma_f32_32x32x2_f32) whatever the conv precision of the surrounding model; no atomics, so
+ * results are bit-identical run to run.  wpack = slu_shuffle_tail_pack of wpw [Co][C] (slu_shuffle_tail_packed_floats(Co, C) floats; 0 =
+ * unsupported).  Co <= 512, stride 1 / 2, N <= 65535, H W < 2^31; anything else is SLU_EUNSUPPORTED.  out must not overlap an input. */
+typedef struct slu_shuffle_tail_desc {   /* HOST struct */
+  const float* src0;
+  const float* src1;
+  int32_t ct0, coff0, c0;
+  int32_t ct1, c1;
+  int32_t N, H, W, stride;
+  int32_t Co, parity;
+  int32_t pass_ct;
+  const float* wdw;      /* [C][9]  */
+  const float* bdw;      /* [C]     */
+  const float* wpack;
+  const float* bpw;      /* [Co]    */
+  const float* pass;
+  float* out;
+} slu_shuffle_tail_desc;
+size_t slu_shuffle_tail_packed_floats(int co, int c);
+int slu_shuffle_tail_pack(const float* w, int co, int c, float* out, slu_stream_t stream);
+int slu_shuffle_tail_fwd(const slu_shuffle_tail_desc* d, slu_stream_t stream);
 
 #ifdef __cplusplus
 }

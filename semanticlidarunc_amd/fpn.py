@@ -5,7 +5,7 @@ Contract kept: constructor keywords (plus the stale `resnet_type=` alias that sr
 `forward(x[B,cin,H,W], meta[B,m,H,W]) -> [B,num_classes,H,W]` (ELU + 1 > 0), and the `state_dict` layout including the
 aliased `stem.0.* / layerN.*` duplicates of `backbone.*` and the never-used `backbone.bn1.* / backbone.fc.*`
 (semanticFCN.py:146-153).  torchvision is not needed: the backbone container below re-creates the public
-resnet18/34 BasicBlock architecture (names, shapes); `pretrained` weights are not downloaded -- load a checkpoint.
+resnet18/34 BasicBlock architecture (names, shapes), shufflenet.py the ShuffleNetV2 one; `pretrained` weights are not downloaded -- load a checkpoint.
 
 How the layers map onto kernels (inference; BatchNorm folded into the preceding conv's weights and bias):
   conv3x3/s1 + BN + ReLU ........ one fused conv launch (ReLU = leaky slope 0)
@@ -17,6 +17,12 @@ How the layers map onto kernels (inference; BatchNorm folded into the preceding 
                                   softmax over azimuth fused with the multiply into the value map
   ConvTranspose2d k = s ......... 1x1 conv to Cout*s*s channels + depth-to-space
   ConvTranspose2d k4 s2 p1 ...... 3x3 conv to 4*classes sub-pixel channels + depth-to-space fused with ELU + 1
+
+ShuffleNetV2 encoders (shufflenet_v2_x0_5 / x1_0 / x1_5 / x2_0, inference only; container in shufflenet.py): stem = conv1 (conv + BN + ReLU at
+stride 1, no maxpool), layer1..3 = stage2..4, layer4 = conv5, so x1 .. x4 sit at 1/2, 1/4, 1/8, 1/8 resolution and the head's transposed convs are
+k4s4 / k4s4 / k2s2.  A unit (InvertedResidual) is the fused conv for branch2's first 1x1 -- reading x[:, C/2:] through `ConvSource.coff` -- plus
+slu_shuffle_tail_fwd for depthwise 3x3 -> BN -> 1x1 -> BN -> ReLU -> concat -> channel shuffle (and the pass-through copy): 2 launches per
+stride-1 unit, 3 per stride-2 unit.  The tail's pointwise product is the exact-fp32 MFMA under "fp32" and "f16x3" alike; "f16" is refused.
 
 Conv precision "f16" (resnet18 / resnet34, inference): the same layers on the half-precision storage path (h8.py) -- activations stay
 [N, G, H, W, 8] fp16 from the stem's input to the last conv's output (`_forward_h8`).  What differs from the list above: the space-to-depth
@@ -34,6 +40,7 @@ import torch.nn as nn
 from . import h8 as _h8
 from . import ops
 from . import salsanext as _sn
+from . import shufflenet as _shf
 from .ops import ConvSource
 
 
@@ -128,11 +135,12 @@ class SemanticNetworkWithFPN(nn.Module):
         super().__init__()
         if resnet_type is not None:          # stale keyword of src/inference_ouster.py:35
             backbone = resnet_type
-        if backbone not in _RESNETS:
-            if backbone in ("regnet_y_400mf", "regnet_y_800mf", "regnet_y_1_6gf", "regnet_y_3_2gf", "shufflenet_v2_x0_5",
-                            "shufflenet_v2_x1_0", "shufflenet_v2_x1_5", "shufflenet_v2_x2_0", "squeezenet1_0", "efficientnet_v2_s",
+        self.is_shuffle = backbone in _shf.BASE_CHANNELS
+        if backbone not in _RESNETS and not self.is_shuffle:
+            if backbone in ("regnet_y_400mf", "regnet_y_800mf", "regnet_y_1_6gf", "regnet_y_3_2gf", "squeezenet1_0", "efficientnet_v2_s",
                             "efficientnet_v2_m", "efficientnet_v2_l"):
-                raise NotImplementedError(f"backbone '{backbone}' is not implemented on the HIP path yet (resnet18 / resnet34 / resnet50 are)")
+                raise NotImplementedError(f"backbone '{backbone}' is not implemented on the HIP path yet (resnet18 / resnet34 / resnet50 and "
+                                          "shufflenet_v2_x0_5 / x1_0 / x1_5 / x2_0 are)")
             raise ValueError("Invalid ResNet type. Supported types: 'resnet18', 'resnet34', 'resnet50', 'regnet_y_400mf','regnet_y_800mf', "
                              "'regnet_y_1_6gf', 'regnet_y_3_2gf', 'shufflenet_v2_x0_5', 'shufflenet_v2_x1_0', 'shufflenet_v2_x1_5', "
                              "'shufflenet_v2_x2_0.")
@@ -140,15 +148,16 @@ class SemanticNetworkWithFPN(nn.Module):
             raise NotImplementedError("only interpolation_mode='nearest' (the reference default) runs on the HIP path")
         self.backbone_name, self.interpolation_mode = backbone, interpolation_mode
         self.num_classes, self.attention, self.multi_scale_meta = num_classes, attention, multi_scale_meta
-        bc = self._build_encoder(backbone, input_channels, meta_channel_dim)
+        bc = self._build_shufflenet(backbone, input_channels, meta_channel_dim) if self.is_shuffle else self._build_encoder(backbone, input_channels, meta_channel_dim)
         self.attention4, self.attention3 = AttentionModule(bc[1], bc[1]), AttentionModule(bc[2], bc[2])
         self.attention2, self.attention1 = AttentionModule(bc[3], bc[3]), AttentionModule(bc[4], bc[4])
         self.fpn_block4, self.fpn_block3 = self._fpn(bc[0], bc[1]), self._fpn(bc[1], bc[2])
         self.fpn_block2, self.fpn_block1 = self._fpn(bc[2], bc[3]), self._fpn(bc[3], bc[4])
-        self.upsample_layer_x4 = nn.ConvTranspose2d(bc[1], bc[1] // 8, 8, 8, 0)
+        s4 = 4 if self.is_shuffle else 8      # semanticFCN.py:217-221: x3 and x4 both sit at 1/8 resolution under a ShuffleNetV2 encoder
+        self.upsample_layer_x4 = nn.ConvTranspose2d(bc[1], bc[1] // s4, s4, s4, 0)
         self.upsample_layer_x3 = nn.ConvTranspose2d(bc[2], bc[2] // 4, 4, 4, 0)
         self.upsample_layer_x2 = nn.ConvTranspose2d(bc[3], bc[3] // 2, 2, 2, 0)
-        up = bc[1] // 8 + bc[2] // 4 + bc[3] // 2
+        up = bc[1] // s4 + bc[2] // 4 + bc[3] // 2
         self.decoder_semantic = nn.Sequential(
             nn.Conv2d(up + bc[4], bc[4], 3, 1, 1), nn.BatchNorm2d(bc[4]), nn.ReLU(inplace=True),
             nn.Conv2d(bc[4], bc[4], 3, 1, 1), nn.BatchNorm2d(bc[4]), nn.ReLU(inplace=True),
@@ -166,6 +175,17 @@ class SemanticNetworkWithFPN(nn.Module):
         self.layer3, self.layer4 = self.backbone.layer3, self.backbone.layer4
         top = 512 * block.expansion                      # semanticFCN.py:85-96: 512 (resnet18 / 34), 2048 (resnet50)
         return [top, top // 2, top // 4, top // 8, top // 16]
+
+    def _build_shufflenet(self, backbone, input_channels, meta_channel_dim):
+        """The torchvision-shaped ShuffleNetV2 with the reference's surgery (semanticFCN.py:181-190): conv1[0] replaced by a 3x3 / stride-1 conv
+        over input + meta channels, `stem` = conv1 (no maxpool), layer1..3 = stage2..4, layer4 = conv5.  Returns the channel ladder."""
+        self.meta_channel_dim = meta_channel_dim
+        self.backbone = _shf.ShuffleNetV2Container(backbone)
+        self.backbone.conv1[0] = nn.Conv2d(input_channels + meta_channel_dim, self.backbone.conv1[0].out_channels, kernel_size=3, stride=1, padding=1,
+                                           bias=False)
+        self.stem = self.backbone.conv1
+        self.layer1, self.layer2, self.layer3, self.layer4 = self.backbone.stage2, self.backbone.stage3, self.backbone.stage4, self.backbone.conv5
+        return list(_shf.BASE_CHANNELS[backbone])
 
     def _check_inputs(self, x, meta_channel):
         if not (isinstance(x, torch.Tensor) and isinstance(meta_channel, torch.Tensor)) or x.dim() != 4 or meta_channel.dim() != 4:
@@ -195,6 +215,68 @@ class SemanticNetworkWithFPN(nn.Module):
         x3 = self._stage("layer3", self.layer3, x2, m2)
         x4 = self._stage("layer4", self.layer4, x3, m3)
         return x1, x2, x3, x4
+
+    # ---------------- ShuffleNetV2 encoder (semanticFCN.py:181-190, :306-314; shufflenet.py) ----------------
+    def _shf_tail(self, name, dw: nn.Conv2d, dw_bn, pw: nn.Conv2d, pw_bn):
+        """(wdw [C, 9], bdw [C], wpack, bpw [Co]) of a unit's depthwise 3x3 -> BN -> 1x1 -> BN -> ReLU tail with both BatchNorms folded in, cached per
+        parameter version and conv precision like `_prep` (the pointwise product is the exact-fp32 MFMA under 'fp32' and 'f16x3' alike)."""
+        cache = self.__dict__.setdefault("_shf_cache", {})
+        k = _key(dw.weight, dw_bn.weight, dw_bn.bias, dw_bn.running_mean, dw_bn.running_var,
+                 pw.weight, pw_bn.weight, pw_bn.bias, pw_bn.running_mean, pw_bn.running_var)
+        hit = cache.get(name)
+        if hit is None or hit[0] != k:
+            w9, b9 = self._fold(dw.weight, None, dw_bn)
+            w1, b1 = self._fold(pw.weight, None, pw_bn)
+            co, c = w1.shape[0], w1.shape[1]
+            hit = cache[name] = (k, w9.detach().float().reshape(c, 9).contiguous(), b9.detach().float().contiguous(),
+                                 ops.pack_shuffle_tail_weight(w1.detach().float().reshape(co, c).contiguous()), b1.detach().float().contiguous())
+        return hit[1:]
+
+    def _shf_unit(self, n: str, blk, x, meta_k):
+        """One InvertedResidual: the fused conv for branch2's first 1x1 (+ BN + ReLU), slu_shuffle_tail_fwd for the rest -- two launches for a
+        stride-1 unit, three for a stride-2 one.  meta_k: the meta channels that replace the last m input channels (first unit of a stage)."""
+        b2 = blk.branch2
+        cx = x.shape[1]
+        bf = b2[5].out_channels
+        if blk.stride == 1:
+            if meta_k is not None:
+                raise NotImplementedError("meta injection into a stride-1 ShuffleNetV2 unit does not occur (every stage opens with a stride-2 unit)")
+            h = self._conv(n + ".branch2.0", b2[0], b2[1], [ConvSource(x, None, False, 0, bf, cx - bf)])                  # x[:, C/2:]
+            return ops.shuffle_tail(h, *self._shf_tail(n + ".branch2.3", b2[3], b2[4], b2[5], b2[6]), bf, 1, passthrough=x)
+        m = 0 if meta_k is None else meta_k.shape[1]
+        b1 = blk.branch1
+        out = torch.empty((x.shape[0], 2 * bf, (x.shape[2] + 1) // 2, (x.shape[3] + 1) // 2), dtype=torch.float32, device=x.device)
+        ops.shuffle_tail(x, *self._shf_tail(n + ".branch1.0", b1[0], b1[1], b1[2], b1[3]), bf, 2, out=out, parity=0, cuse=cx - m, src2=meta_k)
+        src = [ConvSource(x)] if meta_k is None else [ConvSource(meta_k), ConvSource(x, None, False, 0, cx - m)]             # (meta, x[:, :-m])
+        h = self._conv(n + ".branch2.0", b2[0], b2[1], src, tail_first=m)
+        return ops.shuffle_tail(h, *self._shf_tail(n + ".branch2.3", b2[3], b2[4], b2[5], b2[6]), bf, 2, out=out, parity=1)
+
+    def _encode_shufflenet(self, x, meta):
+        """(x1, x2, x3, x4) at 1/2, 1/4, 1/8, 1/8 resolution: stem (conv + BN + ReLU, stride 1), stage2..4, conv5, with the multi-scale meta
+        injection on the way into stage3 / stage4 / conv5 (semanticFCN.py:306-314)."""
+        m1 = m2 = m3 = None
+        if self.multi_scale_meta:
+            m1, m2, m3 = ops.nearest_down(meta, 2), ops.nearest_down(meta, 4), ops.nearest_down(meta, 8)
+        h = self._conv("stem", self.stem[0], self.stem[1], [ConvSource(x), ConvSource(meta)])
+        outs = []
+        for lname, stage, mk in (("layer1", self.layer1, None), ("layer2", self.layer2, m1), ("layer3", self.layer3, m2)):
+            for bi, blk in enumerate(stage):
+                h = self._shf_unit(f"{lname}.{bi}", blk, h, mk if bi == 0 else None)
+            outs.append(h)
+        x3 = outs[2]
+        m = 0 if m3 is None else m3.shape[1]
+        src = [ConvSource(x3)] if m3 is None else [ConvSource(m3), ConvSource(x3, None, False, 0, x3.shape[1] - m)]
+        x4 = self._conv("layer4", self.layer4[0], self.layer4[1], src, tail_first=m)
+        return outs[0], outs[1], x3, x4
+
+    def _shufflenet_guard(self, x, meta, cls: str):
+        """What a ShuffleNetV2 encoder does not run: training / gradients (no stride-2 depthwise backward) and the half-precision storage path."""
+        if self._wants_autograd(x, meta):
+            raise NotImplementedError(f"{cls} with the {self.backbone_name} backbone is inference only on the HIP path: call model.eval() and run "
+                                      "under torch.no_grad() (the ShuffleNetV2 units have no backward kernels)")
+        if _sn.get_conv_precision() == "f16":
+            raise RuntimeError(f"{cls} with the {self.backbone_name} backbone does not run with conv precision 'f16': the half-precision "
+                               "storage path covers the BasicBlock backbones (resnet18 / resnet34) only; use set_conv_precision('fp32')")
 
     @staticmethod
     def _fpn(cin, cout):
@@ -238,7 +320,7 @@ class SemanticNetworkWithFPN(nn.Module):
         def make():
             w, b = self._fold(conv.weight, conv.bias, bn)
             if tail_first:
-                w = torch.cat([w[:, -tail_first:], w[:, :-tail_first]], 1)
+                w = torch.roll(w, tail_first, 1)              # cat(w[:, -m:], w[:, :-m])
             return w, b, conv.kernel_size[0], conv.dilation[0], conv.padding[0]
         return self._prep(name, make,
                           conv.weight, conv.bias, *(() if bn is None else (bn.weight, bn.bias, bn.running_mean, bn.running_var)))
@@ -543,6 +625,8 @@ class SemanticNetworkWithFPN(nn.Module):
 
     def forward(self, x, meta_channel):
         x, meta = self._check_inputs(x, meta_channel)
+        if self.is_shuffle:
+            self._shufflenet_guard(x, meta, "models/semanticFCN")
         if self._wants_autograd(x, meta):
             return self._forward_train(x, meta)
         if self.backbone_name == "resnet50" and _sn.get_conv_precision() == "f16x3":
@@ -553,7 +637,7 @@ class SemanticNetworkWithFPN(nn.Module):
                 raise RuntimeError("models/semanticFCN with the resnet50 backbone does not run with conv precision 'f16': the half-precision "
                                    "storage path covers the BasicBlock backbones (resnet18 / resnet34) only; use set_conv_precision('fp32')")
             return self._forward_h8(x, meta)
-        x1, x2, x3, x4 = self._encode(x, meta)
+        x1, x2, x3, x4 = self._encode_shufflenet(x, meta) if self.is_shuffle else self._encode(x, meta)
         f4 = self._conv("fpn4", self.fpn_block4[0], self.fpn_block4[1], [ConvSource(x4)])
         f3 = self._conv("fpn3", self.fpn_block3[0], self.fpn_block3[1], [ConvSource(x3)])
         f2 = self._conv("fpn2", self.fpn_block2[0], self.fpn_block2[1], [ConvSource(x2)])

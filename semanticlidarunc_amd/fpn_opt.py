@@ -1,5 +1,6 @@
 """The `semanticFCN_opt` variant of the ResNet-FPN segmenter on MI355X -- what the reference's `train_semantics.py:134` builds for
-`baseline: Reichert` (src/baselines/Reichert/semanticFCN_opt.py:109-455) -- for the resnet18 / resnet34 / resnet50 backbones.
+`baseline: Reichert` (src/baselines/Reichert/semanticFCN_opt.py:109-455) -- for the resnet18 / resnet34 / resnet50, efficientnet_v2_s / m / l
+and (inference only, MC dropout on the stacked schedule) shufflenet_v2_x0_5 / x1_0 / x1_5 / x2_0 backbones.
 
 Same encoder as `fpn.SemanticNetworkWithFPN` (shared code); the head differs:
   SpatialAttention (:73-85)   1x1 (C -> C/8, no bias) + ReLU -> 1x1 (-> 1) -> softmax over H*W -> x * w + x
@@ -28,6 +29,7 @@ from . import effnet as _eff
 from . import h8 as _h8
 from . import ops
 from . import salsanext as _sn
+from . import shufflenet as _shf
 from .fpn import SemanticNetworkWithFPN as _FPNBase
 from .fpn import _RESNETS
 from .ops import ConvSource
@@ -66,11 +68,12 @@ class SemanticNetworkWithFPN(_FPNBase):
                  attention=True, multi_scale_meta=True):
         nn.Module.__init__(self)
         self.is_effnet = backbone in _eff.BASE_CHANNELS
-        if backbone not in _RESNETS and not self.is_effnet:
-            known = ("regnet_y_400mf", "regnet_y_800mf", "regnet_y_1_6gf", "regnet_y_3_2gf", "shufflenet_v2_x0_5", "shufflenet_v2_x1_0",
-                     "shufflenet_v2_x1_5", "shufflenet_v2_x2_0", "squeezenet1_0")
+        self.is_shuffle = backbone in _shf.BASE_CHANNELS
+        if backbone not in _RESNETS and not self.is_effnet and not self.is_shuffle:
+            known = ("regnet_y_400mf", "regnet_y_800mf", "regnet_y_1_6gf", "regnet_y_3_2gf", "squeezenet1_0")
             if backbone in known:
-                raise NotImplementedError(f"backbone '{backbone}' is not implemented on the HIP path yet (resnet18 / 34 / 50 and efficientnet_v2_s / m / l are)")
+                raise NotImplementedError(f"backbone '{backbone}' is not implemented on the HIP path yet (resnet18 / 34 / 50, efficientnet_v2_s / m / l "
+                                          "and shufflenet_v2_x0_5 / x1_0 / x1_5 / x2_0 are)")
             raise ValueError("Invalid ResNet type. Supported types: 'resnet18', 'resnet34', 'resnet50', 'regnet_y_400mf','regnet_y_800mf', "
                              "'regnet_y_1_6gf', 'regnet_y_3_2gf', 'shufflenet_v2_x0_5', 'shufflenet_v2_x1_0', 'shufflenet_v2_x1_5', "
                              "'shufflenet_v2_x2_0.")
@@ -78,14 +81,19 @@ class SemanticNetworkWithFPN(_FPNBase):
             raise NotImplementedError("only interpolation_mode='nearest' (the reference default) runs on the HIP path")
         self.backbone_name, self.interpolation_mode = backbone, interpolation_mode
         self.num_classes, self.attention, self.multi_scale_meta = num_classes, attention, multi_scale_meta
-        bc = self._build_effnet(backbone, input_channels, meta_channel_dim) if self.is_effnet else self._build_encoder(backbone, input_channels, meta_channel_dim)
+        if self.is_effnet:
+            bc = self._build_effnet(backbone, input_channels, meta_channel_dim)
+        elif self.is_shuffle:
+            bc = self._build_shufflenet(backbone, input_channels, meta_channel_dim)
+        else:
+            bc = self._build_encoder(backbone, input_channels, meta_channel_dim)
         self.attention4, self.attention3 = SpatialAttention(bc[1]), SpatialAttention(bc[2])
         self.attention2, self.attention1 = SpatialAttention(bc[3]), SpatialAttention(bc[4])
         self.fpn_block4, self.fpn_block3 = self._fpn(bc[0], bc[1]), self._fpn(bc[1], bc[2])
         self.fpn_block2, self.fpn_block1 = self._fpn(bc[2], bc[3]), self._fpn(bc[3], bc[4])
         self.dropout_pyramid = nn.Dropout2d(p=0.1)
-        # semanticFCN_opt.py:270-285: the efficientnet branch sets is_shuffle (x4 and x3 both sit at 1/8 resolution there)
-        scales, out_chs = ([4, 4, 2], [bc[1] // 4, bc[2] // 4, bc[3] // 2]) if self.is_effnet else ([8, 4, 2], [bc[1] // 8, bc[2] // 4, bc[3] // 2])
+        # semanticFCN_opt.py:270-285: the shufflenet and efficientnet branches set is_shuffle (x4 and x3 both sit at 1/8 resolution there)
+        scales, out_chs = ([4, 4, 2], [bc[1] // 4, bc[2] // 4, bc[3] // 2]) if self.is_effnet or self.is_shuffle else ([8, 4, 2], [bc[1] // 8, bc[2] // 4, bc[3] // 2])
         self.upsample_layer_x4 = UpsampleBlock(bc[1], out_chs[0], scale=scales[0], mode="bilinear")
         self.upsample_layer_x3 = UpsampleBlock(bc[2], out_chs[1], scale=scales[1], mode="bilinear")
         self.upsample_layer_x2 = UpsampleBlock(bc[3], out_chs[2], scale=scales[2], mode="bilinear")
@@ -337,6 +345,8 @@ class SemanticNetworkWithFPN(_FPNBase):
         sources of the first decoder conv (cat([x1, x2, x3, x4]) with x3 and x4 sharing a buffer)."""
         if self.is_effnet:
             x1, x2, x3, x4 = self._encode_effnet(x, meta)
+        elif self.is_shuffle:
+            x1, x2, x3, x4 = self._encode_shufflenet(x, meta)
         else:
             x1, x2, x3, x4 = self._encode(x, meta)
         f4 = self._conv("fpn4", self.fpn_block4[0], self.fpn_block4[1], [ConvSource(x4)])
@@ -349,7 +359,11 @@ class SemanticNetworkWithFPN(_FPNBase):
         u4 = self._upsample_block("up4", self.upsample_layer_x4, f4)
         u3 = self._upsample_block("up3", self.upsample_layer_x3, f3)
         u2 = self._upsample_block("up2", self.upsample_layer_x2, f2)
-        return f1, u2, torch.cat([u3, u4], dim=1)              # the fused conv takes up to three sources
+        c3 = u3.shape[1]                                       # the fused conv takes up to three sources: x3 and x4 share a buffer
+        u34 = torch.empty((u3.shape[0], c3 + u4.shape[1], u3.shape[2], u3.shape[3]), dtype=torch.float32, device=u3.device)
+        u34[:, :c3].copy_(u3)
+        u34[:, c3:].copy_(u4)
+        return f1, u2, u34
 
     def _decoder(self, f1, u2, u34, s, passes: int = 0, raw_head_input: bool = False):
         """dropout_pyramid multipliers s ([N, C_pyramid] or None) -> decoder_semantic.  passes = T > 0: the pyramid holds B images and the
@@ -452,6 +466,8 @@ class SemanticNetworkWithFPN(_FPNBase):
 
     def _forward(self, x, meta_channel, drop_scale):
         x, meta = self._check_inputs(x, meta_channel)
+        if self.is_shuffle:
+            self._shufflenet_guard(x, meta, "semanticFCN_opt")
         if self._wants_autograd(x, meta):
             return self._forward_train_opt(x, meta, drop_scale)
         if self._use_h8():
@@ -467,6 +483,11 @@ class SemanticNetworkWithFPN(_FPNBase):
     def _mc_shared(self, x, meta_channel, T: int, scale, raw_head_input: bool):
         if self.training:
             raise RuntimeError("forward_mc needs the model in eval mode (use utils.mc_dropout.mc_forward)")
+        if self.is_shuffle:
+            # the shared-prefix schedule runs the encoder at N = B and the stacked one at N = T B: equal to rounding, not verified bit for bit
+            # for these encoders, so it is refused rather than allowed to differ silently
+            raise RuntimeError(f"semanticFCN_opt with the {self.backbone_name} backbone runs MC dropout on the stacked schedule only: "
+                               "use utils.mc_dropout.mc_predict / mc_forward with share_prefix=False")
         x, meta = self._check_inputs(x, meta_channel)
         if self._wants_autograd(x, meta):
             raise RuntimeError("forward_mc is inference only: no train-mode BatchNorm and no gradients")

@@ -56,6 +56,7 @@ class ConvSource(NamedTuple):
     pixel_shuffle: bool = False
     nbatch: int = 0                         # > 0: tensor holds nbatch images, output image n reads image n % nbatch
     cuse: int = 0                           # > 0: only the first cuse channels of the tensor contribute
+    coff: int = 0                           # > 0: the channels read start at coff (x[:, coff:coff + cuse]); needs cuse, no scale / pixel_shuffle
 
 
 def conv_ck(ksize: int) -> int:
@@ -185,6 +186,12 @@ def conv2d_fused(srcs: Sequence[ConvSource], wpack: torch.Tensor, cout: int, ksi
             contributed = s.cuse
         else:
             contributed = sc
+        if s.coff:
+            # a channel range x[:, coff:coff + cuse] is the prefix of the tensor that starts coff planes later with the same batch stride: the
+            # kernels bound every channel they read by `cuse` (a ragged last K-chunk reads element 0 of the source instead), so nothing past
+            # plane coff + cuse - 1 of the last image is touched
+            if s.pixel_shuffle or s.scale is not None or not s.cuse or s.coff < 0 or s.coff + s.cuse > sc:
+                raise RuntimeError(f"src[{i}]: coff needs cuse with coff + cuse <= C and neither scale nor pixel_shuffle")
         if s.nbatch:
             if n is None or sn != s.nbatch or n % sn:
                 raise RuntimeError(f"src[{i}]: a batch-broadcast source must follow a full-batch source (or n_out be given) and divide N")
@@ -199,7 +206,7 @@ def conv2d_fused(srcs: Sequence[ConvSource], wpack: torch.Tensor, cout: int, ksi
                 raise RuntimeError(f"src[{i}].scale: expected {(sn, sc)}, got {tuple(s.scale.shape)}")
         d.src[i].nbatch = int(s.nbatch)
         d.src[i].cuse = int(s.cuse)
-        d.src[i].ptr = t.data_ptr()
+        d.src[i].ptr = t.data_ptr() + 4 * int(s.coff) * sh * sw
         d.src[i].scale = _ptr(s.scale)
         d.src[i].C = sc
         d.src[i].pixel_shuffle = 1 if s.pixel_shuffle else 0
@@ -472,6 +479,8 @@ def _fill_srcs(arr, srcs):
     for i, s in enumerate(srcs):
         t = _req(s.tensor, f"src[{i}]")
         sn, sc, sh, sw = t.shape
+        if s.coff:
+            raise RuntimeError(f"src[{i}]: a channel offset is only read by the forward conv")
         if s.pixel_shuffle:
             sh, sw = sh * 2, sw * 2
         if n is None:
@@ -1654,3 +1663,79 @@ def se_scale(x: torch.Tensor, w1: torch.Tensor, b1: Optional[torch.Tensor], w2: 
     scale = torch.empty((n, c), dtype=torch.float32, device=x.device)
     check(lib.slu_se_gate(avg.data_ptr(), w1.data_ptr(), _ptr(b1), w2.data_ptr(), _ptr(b2), scale.data_ptr(), n, c, s, _stream()), "slu_se_gate")
     return scale
+
+
+# ------------------------------------------------------------------------------------------------
+# ShuffleNetV2 unit tail (csrc/shuffle_unit.hip)
+# ------------------------------------------------------------------------------------------------
+def pack_shuffle_tail_weight(w: torch.Tensor) -> torch.Tensor:
+    """[Co, C] fp32 pointwise weight -> the MFMA A-fragment image slu_shuffle_tail_fwd streams (re-run after every weight update)."""
+    _req(w, "w")
+    if w.dim() != 2:
+        raise RuntimeError(f"pack_shuffle_tail_weight: expected [Co, C], got {tuple(w.shape)}")
+    lib = _lib.load()
+    co, c = w.shape
+    n = lib.slu_shuffle_tail_packed_floats(co, c)
+    if n == 0:
+        raise _lib.SluError(f"slu_shuffle_tail_pack: {lib.slu_strerror(-2).decode()} (code -2): Co={co}")
+    out = torch.empty(n, dtype=torch.float32, device=w.device)
+    check(lib.slu_shuffle_tail_pack(w.data_ptr(), co, c, out.data_ptr(), _stream()), "slu_shuffle_tail_pack")
+    return out
+
+
+def shuffle_tail(src: torch.Tensor, wdw: torch.Tensor, bdw: torch.Tensor, wpack: torch.Tensor, bpw: torch.Tensor, co: int, stride: int,
+                 out: Optional[torch.Tensor] = None, parity: int = 1, coff: int = 0, cuse: int = 0, src2: Optional[torch.Tensor] = None,
+                 passthrough: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The tail of a ShuffleNetV2 unit in one launch (slu_shuffle_tail_fwd): y = relu(W_pw . (dw3x3_stride(src) + bdw) + bpw) with both eval
+    BatchNorms folded into the weights, stored as out[:, 2 j + parity] = y[j] -- the unit's concat + channel_shuffle(., 2) -- and, with
+    `passthrough`, out[:, 2 j] = passthrough[:, j] for j < co.  src is cat(src[:, coff:coff + cuse], src2) (cuse = 0: every channel from coff on;
+    src2 optional), wdw [C, 9], bdw [C], wpack = pack_shuffle_tail_weight(W_pw [co, C]), bpw [co].  out [N, 2 co, Ho, Wo] is allocated when not
+    given; without `passthrough` its channels of the other parity are left as they were.  The depthwise result stays on chip.  The pointwise
+    product is the exact-fp32 MFMA under every conv precision ('fp32' and 'f16x3' alike): the kernel is bandwidth-bound, split products buy nothing."""
+    _req(src, "src")
+    if src.dim() != 4:
+        raise RuntimeError(f"src: expected NCHW, got {tuple(src.shape)}")
+    n, ct0, h, w = src.shape
+    coff, cuse = int(coff), int(cuse)
+    c0 = cuse if cuse else ct0 - coff
+    if coff < 0 or c0 <= 0 or coff + c0 > ct0:
+        raise RuntimeError(f"src: channel range [{coff}, {coff + c0}) is outside the tensor's {ct0} channels")
+    ct1 = c1 = 0
+    if src2 is not None:
+        _req(src2, "src2")
+        if src2.dim() != 4 or (src2.shape[0], src2.shape[2], src2.shape[3]) != (n, h, w):
+            raise RuntimeError(f"src2: expected [{n}, *, {h}, {w}], got {tuple(src2.shape)}")
+        ct1 = c1 = src2.shape[1]
+    c = c0 + c1
+    if stride not in (1, 2) or parity not in (0, 1) or co <= 0:
+        raise RuntimeError("shuffle_tail: stride must be 1 or 2, parity 0 or 1, co positive")
+    lib = _lib.load()
+    for t, nme, shp in ((wdw, "wdw", (c, 9)), (bdw, "bdw", (c,)), (bpw, "bpw", (co,))):
+        _req(t, nme)
+        if tuple(t.shape) != shp:
+            raise RuntimeError(f"{nme}: expected {shp}, got {tuple(t.shape)}")
+    _req(wpack, "wpack")
+    want = lib.slu_shuffle_tail_packed_floats(co, c)
+    if want and wpack.numel() != want:
+        raise RuntimeError(f"wpack: {wpack.numel()} floats does not match Co={co} C={c}")
+    ho, wo = (h + stride - 1) // stride, (w + stride - 1) // stride
+    if out is None:
+        out = torch.empty((n, 2 * co, ho, wo), dtype=torch.float32, device=src.device)
+    else:
+        _req(out, "out")
+        if tuple(out.shape) != (n, 2 * co, ho, wo):
+            raise RuntimeError(f"out: expected {(n, 2 * co, ho, wo)}, got {tuple(out.shape)}")
+    d = _lib.ShuffleTailDesc()
+    if passthrough is not None:
+        _req(passthrough, "passthrough")
+        if passthrough.dim() != 4 or (passthrough.shape[0], passthrough.shape[2], passthrough.shape[3]) != (n, ho, wo) or passthrough.shape[1] < co:
+            raise RuntimeError(f"passthrough: expected [{n}, >= {co}, {ho}, {wo}], got {tuple(passthrough.shape)}")
+        if parity != 1:
+            raise RuntimeError("shuffle_tail: the pass-through half takes the even channels, so parity must be 1")
+        d.pass_, d.pass_ct = passthrough.data_ptr(), passthrough.shape[1]
+    d.src0, d.src1 = src.data_ptr(), _ptr(src2)
+    d.ct0, d.coff0, d.c0, d.ct1, d.c1 = ct0, coff, c0, ct1, c1
+    d.N, d.H, d.W, d.stride, d.Co, d.parity = n, h, w, int(stride), int(co), int(parity)
+    d.wdw, d.bdw, d.wpack, d.bpw, d.out = wdw.data_ptr(), bdw.data_ptr(), wpack.data_ptr(), bpw.data_ptr(), out.data_ptr()
+    check(lib.slu_shuffle_tail_fwd(C.byref(d), _stream()), "slu_shuffle_tail_fwd")
+    return out
