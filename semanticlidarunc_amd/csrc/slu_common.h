@@ -85,6 +85,14 @@ static inline int slu_conv_family(int ksize, int dil, int pad, F&& f) {
   return SLU_EUNSUPPORTED;
 }
 
+// The class counts the per-pixel metric kernels (one thread holds a pixel's C values in registers) are instantiated for: f receives
+// the smaller one that holds C as a std::integral_constant.  The caller has refused C > 32.
+template <class F>
+static inline void slu_class_cap(int C, F&& f) {
+  if (C <= 20) f(std::integral_constant<int, 20>{});
+  else f(std::integral_constant<int, 32>{});
+}
+
 // compile-time loop: f(std::integral_constant<int, 0>{}), ..., f(std::integral_constant<int, N - 1>{}) -- for bodies too large for `#pragma unroll`
 // whose index must stay a constant (register arrays indexed by it would otherwise move to scratch memory)
 template <class F, int... Is>

@@ -1,7 +1,7 @@
 """Mirror of the reference's ``losses.lovasz`` (src/losses/lovasz.py:6-23): same class name, constructor and
 ``forward(outputs, labels, model_act)`` contract, ``ValueError`` on an unknown ``model_act``.
 
-The arithmetic is the batched device radix sort + Jaccard scan of ``csrc/lovasz.hip``; the value equals the
+The arithmetic is the batched device radix sort (``csrc/radix_sort.hip``) + Jaccard scan of ``csrc/lovasz.hip``; the value equals the
 reference's to fp32 rounding.  The gradient w.r.t. the probabilities is a sub-gradient: over every group of
 pixels with equal error it sums to the Jaccard step across the group, J(after) - J(before), to fp32 rounding,
 which for distinct errors is the reference's gradient element by element.  Inside a group the split follows

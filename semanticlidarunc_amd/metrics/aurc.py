@@ -1,7 +1,7 @@
 """Drop-in for ``metrics.aurc`` of the reference (``src/metrics/aurc.py``): ``UncertaintyAggregator`` with the same constructor,
 ``add_batch`` / ``finalize`` and result keys, and ``compute_batch_uncertainty_metrics`` with the same arguments and result dict --
 but predictions, confidences, error flags, the sort, the risk-coverage curve, AURC, the optimal curve and the top-k% error recall
-run in HIP kernels (``csrc/lovasz.hip``); the samples stay on the GPU and nothing is copied to the host per batch.  The reservoir
+run in HIP kernels (``csrc/aurc.hip``); the samples stay on the GPU and nothing is copied to the host per batch.  The reservoir
 is this module's own policy (merge, then ``rng.choice(merged, size=reservoir_size, replace=False)``): its draws are made on the
 host with ``np.random.RandomState(seed)`` (the global ``np.random`` without a seed) exactly as the reference makes them and applied
 as an index to the device buffers, so the kept sample set is the reference's.

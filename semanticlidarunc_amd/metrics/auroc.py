@@ -1,7 +1,7 @@
 """Drop-in for ``metrics.auroc.AUROCAggregator`` of the reference (``src/metrics/auroc.py``): same constructor, ``update`` /
 ``compute`` / ``reset`` and the same sample selection -- including the numpy-seeded reservoir cap, whose index draws are made
 on the host exactly as the reference makes them and applied to the DEVICE-resident sample buffers -- but probabilities,
-scores, error flags, the sort and the ROC integral run in HIP kernels (``csrc/lovasz.hip``) and nothing is copied to the host
+scores, error flags, the sort and the ROC integral run in HIP kernels (``csrc/auroc.hip``) and nothing is copied to the host
 per batch.  ``compute`` returns ``(auroc, curves, fig)`` with ``fig`` None unless ``save_plot_path`` is given (the reference
 raises UnboundLocalError in that case, auroc.py:147-164)."""
 from __future__ import annotations

@@ -63,6 +63,29 @@ def test_sort_and_integral_exact_on_large_tie_free_input(cuda):
     assert a_inf == 0.75
 
 
+def test_key_order_of_signed_zeros_and_nan(cuda):
+    """The AUROC key keeps -0.0 and +0.0 apart (the AURC key folds them) and ranks the positive quiet NaN above +inf; the sorted
+    list gives every score back bit for bit."""
+    n = 2049                                          # one key in a second sort tile
+    rng = np.random.default_rng(16)
+    values = torch.tensor([-1.5, -0.0, 0.0, 0.25, float("inf"), torch.nan], dtype=torch.float32)
+    scores = values[_t(rng.integers(0, len(values), n))]
+    err = _t((rng.random(n) < 0.4).astype(np.uint8))
+    u = scores.numpy().view(np.uint32)
+    asc = np.where(u >> 31, ~u, u | np.uint32(0x80000000))
+    order = np.argsort(~asc, kind="stable")
+    want_u, want_e = u[order], err.numpy()[order]
+    assert want_u[0] == 0x7FC00000 and {0x00000000, 0x80000000} <= set(want_u.tolist())       # NaN first; both zeros drawn
+    first_neg_zero = int(np.argmax(want_u == 0x80000000))
+    assert np.all(want_u[:first_neg_zero] != 0x80000000) and want_u[first_neg_zero - 1] == 0        # +0.0 right before -0.0
+    a, pos, neg, ss, se = ops.auroc_from_samples(scores.to(cuda), err.to(cuda), want_sorted=True)
+    assert np.array_equal(ss.cpu().numpy().view(np.int32), want_u.view(np.int32))
+    assert np.array_equal(se.cpu().numpy(), want_e)
+    assert pos == int(err.sum()) and neg == n - pos
+    pos_before = np.cumsum(want_e, dtype=np.int64) - want_e
+    assert abs(a - int(pos_before[want_e == 0].sum()) / (pos * neg)) <= 1e-12
+
+
 def test_scores_full_size_and_argument_checks(cuda):
     gen = torch.Generator().manual_seed(8)
     labs = torch.randint(0, 20, (2, 64, 2048), generator=gen)

@@ -1,4 +1,4 @@
-"""GPU: the Lovasz radix sort, Jaccard scan and gradient of csrc/lovasz.hip at the sizes where their tail logic works -- more than
+"""GPU: the radix sort of csrc/radix_sort.hip, the Jaccard scan and gradient of csrc/lovasz.hip at the sizes where their tail logic works -- more than
 one 2048-key tile with a partial last tile, 2 to 32 classes, absent classes between present ones -- and on inputs with ties
 (saturated probabilities: errors exactly 0 and exactly 1); then the stability of the shared sort through the AUROC entry point.
 

@@ -10,7 +10,8 @@ object, not with the kernel) is masked.  Verdicts: `same`; `commuted` = same len
 differing lines permuted; `CHANGED` with both instruction counts.  --launched: kernel names as rocprofv3 prints them (a JSON object keyed
 by name or a --stats CSV); a CHANGED kernel of that set, or (default match only) any CHANGED ring3_h8_kernel / tail2_h8_kernel, makes the
 exit status 1.  For the fp32-storage conv / wgrad kernels: --match kernel --launched profiles/r05/coverage_recorded_names.json --launched
-profiles/r03/train_kernel_stats.csv."""
+profiles/r03/train_kernel_stats.csv.  For any other refactor: --match kernel (every kernel of the library); a kernel the change renamed shows as
+`only in OLD` / `only in NEW` and is compared pairwise with kernels() and verdict() of this module (profiles/r16)."""
 import collections
 import csv
 import json
