@@ -311,7 +311,7 @@ int slu_head_mc_f32(const float* x, int T, int B, int Cin, int HW, const float* 
                     const float* gn_beta, int groups, int relu, const float* w, const float* bias, int C, float eps, float* p_bar, float* h_norm,
                     float* mi_norm, int64_t* preds, slu_stream_t stream);
 
-/* ---- fp16 channel-blocked ("h8") inference path: BASELINE.json configs[2],[4] (half-precision storage, fp32 accumulate): conv2d_h8.hip ----
+/* ---- fp16 channel-blocked ("h8") inference path: BASELINE.json configs[2],[4] (half-precision storage, fp32 accumulate): conv2d_h8.hip (dispatch) and the kernel families of conv_h8.h ----
  * Activation layout: x[N][G = ceil(C/8)][H][W][8] fp16, pad channels = 0, base pointers 16-byte aligned.
  * Replaces the same reference arithmetic as slu_conv2d_fwd (SalsaNext.py:25-39,73-109,142-170,197-215) with fp16 operands. */
 typedef struct slu_h8_src {

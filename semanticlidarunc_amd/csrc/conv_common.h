@@ -316,7 +316,7 @@ inline long long wg_count(const ConvArgs& a, int th, int mblk) {
 // Tile choice: the biggest tile that still gives >= 2 workgroups per CU (256 CUs); below that,
 // shrink rows first (TH 8 -> 4), then the channel tile, so small feature maps still fill the chip.
 inline int choose_cfg(const ConvArgs& a) {
-  static const int forced = [] { const char* e = getenv("SLU_CONV_CFG"); return e ? atoi(e) : -1; }();      // development override: 0..4 = TileCfg
+  static const int forced = slu_env_int("SLU_CONV_CFG", -1);      // development override: 0..4 = TileCfg
   if (forced >= 0 && forced <= 4 && !(forced == M128_TH4 && a.nmblk < 4) && !((forced == M64_TH8 || forced == M64_TH4) && a.nmblk < 2) &&
       !((forced == M32_TH8 || forced == M64_TH8) && a.H < 8))
     return forced;

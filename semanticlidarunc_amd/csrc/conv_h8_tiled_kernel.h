@@ -1,5 +1,5 @@
-// The tiled h8 conv kernel's definition (see "Tiled kernel" in conv2d_h8.hip, which includes this file and owns everything it names).
-// No include guard: conv2d_h8.hip includes it once per kernel symbol, with
+// The tiled h8 conv kernel's definition (see "Tiled kernel" in conv_h8_tiled.hip, which includes this file; what it names is there and in conv_h8.h).
+// No include guard: conv_h8_tiled.hip includes it once per kernel symbol, with
 //   H8_TILED_KERNEL   the symbol: conv_h8_kernel, conv_h8_late_kernel
 //   H8_TILED_LATE     false: out = [resid +] bn(act(conv + bias));  true: out = act(conv + bias + resid), the activation after the residual add
 // Two symbols from one text rather than one more template parameter or a shared __device__ body: either of those changes the name or the

@@ -5,7 +5,7 @@
 //
 // Unfused these are two kernels moving 7 tensor passes (read a2, write a3; read a1, a2, a3, resid, write out); here a3 never
 // leaves the CU: 4 passes (a1, a2, resid, out), both layers HBM-bound at full resolution.  Structure = the persistent LDS-DMA
-// kernel of conv2d_h8.hip (round-robin tiles, one K-step = 16 channels per chunk, double-buffered, the next tile's first chunk
+// kernel of conv_h8_tiled.hip (round-robin tiles, one K-step = 16 channels per chunk, double-buffered, the next tile's first chunk
 // in flight across the epilogues):
 //   chunks 0 .. nks-1      : a2 tile (halo 1) -> 4 dilated taps into acc3  +  the centre tap (1x1 over a2) into acc_out
 //   chunks nks .. 2 nks-1  : a1 tile          -> the centre tap (1x1 over a1) into acc_out
@@ -16,7 +16,6 @@
 // -- the a3 image takes C * TH * 128 B = 64 KB in each.  W3RES: the 1x1 weights over a3 stay resident in LDS (C <= 64); otherwise
 // they stream through the chunk pipeline as NKS more (weights-only) chunks, for which the LDS has no room at C = 128.
 #include "h8_common.h"
-#include <cstdlib>
 
 namespace {
 
@@ -652,10 +651,10 @@ static int conv_tail_dispatch(const slu_conv_tail_h8_desc* d, const SluEmit& e) 
   a.out = reinterpret_cast<uint2*>(d->out);
   a.N = d->N; a.H = d->H; a.W = d->W; a.G = d->C / 8;
 #ifdef SLU_H8_AB
-  static const int dbg = [] { const char* v = getenv("SLU_TAIL_DBG"); return v ? atoi(v) : 0; }();
+  static const int dbg = slu_env_int("SLU_TAIL_DBG", 0);
   a.dbg = dbg;
 #endif
-  static const bool v1 = [] { const char* v = getenv("SLU_TAIL_V1"); return v && v[0] == '1'; }();     // A/B switch: the round-1 kernel
+  static const bool v1 = slu_env_int("SLU_TAIL_V1", 0) == 1;     // A/B switch: the round-1 kernel
   if (d->sc_x) {      // shortcut mode
     if (d->resid || !d->sc_w || !slu_conv_tail_h8_shortcut_supported(d->C, d->sc_cin) || (((uintptr_t)d->sc_x | (uintptr_t)d->sc_w) & 15)) return SLU_EINVAL;
     if (d->sc_hasact && !(d->sc_slope >= 0.0f && d->sc_slope <= 1.0f)) return SLU_EINVAL;

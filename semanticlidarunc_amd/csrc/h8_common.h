@@ -1,4 +1,4 @@
-// Vocabulary shared by the half-precision ("h8") kernels and their launchers: conv2d_h8.hip, conv_tail_h8.hip, ctx_block_h8.hip, head_mc_h8.hip,
+// Vocabulary shared by the half-precision ("h8") kernels and their launchers: the conv families of conv_h8.h, conv_tail_h8.hip, ctx_block_h8.hip, head_mc_h8.hip,
 // layout_h8.hip, fpn_h8.hip, fpn_opt_h8.hip.
 // Every helper is forced inline, and its form (what comes by value, by reference, as a macro) is the one with which the kernels compile
 // to the instruction streams of the hand-written copies they replace: check a change here with tools/h8_isa_diff.py (profiles/r07).

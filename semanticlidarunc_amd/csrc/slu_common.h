@@ -4,6 +4,7 @@
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <utility>
 #include "slu.h"
 
@@ -33,6 +34,12 @@ __attribute__((format(printf, 2, 3))) static inline int slu_emit_name(const SluE
   return len >= 0 && (size_t)len < e.n ? SLU_OK : SLU_EINVAL;
 }
 static inline const char* slu_tf(bool b) { return b ? "true" : "false"; }
+
+// An integer switch of the environment, `dflt` when unset.  Call sites keep the value in a `static const`: read once per process.
+static inline int slu_env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
 
 // Ablation switches (a kernel drops its DMAs or MFMAs and computes WRONG results, to see what the rest costs) exist only in the
 // development build (-DSLU_H8_AB, tools/h8_ab.py): there the host reads SLU_GEMM_DBG / SLU_TAIL_DBG into the argument structs' `dbg`;

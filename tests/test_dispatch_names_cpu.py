@@ -21,8 +21,10 @@ def _name(fn, desc, n=96):
     return rc, buf.value.decode()
 
 
-def _h8_desc(fam, parts, cout, n, h, w, scales=False, resid=True, out_f32=False, nbatch_last=0, bias=True, bn=True, act=True, big=False):
-    """The descriptor test_gpu_h8._conv_case hands to h8.conv2d_h8 for these options."""
+def _h8_desc(fam, parts, cout, n, h, w, scales=False, resid=True, out_f32=False, nbatch_last=0, bias=True, bn=True, act=True, big=False,
+             late=False, shuffle=False):
+    """The descriptor test_gpu_h8._conv_case hands to h8.conv2d_h8 for these options.  late: the activation after the residual add
+    (act_after_resid); shuffle: source 0 is read through PixelShuffle in place (4x the stored blocks, at half the size)."""
     d = _lib.ConvH8Desc()
     for i, c in enumerate(parts):
         g = (c + 7) // 8
@@ -36,6 +38,9 @@ def _h8_desc(fam, parts, cout, n, h, w, scales=False, resid=True, out_f32=False,
     d.bn_a = d.bn_b = PTR if bn else None
     d.resid, d.out = PTR if (resid and not out_f32) else None, PTR
     d.out_f32_nchw = 1 if out_f32 else 0
+    d.act_after_resid = 1 if late else 0
+    if shuffle:
+        d.src[0].G, d.src[0].shuffle = 4 * d.src[0].G, 1
     return d
 
 
@@ -94,6 +99,21 @@ def test_tail_shape_selects_its_instantiation(c, resid, shortcut, name):
         d.sc_x = d.sc_w = d.sc_bias = PTR
         d.sc_cin, d.sc_hasact, d.sc_slope = 32, 1, 0.01
     assert _name("slu_conv_tail_h8_kernel_name", d) == (0, name)
+
+
+@pytest.mark.parametrize("what,fam,parts,cout,opts", [
+    ("2x2 / dil 1 with multipliers", (2, 1, 1), [64], 64, dict(scales=True, resid=False)),
+    ("a geometry no family has", (3, 3, 3), [64], 64, dict()),
+    ("late activation without a residual", (3, 1, 1), [64], 64, dict(late=True, resid=False, bn=False)),
+    ("late activation on a 1x1", (1, 1, 0), [64], 64, dict(late=True, bn=False)),
+    ("late activation with a folded BatchNorm", (3, 1, 1), [64], 64, dict(late=True)),
+    ("shuffled source 0 on a 1x1", (1, 1, 0), [16, 64], 32, dict(shuffle=True, scales=True, resid=False)),
+    ("shuffled source, no multipliers, not a ring3 shape", (3, 1, 1), [16, 64], 128, dict(shuffle=True, resid=False)),
+    ("fp32 output of a 3x3", (3, 1, 1), [64], 20, dict(out_f32=True)),
+], ids=lambda v: v.replace(" ", "_") if isinstance(v, str) else "")
+def test_h8_dispatch_refuses(what, fam, parts, cout, opts):
+    """The refusals that sit between the families' gates: each must come back as SLU_EUNSUPPORTED, not as some kernel's name."""
+    assert _name("slu_conv2d_h8_kernel_name", _h8_desc(fam, parts, cout, 2, 64, 1024, **opts)) == (SLU_EUNSUPPORTED, "")
 
 
 def test_name_call_returns_the_status_of_the_launch():

@@ -1,7 +1,7 @@
 """GPU: one oracle case for every conv kernel instantiation the benchmark and the training step launch, at a shape that
 selects it, and a coverage test that keeps that true as the dispatch rules change.
 
-The dispatchers (choose_h8 in csrc/conv2d_h8.hip, choose_cfg in csrc/conv_common.h, launch_h8_m128) choose the tile from the
+The dispatchers (choose_h8 in csrc/conv_h8_tiled.hip, choose_cfg in csrc/conv_common.h, launch_h8_m128) choose the tile from the
 launch size, so the configurations of the full-size runs (>= 256 / 512 / 3 072 workgroups) are never reached by the small shapes of
 test_gpu_h8.py / test_gpu_conv.py / test_gpu_f16x3.py.  Each row of the tables below names the instantiation its shape must select
 (read back from ops.TIMING, i.e. slu_conv2d_h8_kernel_name / slu_conv2d_kernel_name: the launch's own dispatch with a leaf that

@@ -1,4 +1,4 @@
-"""GPU: gemm1x1_h8_kernel's epilogue with the residual loaded ahead (conv2d_h8.hip): whole 16-byte residual records from untracked loads,
+"""GPU: gemm1x1_h8_kernel's epilogue with the residual loaded ahead (gemm1x1_h8.hip): whole 16-byte residual records from untracked loads,
 the first two M-blocks issued before the last chunk's staging burst and retired by a counted wait, the rest issued at the top of the epilogue.
 
 Reference and bar are those of test_gpu_h8._conv_case: oracle.salsanext.fused_conv on the same fp16-rounded operands,

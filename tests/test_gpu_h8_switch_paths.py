@@ -4,7 +4,7 @@ aborts or times out fails the test, which then starts nothing further.
 
 SLU_TAIL_V1=1   the round-1 fused tail, tail_h8_kernel (conv_tail_h8.hip): the child runs test_gpu_h8_tail._case -- against the unfused h8
                 kernels at 2e-3 and the fp32 CPU oracle at 3e-3 of the output scale -- and checks that the launch names that kernel.
-SLU_H8_ORDER=0  conv_h8_kernel's contiguous tile runs (conv2d_h8.hip): the two orders deal the same tiles to different workgroups and the
+SLU_H8_ORDER=0  conv_h8_kernel's contiguous tile runs (conv_h8_tiled.hip): the two orders deal the same tiles to different workgroups and the
                 arithmetic per tile is the same, so the child's raw h8 outputs must equal the parent's (default order) byte for byte; the
                 parent's own result is held to the single-kernel bar of test_gpu_h8.py against oracle.salsanext.fused_conv."""
 import os

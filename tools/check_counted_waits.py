@@ -10,7 +10,7 @@ a register behind a counted wait with N > 0 is caught too.  The scan is linear o
 
     python tools/check_counted_waits.py [path/to/libslu_hip.so] [--kernels REGEX]
 
---kernels REGEX scans the kernels whose (mangled) name matches REGEX as well.  gemm1x1_h8_kernel (conv2d_h8.hip; not its A/B form
+--kernels REGEX scans the kernels whose (mangled) name matches REGEX as well.  gemm1x1_h8_kernel (gemm1x1_h8.hip; not its A/B form
 gemm1x1_h8_kernel_v1) has rules of its own: its residual epilogue must not wait in full, so every `vmcnt(0)` has to be, by what follows it
 within three instructions, one of the set-up (a `ds_write` of an epilogue constant: the tile loops fill LDS by DMA alone), the chunk wait of a
 ring of depth 2 (D = 2: `vmcnt(0)`, `lgkmcnt(0)`, `s_barrier`) or the exit's (`s_endpgm`, or the branch to it from the first of the kernel's

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Where the streaming 1x1 h8 kernel spends its shader clocks (development aid; library built with -DSLU_H8_PROF, see tools/h8_phase_prof.py):
+"""Where the streaming 1x1 h8 kernel spends its shader clocks (development aid; library built with -DSLU_H8_PROF, see tools/h8_phase_prof.py: conv1x1_h8.h is compiled in that unit):
     python tools/h8_1x1_prof.py <libslu_prof.so> [N]
 Per layer: mean clocks of wave 0 of a workgroup per phase (input loads issued + first barrier | weight staging | second barrier |
 MFMAs incl. waiting for the inputs | epilogue)."""

@@ -2,7 +2,7 @@
 """Where the tiled h8 kernel spends its shader clocks (development aid).  Needs a library built with -DSLU_H8_PROF:
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -DSLU_H8_PROF -Iinclude -Isemanticlidarunc_amd/csrc \
-          -c semanticlidarunc_amd/csrc/conv2d_h8.hip -o build_prof/conv2d_h8.o     # + link with the other objects
+          -c semanticlidarunc_amd/csrc/conv_h8_tiled.hip -o build_prof/conv_h8_tiled.o     # + link with the other objects
     python tools/h8_phase_prof.py build_prof/libslu_hip.so [N]
 
 Prints, per layer, the mean clocks of wave 0 of a workgroup in each phase (wait for DMA | barrier | DMA issue | LDS+MFMA | epilogue)."""

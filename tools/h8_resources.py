@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Register / scratch summary of the kernels in a `-Rpass-analysis=kernel-resource-usage` log (development aid):
-    hipcc ... -Rpass-analysis=kernel-resource-usage -c conv2d_h8.hip 2> log ; python tools/h8_resources.py log [name-substring ...]
+    hipcc ... -Rpass-analysis=kernel-resource-usage -c conv_h8_tiled.hip 2> log ; python tools/h8_resources.py log [name-substring ...]
     python tools/h8_resources.py --diff old.log new.log      every kernel whose resource lines differ between two logs (exit status 1 if any)"""
 import collections
 import re

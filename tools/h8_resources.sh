@@ -1,10 +1,10 @@
 #!/bin/bash
-# Development aid: compile conv2d_h8.hip with extra flags ($@) into build_ab/ and list registers / spills of the conv_h8_kernel instantiations
+# Development aid: compile conv_h8_tiled.hip (or $H8_SRC) with extra flags ($@) into build_ab/ and list registers / spills of the conv_h8_kernel instantiations
 # whose mangled name contains $H8_FILTER (default: the 8-wave 128-channel configuration).
 set -e
 cd "$(dirname "$0")/.."
 mkdir -p build_ab
-( cd semanticlidarunc_amd/csrc && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC "$@" -I../../include -I. -c ${H8_SRC:-conv2d_h8.hip} -o ../../build_ab/${H8_OBJ:-conv2d_h8.o} -Rpass-analysis=kernel-resource-usage 2> ../../build_ab/res.txt ) || { tail -30 build_ab/res.txt; exit 1; }
+( cd semanticlidarunc_amd/csrc && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC "$@" -I../../include -I. -c ${H8_SRC:-conv_h8_tiled.hip} -o ../../build_ab/${H8_OBJ:-conv_h8_tiled.o} -Rpass-analysis=kernel-resource-usage 2> ../../build_ab/res.txt ) || { tail -30 build_ab/res.txt; exit 1; }
 python3 - <<'PY'
 import os, re
 t = open('build_ab/res.txt').read()
