@@ -15,6 +15,7 @@
 //   after the sort:  the sort's flag prefix (errors per tile)  +  group starts per tile and their scan over tiles
 //                    -> one pass: e_i and the rank of every group start, compacted (s_k, R_k [, cov_k]), recall numerators
 //                    -> trapezoid + optimal-curve partials -> final sum.
+#include "class_column.h"
 #include "radix_sort.h"
 
 namespace {
@@ -45,17 +46,9 @@ __global__ __launch_bounds__(256) void aurc_sample_kernel(const float* __restric
   const size_t npix = (size_t)B * HW;
   const size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (pix >= npix) return;
-  const int b = (int)(pix / HW);
-  const int hw = (int)(pix - (size_t)b * HW);
-  const float* src = probs + (size_t)b * C * HW + hw;
-  float p[CMAX];
-#pragma unroll
-  for (int c = 0; c < CMAX; ++c) p[c] = c < C ? src[(size_t)c * HW] : 0.0f;
-  float best = -INFINITY;
-  int arg = 0;
-#pragma unroll
-  for (int c = 0; c < CMAX; ++c)
-    if (c < C && p[c] > best) { best = p[c]; arg = c; }        // first argmax of the probabilities as given
+  float p[CMAX], best;
+  slu_load_column(probs + slu_pixel(pix, C, HW).col, C, HW, 0.0f, p);
+  const int arg = slu_first_argmax(p, C, best);                // of the probabilities as given
   float conf;
   if (form == 0) {
     conf = best;
@@ -77,7 +70,7 @@ __global__ __launch_bounds__(256) void aurc_sample_kernel(const float* __restric
   }
   const int64_t lab = labels[pix];
   conf_out[pix] = conf;
-  flag_out[pix] = lab == ignore ? (uint8_t)2 : (uint8_t)(arg != lab ? 1 : 0);
+  flag_out[pix] = slu_label_ignored(lab, ignore) ? (uint8_t)2 : (uint8_t)(arg != lab ? 1 : 0);
 }
 
 __device__ __forceinline__ bool aurc_group_start(const unsigned* __restrict__ keys, long long i, long long n) {
@@ -262,8 +255,7 @@ extern "C" int slu_aurc_samples(const float* probs, const int64_t* labels, const
   if (C > 32) return SLU_EUNSUPPORTED;
   const int form = use_max_prob_confidence ? 0 : (ent_mc ? 1 : 2);
   const float logc = (float)log((double)C);
-  const size_t npix = (size_t)B * HW;
-  const unsigned nb = (unsigned)((npix + 255) / 256);
+  const unsigned nb = slu_grid_per_pixel((size_t)B * HW);
   slu_class_cap(C, [&](auto cmax) {
     hipLaunchKernelGGL(aurc_sample_kernel<decltype(cmax)::value>, dim3(nb), dim3(256), 0, slu_stream(stream), probs, labels, ent_mc, B, C, HW,
                        ignore_index, form, logc, conf, flags);

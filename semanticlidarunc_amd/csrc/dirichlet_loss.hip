@@ -11,28 +11,11 @@
 //                                                                         max(sum of the weights, 1); param gamma
 //   kind 6  WrongLowEvidence         losses/regularizers.py:218-289       gate * relu(ln a0 - ln(C + s_low + eps))^2 on wrong pixels, averaged over
 //                                                                         sum(gate) (second accumulator); params s_low, margin, soft_margin_k
-// One lane per pixel, class axis in registers, fp32 per pixel, fp64 sums: HBM-bound (4 C bytes in; backward 4 C in + 4 C out).
-#include "slu_common.h"
+// One lane per pixel, class axis in registers (class_column.h; digamma_pos / trigamma_pos: the arguments are any alpha > 0), fp32 per
+// pixel, fp64 sums: HBM-bound (4 C bytes in; backward 4 C in + 4 C out).
+#include "class_column.h"
 
 namespace {
-
-__device__ __forceinline__ float digamma_pos(float x) {       // x > 0: recurrence to x >= 6, then the asymptotic series
-  float r = 0.0f;
-#pragma unroll
-  for (int i = 0; i < 6; ++i)
-    if (x < 6.0f) { r -= 1.0f / x; x += 1.0f; }
-  const float inv = 1.0f / x, inv2 = inv * inv;
-  return r + logf(x) - 0.5f * inv - inv2 * (1.0f / 12.0f - inv2 * (1.0f / 120.0f - inv2 * (1.0f / 252.0f)));
-}
-
-__device__ __forceinline__ float trigamma_pos(float x) {      // psi'(x) = psi'(x + 1) + 1 / x^2; asymptotic series for x >= 6
-  float r = 0.0f;
-#pragma unroll
-  for (int i = 0; i < 6; ++i)
-    if (x < 6.0f) { r += 1.0f / (x * x); x += 1.0f; }
-  const float inv = 1.0f / x, inv2 = inv * inv;
-  return r + inv * (1.0f + 0.5f * inv + inv2 * (1.0f / 6.0f - inv2 * (1.0f / 30.0f - inv2 * (1.0f / 42.0f))));
-}
 
 struct LossParams { float p[6]; };
 
@@ -50,11 +33,10 @@ __global__ __launch_bounds__(256) void dirichlet_loss_kernel(const float* __rest
   double lsum = 0.0, lsum2 = 0.0;
   unsigned lcnt = 0;
   for (size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x; pix < npix; pix += (size_t)gridDim.x * blockDim.x) {
-    const int b = (int)(pix / HW);
-    const size_t hw = pix - (size_t)b * HW;
+    const size_t col = slu_pixel(pix, C, HW).col;
     const int64_t y64 = labels[pix];
-    const bool valid = !(has_ignore && y64 == ignore) && y64 >= 0 && y64 < C;
-    float* dst = BWD ? grad + (size_t)b * C * HW + hw : nullptr;
+    const bool valid = !slu_label_ignored(y64, has_ignore, ignore) && slu_label_in_range(y64, C);
+    float* dst = BWD ? grad + col : nullptr;
     if (!valid) {
       if constexpr (BWD) {
 #pragma unroll
@@ -64,12 +46,11 @@ __global__ __launch_bounds__(256) void dirichlet_loss_kernel(const float* __rest
       continue;
     }
     const int y = (int)y64;
-    const float* src = alpha + (size_t)b * C * HW + hw;
     float a[CMAX];
+    slu_load_column(alpha + col, C, HW, 0.0f, a);
     float a0 = 0.0f, ay = 0.0f;
 #pragma unroll
     for (int c = 0; c < CMAX; ++c) {
-      a[c] = c < C ? src[(size_t)c * HW] : 0.0f;
       a0 += a[c];
       ay = (c == y) ? a[c] : ay;
     }
@@ -186,7 +167,7 @@ __global__ __launch_bounds__(256) void dirichlet_loss_kernel(const float* __rest
     } else if (kind == 6) {
       const float s_low = prm.p[0], margin = prm.p[1], kk = prm.p[2];
       const float d = fmaxf(a0, eps);
-      float pmax = -1.0f;
+      float pmax = -1.0f;                                          // not slu_first_argmax: it starts at -inf, this at -1 (a column of negative alpha gives 0 here)
       int pred = 0;
 #pragma unroll
       for (int c = 0; c < CMAX; ++c)
@@ -247,17 +228,14 @@ __global__ __launch_bounds__(256) void dirichlet_loss_kernel(const float* __rest
     ++lcnt;
   }
   if constexpr (!BWD) {
-    lsum = wave_sum(lsum);
-    lsum2 = wave_sum(lsum2);
-    lcnt = (unsigned)wave_sum((float)lcnt);
-    if ((threadIdx.x & 63) == 0) { s_sum[threadIdx.x >> 6] = lsum; s_sum2[threadIdx.x >> 6] = lsum2; s_cnt[threadIdx.x >> 6] = lcnt; }
+    slu_stage_wave_total(wave_sum(lsum), s_sum);
+    slu_stage_wave_total(wave_sum(lsum2), s_sum2);
+    slu_stage_wave_total((unsigned)wave_sum((float)lcnt), s_cnt);
     __syncthreads();
     if (threadIdx.x == 0) {
-      double t = 0.0, t2 = 0.0;
-      unsigned long long n = 0;
-      for (int w = 0; w < 4; ++w) { t += s_sum[w]; t2 += s_sum2[w]; n += s_cnt[w]; }
-      if (n) { atomicAdd(sum, t); atomicAdd(count, n); }
-      if (n && sum2) atomicAdd(sum2, t2);
+      const unsigned long long n = slu_block_total(s_cnt);
+      if (n) { atomicAdd(sum, slu_block_total(s_sum)); atomicAdd(count, n); }
+      if (n && sum2) atomicAdd(sum2, slu_block_total(s_sum2));
     }
   }
 }
@@ -265,17 +243,12 @@ __global__ __launch_bounds__(256) void dirichlet_loss_kernel(const float* __rest
 template <bool BWD>
 int launch(const float* alpha, const int64_t* labels, int B, int C, int HW, int kind, const LossParams& prm, float eps, int has_ignore, int64_t ignore,
            double* sum, double* sum2, int64_t* count, const float* gscale, float* grad, hipStream_t st) {
-  const size_t npix = (size_t)B * HW;
-  size_t nb = (npix + 255) / 256;
-  if (!BWD && nb > 2048) nb = 2048;
-  if (BWD && nb > 65535u * 16) nb = 65535u * 16;
+  const unsigned nb = slu_grid_1d((size_t)B * HW, BWD ? 65535u * 16 : 2048);
   auto cnt = reinterpret_cast<unsigned long long*>(count);
-  if (C <= 20)
-    hipLaunchKernelGGL((dirichlet_loss_kernel<20, BWD>), dim3((unsigned)nb), dim3(256), 0, st, alpha, labels, B, C, HW, kind, prm, eps, has_ignore,
-                       ignore, sum, sum2, cnt, gscale, grad);
-  else
-    hipLaunchKernelGGL((dirichlet_loss_kernel<32, BWD>), dim3((unsigned)nb), dim3(256), 0, st, alpha, labels, B, C, HW, kind, prm, eps, has_ignore,
-                       ignore, sum, sum2, cnt, gscale, grad);
+  slu_class_cap(C, [&](auto cmax) {
+    hipLaunchKernelGGL((dirichlet_loss_kernel<decltype(cmax)::value, BWD>), dim3(nb), dim3(256), 0, st, alpha, labels, B, C, HW, kind, prm, eps,
+                       has_ignore, ignore, sum, sum2, cnt, gscale, grad);
+  });
   SLU_CHECK_LAUNCH();
 }
 

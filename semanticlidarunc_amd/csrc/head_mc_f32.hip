@@ -3,7 +3,7 @@
 //                                                              slu_groupnorm_stats)
 //   logits_t = W v_t + b                                      (semanticFCN_opt.py:296, a 1x1 conv over the UpsampleBlock output)
 //   p_t      = exp(log_softmax(logits_t));  p_bar = mean_t p_t;  H = -sum clamp(p_bar) log clamp(p_bar) / ln C
-//   MI       = max((H_bar - mean_t H[p_t]) / ln C, 0);  preds = argmax_c p_bar          (mc_reduce_kernel, pointwise.hip)
+//   MI       = max((H_bar - mean_t H[p_t]) / ln C, 0);  preds = argmax_c p_bar          (mc_reduce_kernel, uncertainty.hip)
 // Unfused, every pass writes the normalised tensor and C fp32 logit maps that the next kernel reads back; here x is read once and nothing
 // but the four results is written.  A wave owns 128 pixels of one scan and walks its T passes.  The product runs on
 // v_mfma_f32_32x32x2_f32 (== a k-ordered fmaf chain): classes padded to M = 32, pixels on N, channels in K-steps of 2; lane l feeds channel

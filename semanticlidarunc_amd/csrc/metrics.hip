@@ -1,7 +1,7 @@
-// On-device metric accumulators: confusion matrix (IoU) and top-label calibration bins (ECE),
-// plus the softmax + NLL reduction of the SalsaNext loss.  Integer counts are exact (LDS integer
+// On-device metric accumulators: confusion matrix (IoU), top-label calibration bins and samples (ECE), the
+// uncertainty-accuracy samples and histograms, samples grouped by class.  Integer counts are exact (LDS integer
 // histograms -> one 64-bit global atomic per non-empty bin per workgroup).
-#include "slu_common.h"
+#include "class_column.h"
 
 namespace {
 
@@ -37,20 +37,12 @@ __global__ __launch_bounds__(256) void ece_kernel(const float* __restrict__ prob
   const size_t npix = (size_t)B * HW;
   for (size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x; pix < npix; pix += (size_t)gridDim.x * blockDim.x) {
     const int64_t lab = labels[pix];
-    if (lab == ignore_index) continue;
-    const int b = (int)(pix / HW);
-    const int hw = (int)(pix - (size_t)b * HW);
-    const float* src = probs + (size_t)b * C * (size_t)HW + hw;
-    float s = 0.0f, best = -INFINITY;
-    int arg = 0;
-#pragma unroll
-    for (int c = 0; c < CMAX; ++c)
-      if (c < C) {
-        const float p = fmaxf(src[(size_t)c * HW], 0.0f);
-        s += p;
-        if (p > best) { best = p; arg = c; }
-      }
-    float conf = best / fmaxf(s, 1e-12f);
+    if (slu_label_ignored(lab, ignore_index)) continue;            // a label outside [0, C) stays: it counts as wrong
+    float p[CMAX];
+    const float den = slu_mode_column(probs + slu_pixel(pix, C, HW).col, C, HW, 2, 1e-12f, p);      // 'probs' mode
+    float best;
+    const int arg = slu_first_argmax(p, C, best);
+    float conf = best / den;
     conf = fminf(fmaxf(conf, 0.0f), 1.0f);
     int bin = (int)(conf * (float)n_bins);
     bin = bin < 0 ? 0 : (bin > n_bins - 1 ? n_bins - 1 : bin);
@@ -69,56 +61,6 @@ __global__ __launch_bounds__(256) void ece_kernel(const float* __restrict__ prob
     }
 }
 
-// models/trainer.py:511-514 : probs = softmax(logits); -log(max(probs[y], clamp)) summed over pixels
-template <int CMAX>
-__global__ __launch_bounds__(256) void softmax_nll_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
-                                                          int B, int C, int HW, float clampv, float* __restrict__ probs,
-                                                          double* __restrict__ nll_sum) {
-  __shared__ double s_part[4];
-  const size_t npix = (size_t)B * HW;
-  double local = 0.0;
-  for (size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x; pix < npix; pix += (size_t)gridDim.x * blockDim.x) {
-    const int b = (int)(pix / HW);
-    const int hw = (int)(pix - (size_t)b * HW);
-    const float* src = logits + (size_t)b * C * (size_t)HW + hw;
-    float x[CMAX];
-    float m = -INFINITY;
-#pragma unroll
-    for (int c = 0; c < CMAX; ++c) {
-      x[c] = (c < C) ? src[(size_t)c * HW] : -INFINITY;
-      m = fmaxf(m, x[c]);
-    }
-    float se = 0.0f;
-#pragma unroll
-    for (int c = 0; c < CMAX; ++c)
-      if (c < C) { x[c] = expf(x[c] - m); se += x[c]; }
-    const int64_t lab = labels[pix];
-    float py = 1.0f;
-#pragma unroll
-    for (int c = 0; c < CMAX; ++c)
-      if (c < C) {
-        const float p = x[c] / se;
-        if (probs) probs[((size_t)b * C + c) * HW + hw] = p;
-        if ((int64_t)c == lab) py = p;
-      }
-    if (lab >= 0 && lab < C) local += (double)(-logf(fmaxf(py, clampv)));
-  }
-  local = wave_sum(local);
-  if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = local;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double tot = 0.0;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) tot += s_part[w];
-    atomicAdd(nll_sum, tot);
-  }
-}
-
-inline unsigned grid_for(size_t n, unsigned cap) {
-  const size_t nb = (n + 255) / 256;
-  return (unsigned)(nb > cap ? cap : (nb ? nb : 1));
-}
-
-
 // models/evaluator.py:659-673 (UncertaintyAccuracyAggregator.update): u = clamp(uncertainty, 0, 1), flag = label == pred, pixels whose
 // label is in ignore_ids dropped.  flag: 0 wrong, 1 correct, 2 ignored.
 __global__ __launch_bounds__(256) void ua_samples_kernel(const int64_t* __restrict__ labels, const int64_t* __restrict__ preds,
@@ -134,14 +76,18 @@ __global__ __launch_bounds__(256) void ua_samples_kernel(const int64_t* __restri
 }
 
 // models/evaluator.py:733-739: np.histogram(u, bins=edges) and the same with weights = correct, for arbitrary strictly increasing
-// float32 edges: bin i = [e_i, e_{i+1}), the last one closed, values outside [e_0, e_K] dropped.  K <= 256.
-__global__ __launch_bounds__(256) void binned_counts_kernel(const float* __restrict__ u, const uint8_t* __restrict__ correct, size_t n,
-                                                            const float* __restrict__ edges, int K, unsigned long long* __restrict__ count,
-                                                            unsigned long long* __restrict__ n_correct) {
+// float32 edges: bin i = [e_i, e_{i+1}), the last one closed, values outside [e_0, e_K] dropped.  K <= 256.  SUM_U: also the per-bin
+// sum of u (weights = u, metrics/ece.py:136-140), through an LDS float atomic per sample.
+template <bool SUM_U>
+__device__ __forceinline__ void binned_body(const float* __restrict__ u, const uint8_t* __restrict__ correct, size_t n, const float* __restrict__ edges,
+                                            int K, unsigned long long* __restrict__ count, unsigned long long* __restrict__ n_correct,
+                                            double* __restrict__ sum_u) {
   __shared__ unsigned s_n[256], s_ok[256];
+  __shared__ float s_u[256];                // referenced only where SUM_U: binned_counts_kernel has no such array
   __shared__ float s_edge[257];
   s_n[threadIdx.x] = 0;
   s_ok[threadIdx.x] = 0;
+  if constexpr (SUM_U) s_u[threadIdx.x] = 0.0f;
   for (int i = threadIdx.x; i <= K; i += blockDim.x) s_edge[i] = edges[i];
   __syncthreads();
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
@@ -154,12 +100,25 @@ __global__ __launch_bounds__(256) void binned_counts_kernel(const float* __restr
     }
     atomicAdd(&s_n[lo], 1u);
     if (correct[i]) atomicAdd(&s_ok[lo], 1u);
+    if constexpr (SUM_U) atomicAdd(&s_u[lo], v);
   }
   __syncthreads();
   if ((int)threadIdx.x < K && s_n[threadIdx.x]) {
     atomicAdd(&count[threadIdx.x], (unsigned long long)s_n[threadIdx.x]);
     atomicAdd(&n_correct[threadIdx.x], (unsigned long long)s_ok[threadIdx.x]);
+    if constexpr (SUM_U) atomicAdd(&sum_u[threadIdx.x], (double)s_u[threadIdx.x]);
   }
+}
+// the two instantiations keep the kernel names they had as two kernels
+__global__ __launch_bounds__(256) void binned_counts_kernel(const float* __restrict__ u, const uint8_t* __restrict__ correct, size_t n,
+                                                            const float* __restrict__ edges, int K, unsigned long long* __restrict__ count,
+                                                            unsigned long long* __restrict__ n_correct) {
+  binned_body<false>(u, correct, n, edges, K, count, n_correct, nullptr);
+}
+__global__ __launch_bounds__(256) void binned_stats_kernel(const float* __restrict__ u, const uint8_t* __restrict__ correct, size_t n,
+                                                           const float* __restrict__ edges, int K, unsigned long long* __restrict__ count,
+                                                           unsigned long long* __restrict__ n_correct, double* __restrict__ sum_u) {
+  binned_body<true>(u, correct, n, edges, K, count, n_correct, sum_u);
 }
 
 // metrics/ece.py:55-84 (ECEAggregator._to_probs + update): per pixel the top-label confidence of p (by mode: 0 alpha a / (sum a + eps),
@@ -171,68 +130,16 @@ __global__ __launch_bounds__(256) void ece_samples_kernel(const float* __restric
                                                           uint8_t* __restrict__ flag_out) {
   const size_t npix = (size_t)B * HW;
   for (size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x; pix < npix; pix += (size_t)gridDim.x * blockDim.x) {
-    const int b = (int)(pix / HW);
-    const int hw = (int)(pix - (size_t)b * HW);
-    const float* src = preds + (size_t)b * C * (size_t)HW + hw;
-    float x[CMAX];
-    float m = -INFINITY;
-#pragma unroll
-    for (int c = 0; c < CMAX; ++c) {
-      x[c] = (c < C) ? src[(size_t)c * HW] : -INFINITY;
-      if (mode == 2 && c < C) x[c] = fmaxf(x[c], 0.0f);
-      m = fmaxf(m, x[c]);
-    }
-    float s = 0.0f;
+    float p[CMAX];
+    const float den = slu_mode_column(preds + slu_pixel(pix, C, HW).col, C, HW, mode, eps, p);
 #pragma unroll
     for (int c = 0; c < CMAX; ++c)
-      if (c < C) {
-        if (mode == 1) x[c] = expf(x[c] - m);
-        s += x[c];
-      }
-    const float den = mode == 0 ? s + eps : (mode == 1 ? s : fmaxf(s, eps));
-    float best = -INFINITY;
-    int arg = 0;
-#pragma unroll
-    for (int c = 0; c < CMAX; ++c)
-      if (c < C) {
-        const float p = x[c] / den;
-        if (p > best) { best = p; arg = c; }
-      }
+      if (c < C) p[c] /= den;
+    float best;
+    const int arg = slu_first_argmax(p, C, best);
     const int64_t lab = labels[pix];
     conf_out[pix] = fminf(fmaxf(best, 0.0f), 1.0f);
-    flag_out[pix] = (has_ignore && lab == ignore_index) ? (uint8_t)2 : (uint8_t)((int64_t)arg == lab ? 1 : 0);
-  }
-}
-
-// np.histogram(u, bins=edges) with weights None / correct / u (metrics/ece.py:136-140): binned_counts_kernel plus the per-bin sum of u.
-__global__ __launch_bounds__(256) void binned_stats_kernel(const float* __restrict__ u, const uint8_t* __restrict__ correct, size_t n,
-                                                           const float* __restrict__ edges, int K, unsigned long long* __restrict__ count,
-                                                           unsigned long long* __restrict__ n_correct, double* __restrict__ sum_u) {
-  __shared__ unsigned s_n[256], s_ok[256];
-  __shared__ float s_u[256];
-  __shared__ float s_edge[257];
-  s_n[threadIdx.x] = 0;
-  s_ok[threadIdx.x] = 0;
-  s_u[threadIdx.x] = 0.0f;
-  for (int i = threadIdx.x; i <= K; i += blockDim.x) s_edge[i] = edges[i];
-  __syncthreads();
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const float v = u[i];
-    if (!(v >= s_edge[0] && v <= s_edge[K])) continue;
-    int lo = 0, hi = K;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (v >= s_edge[mid]) lo = mid; else hi = mid;
-    }
-    atomicAdd(&s_n[lo], 1u);
-    if (correct[i]) atomicAdd(&s_ok[lo], 1u);
-    atomicAdd(&s_u[lo], v);
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < K && s_n[threadIdx.x]) {
-    atomicAdd(&count[threadIdx.x], (unsigned long long)s_n[threadIdx.x]);
-    atomicAdd(&n_correct[threadIdx.x], (unsigned long long)s_ok[threadIdx.x]);
-    atomicAdd(&sum_u[threadIdx.x], (double)s_u[threadIdx.x]);
+    flag_out[pix] = slu_label_ignored(lab, has_ignore, ignore_index) ? (uint8_t)2 : (uint8_t)((int64_t)arg == lab ? 1 : 0);
   }
 }
 
@@ -243,7 +150,7 @@ extern "C" int slu_confusion_update(const int64_t* preds, const int64_t* targets
   if (!preds || !targets || !confmat || n < 0 || C <= 0) return SLU_EINVAL;
   if (C > 32) return SLU_EUNSUPPORTED;
   if (n == 0) return SLU_OK;
-  hipLaunchKernelGGL(confusion_kernel, dim3(grid_for((size_t)n, 1024)), dim3(256), 0, slu_stream(stream), preds, targets, n, C,
+  hipLaunchKernelGGL(confusion_kernel, dim3(slu_grid_1d((size_t)n, 1024)), dim3(256), 0, slu_stream(stream), preds, targets, n, C,
                      reinterpret_cast<unsigned long long*>(confmat));
   SLU_CHECK_LAUNCH();
 }
@@ -252,35 +159,19 @@ extern "C" int slu_ece_update(const float* probs, const int64_t* labels, int B, 
                               int64_t* count, double* sum_correct, double* sum_conf, slu_stream_t stream) {
   if (!probs || !labels || !count || !sum_correct || !sum_conf || B <= 0 || C <= 0 || HW <= 0) return SLU_EINVAL;
   if (C > 32 || n_bins < 2 || n_bins > 64) return SLU_EUNSUPPORTED;
-  const unsigned g = grid_for((size_t)B * HW, 1024);
+  const unsigned g = slu_grid_1d((size_t)B * HW, 1024);
   unsigned long long* cnt = reinterpret_cast<unsigned long long*>(count);
-  if (C <= 20)
-    hipLaunchKernelGGL(ece_kernel<20>, dim3(g), dim3(256), 0, slu_stream(stream), probs, labels, B, C, HW, ignore_index, n_bins, cnt,
+  slu_class_cap(C, [&](auto cmax) {
+    hipLaunchKernelGGL(ece_kernel<decltype(cmax)::value>, dim3(g), dim3(256), 0, slu_stream(stream), probs, labels, B, C, HW, ignore_index, n_bins, cnt,
                        sum_correct, sum_conf);
-  else
-    hipLaunchKernelGGL(ece_kernel<32>, dim3(g), dim3(256), 0, slu_stream(stream), probs, labels, B, C, HW, ignore_index, n_bins, cnt,
-                       sum_correct, sum_conf);
-  SLU_CHECK_LAUNCH();
-}
-
-extern "C" int slu_softmax_nll_fwd(const float* logits, const int64_t* labels, int B, int C, int HW, float clampv, float* probs,
-                                   double* nll_sum, slu_stream_t stream) {
-  if (!logits || !labels || !nll_sum || B <= 0 || C <= 0 || HW <= 0) return SLU_EINVAL;
-  if (C > 32) return SLU_EUNSUPPORTED;
-  const unsigned g = grid_for((size_t)B * HW, 2048);
-  if (C <= 20)
-    hipLaunchKernelGGL(softmax_nll_kernel<20>, dim3(g), dim3(256), 0, slu_stream(stream), logits, labels, B, C, HW, clampv, probs,
-                       nll_sum);
-  else
-    hipLaunchKernelGGL(softmax_nll_kernel<32>, dim3(g), dim3(256), 0, slu_stream(stream), logits, labels, B, C, HW, clampv, probs,
-                       nll_sum);
+  });
   SLU_CHECK_LAUNCH();
 }
 
 extern "C" int slu_ua_samples(const int64_t* labels, const int64_t* preds, const float* uncertainty, long long n, const int64_t* ignore_ids,
                               int n_ignore, float* u_out, uint8_t* flags, slu_stream_t stream) {
   if (!labels || !preds || !uncertainty || !u_out || !flags || n <= 0 || n_ignore < 0 || (n_ignore > 0 && !ignore_ids)) return SLU_EINVAL;
-  hipLaunchKernelGGL(ua_samples_kernel, dim3(grid_for((size_t)n, 4096)), dim3(256), 0, slu_stream(stream), labels, preds, uncertainty, (size_t)n,
+  hipLaunchKernelGGL(ua_samples_kernel, dim3(slu_grid_1d((size_t)n, 4096)), dim3(256), 0, slu_stream(stream), labels, preds, uncertainty, (size_t)n,
                      ignore_ids, n_ignore, u_out, flags);
   SLU_CHECK_LAUNCH();
 }
@@ -289,23 +180,20 @@ extern "C" int slu_binned_counts(const float* u, const uint8_t* correct, long lo
                                  int64_t* n_correct, slu_stream_t stream) {
   if (!u || !correct || !edges || !count || !n_correct || n <= 0 || n_bins <= 0) return SLU_EINVAL;
   if (n_bins > 256) return SLU_EUNSUPPORTED;
-  hipLaunchKernelGGL(binned_counts_kernel, dim3(grid_for((size_t)n, 2048)), dim3(256), 0, slu_stream(stream), u, correct, (size_t)n, edges, n_bins,
+  hipLaunchKernelGGL(binned_counts_kernel, dim3(slu_grid_1d((size_t)n, 2048)), dim3(256), 0, slu_stream(stream), u, correct, (size_t)n, edges, n_bins,
                      reinterpret_cast<unsigned long long*>(count), reinterpret_cast<unsigned long long*>(n_correct));
   SLU_CHECK_LAUNCH();
 }
-
 
 extern "C" int slu_ece_samples(const float* preds, const int64_t* labels, int B, int C, int HW, int mode, int has_ignore, int64_t ignore_index,
                                float eps, float* conf, uint8_t* flags, slu_stream_t stream) {
   if (!preds || !labels || !conf || !flags || B <= 0 || C <= 0 || HW <= 0 || mode < 0 || mode > 2) return SLU_EINVAL;
   if (C > 32) return SLU_EUNSUPPORTED;
-  const unsigned g = grid_for((size_t)B * HW, 4096);
-  if (C <= 20)
-    hipLaunchKernelGGL(ece_samples_kernel<20>, dim3(g), dim3(256), 0, slu_stream(stream), preds, labels, B, C, HW, mode, has_ignore, ignore_index,
-                       eps, conf, flags);
-  else
-    hipLaunchKernelGGL(ece_samples_kernel<32>, dim3(g), dim3(256), 0, slu_stream(stream), preds, labels, B, C, HW, mode, has_ignore, ignore_index,
-                       eps, conf, flags);
+  const unsigned g = slu_grid_1d((size_t)B * HW, 4096);
+  slu_class_cap(C, [&](auto cmax) {
+    hipLaunchKernelGGL(ece_samples_kernel<decltype(cmax)::value>, dim3(g), dim3(256), 0, slu_stream(stream), preds, labels, B, C, HW, mode, has_ignore,
+                       ignore_index, eps, conf, flags);
+  });
   SLU_CHECK_LAUNCH();
 }
 
@@ -313,7 +201,7 @@ extern "C" int slu_binned_stats(const float* u, const uint8_t* correct, long lon
                                 int64_t* n_correct, double* sum_u, slu_stream_t stream) {
   if (!u || !correct || !edges || !count || !n_correct || !sum_u || n <= 0 || n_bins <= 0) return SLU_EINVAL;
   if (n_bins > 256) return SLU_EUNSUPPORTED;
-  hipLaunchKernelGGL(binned_stats_kernel, dim3(grid_for((size_t)n, 2048)), dim3(256), 0, slu_stream(stream), u, correct, (size_t)n, edges, n_bins,
+  hipLaunchKernelGGL(binned_stats_kernel, dim3(slu_grid_1d((size_t)n, 2048)), dim3(256), 0, slu_stream(stream), u, correct, (size_t)n, edges, n_bins,
                      reinterpret_cast<unsigned long long*>(count), reinterpret_cast<unsigned long long*>(n_correct), sum_u);
   SLU_CHECK_LAUNCH();
 }

@@ -1,8 +1,5 @@
-// HBM-bound per-pixel kernels: BatchNorm fold, 3x3/s2 average pool, MC-dropout reduction
-// (softmax over C, running mean over T, predictive entropy, mutual information, argmax) and the
-// single-pass softmax/entropy map.  One lane owns one pixel; lanes of a wave are azimuth-adjacent,
-// so every load/store instruction is a 256-byte contiguous row segment; the class axis (C <= 32,
-// 20 for SemanticKITTI) lives in registers, never in LDS.
+// BatchNorm fold (one thread per channel) and the 3x3 / stride-2 average pool (grid-stride over output elements, optionally
+// broadcasting one source image to several outputs): HBM-bound.
 #include "slu_common.h"
 
 namespace {
@@ -46,98 +43,6 @@ __global__ void avgpool3s2_kernel(const float* __restrict__ x, const float* __re
   }
 }
 
-// probs_t = exp(log_softmax(x_t)); accumulates over t in registers; never materialises [T,B,C,HW].
-template <int CMAX>
-__global__ __launch_bounds__(256) void mc_reduce_kernel(const float* __restrict__ logits, int T, int B, int C, int HW,
-                                                        float eps, float lnC, float* __restrict__ p_bar,
-                                                        float* __restrict__ h_norm, float* __restrict__ mi_norm,
-                                                        int64_t* __restrict__ preds) {
-  const size_t npix = (size_t)B * HW;
-  const size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (pix >= npix) return;
-  const int b = (int)(pix / HW);
-  const int hw = (int)(pix - (size_t)b * HW);
-  float psum[CMAX];
-#pragma unroll
-  for (int c = 0; c < CMAX; ++c) psum[c] = 0.0f;
-  float hsum = 0.0f;
-  for (int t = 0; t < T; ++t) {
-    const float* src = logits + ((size_t)t * B + b) * C * (size_t)HW + hw;
-    float x[CMAX];
-    float m = -INFINITY;
-#pragma unroll
-    for (int c = 0; c < CMAX; ++c) {
-      x[c] = (c < C) ? src[(size_t)c * HW] : -INFINITY;
-      m = fmaxf(m, x[c]);
-    }
-    float se = 0.0f;
-#pragma unroll
-    for (int c = 0; c < CMAX; ++c)
-      if (c < C) se += expf(x[c] - m);
-    const float lse = logf(se);
-    float ht = 0.0f;
-#pragma unroll
-    for (int c = 0; c < CMAX; ++c)
-      if (c < C) {
-        const float p = expf(x[c] - m - lse);
-        psum[c] += p;
-        const float pc = fmaxf(p, eps);
-        ht -= pc * logf(pc);
-      }
-    hsum += ht;
-  }
-  float hb = 0.0f, best = -INFINITY;
-  int arg = 0;
-#pragma unroll
-  for (int c = 0; c < CMAX; ++c)
-    if (c < C) {
-      const float p = psum[c] / (float)T;
-      p_bar[((size_t)b * C + c) * HW + hw] = p;
-      if (p > best) { best = p; arg = c; }
-      const float pc = fmaxf(p, eps);
-      hb -= pc * logf(pc);
-    }
-  h_norm[pix] = hb / lnC;
-  mi_norm[pix] = fmaxf((hb - hsum / (float)T) / lnC, 0.0f);
-  preds[pix] = arg;
-}
-
-template <int CMAX>
-__global__ __launch_bounds__(256) void softmax_entropy_kernel(const float* __restrict__ logits, int B, int C, int HW,
-                                                              float eps, float lnC, float* __restrict__ probs,
-                                                              float* __restrict__ h_norm, int64_t* __restrict__ preds) {
-  const size_t npix = (size_t)B * HW;
-  const size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (pix >= npix) return;
-  const int b = (int)(pix / HW);
-  const int hw = (int)(pix - (size_t)b * HW);
-  const float* src = logits + (size_t)b * C * (size_t)HW + hw;
-  float x[CMAX];
-  float m = -INFINITY;
-#pragma unroll
-  for (int c = 0; c < CMAX; ++c) {
-    x[c] = (c < C) ? src[(size_t)c * HW] : -INFINITY;
-    m = fmaxf(m, x[c]);
-  }
-  float se = 0.0f;
-#pragma unroll
-  for (int c = 0; c < CMAX; ++c)
-    if (c < C) se += expf(x[c] - m);
-  const float lse = logf(se);
-  float h = 0.0f, best = -INFINITY;
-  int arg = 0;
-#pragma unroll
-  for (int c = 0; c < CMAX; ++c)
-    if (c < C) {
-      const float p = expf(x[c] - m - lse);
-      if (probs) probs[((size_t)b * C + c) * HW + hw] = p;
-      if (p > best) { best = p; arg = c; }
-      h -= p * logf(fmaxf(p, eps));
-    }
-  if (h_norm) h_norm[pix] = h / lnC;
-  if (preds) preds[pix] = arg;
-}
-
 }  // namespace
 
 extern "C" int slu_bn_fold(const float* gamma, const float* beta, const float* mean, const float* var, float eps, int C,
@@ -166,37 +71,5 @@ extern "C" int slu_avgpool3s2_bcast_fwd(const float* x, const float* scale, floa
   const size_t nb = (total + 255) / 256;
   hipLaunchKernelGGL(avgpool3s2_kernel, dim3((unsigned)(nb > 16384 ? 16384 : nb)), dim3(256), 0, slu_stream(stream), x, scale, y,
                      N * C, H, W, OH, OW, C, in_batch);
-  SLU_CHECK_LAUNCH();
-}
-
-extern "C" int slu_mc_reduce(const float* logits, int T, int B, int C, int HW, float eps, float* p_bar, float* h_norm,
-                             float* mi_norm, int64_t* preds, slu_stream_t stream) {
-  if (!logits || !p_bar || !h_norm || !mi_norm || !preds || T <= 0 || B <= 0 || C <= 0 || HW <= 0) return SLU_EINVAL;
-  if (C > 32) return SLU_EUNSUPPORTED;
-  const size_t npix = (size_t)B * HW;
-  const unsigned nb = (unsigned)((npix + 255) / 256);
-  const float lnC = (float)log((double)C);
-  if (C <= 20)
-    hipLaunchKernelGGL(mc_reduce_kernel<20>, dim3(nb), dim3(256), 0, slu_stream(stream), logits, T, B, C, HW, eps, lnC, p_bar,
-                       h_norm, mi_norm, preds);
-  else
-    hipLaunchKernelGGL(mc_reduce_kernel<32>, dim3(nb), dim3(256), 0, slu_stream(stream), logits, T, B, C, HW, eps, lnC, p_bar,
-                       h_norm, mi_norm, preds);
-  SLU_CHECK_LAUNCH();
-}
-
-extern "C" int slu_softmax_entropy(const float* logits, int B, int C, int HW, float eps, float* probs, float* h_norm,
-                                   int64_t* preds, slu_stream_t stream) {
-  if (!logits || B <= 0 || C <= 0 || HW <= 0) return SLU_EINVAL;
-  if (C > 32) return SLU_EUNSUPPORTED;
-  const size_t npix = (size_t)B * HW;
-  const unsigned nb = (unsigned)((npix + 255) / 256);
-  const float lnC = (float)log((double)C);
-  if (C <= 20)
-    hipLaunchKernelGGL(softmax_entropy_kernel<20>, dim3(nb), dim3(256), 0, slu_stream(stream), logits, B, C, HW, eps, lnC, probs,
-                       h_norm, preds);
-  else
-    hipLaunchKernelGGL(softmax_entropy_kernel<32>, dim3(nb), dim3(256), 0, slu_stream(stream), logits, B, C, HW, eps, lnC, probs,
-                       h_norm, preds);
   SLU_CHECK_LAUNCH();
 }

@@ -4,8 +4,8 @@
 //   tversky_c = (TP_c + s) / (TP_c + alpha FP_c + beta FN_c + s),   loss = reduce_c (1 - tversky_c)
 // Forward: one pass, per-workgroup LDS partial sums of (S_c, TP_c, N_c), fp64 atomics.  Backward: one pass,
 //   d tversky_c / d p_c,i = ([y_i = c] D_c - A_c (alpha + [y_i = c] (1 - alpha - beta))) / D_c^2   (A = TP + s, D = denominator),
-// chained through softmax / exp for logits / log-probs.  One lane per pixel, class axis in registers: HBM-bound.
-#include "slu_common.h"
+// chained through softmax / exp for logits / log-probs.  One lane per pixel, class axis in registers (class_column.h): HBM-bound.
+#include "class_column.h"
 
 namespace {
 
@@ -13,17 +13,9 @@ enum { kActLogits = 0, kActProbs = 1, kActLogProbs = 2 };
 
 template <int CMAX>
 __device__ __forceinline__ void load_probs(const float* src, int C, size_t HW, int act, float (&p)[CMAX]) {
-  float m = -INFINITY;
-#pragma unroll
-  for (int c = 0; c < CMAX; ++c) {
-    p[c] = c < C ? src[(size_t)c * HW] : (act == kActLogits ? -INFINITY : 0.0f);
-    m = fmaxf(m, p[c]);
-  }
+  const float m = slu_load_column(src, C, HW, act == kActLogits ? -INFINITY : 0.0f, p);
   if (act == kActLogits) {
-    float se = 0.0f;
-#pragma unroll
-    for (int c = 0; c < CMAX; ++c)
-      if (c < C) { p[c] = expf(p[c] - m); se += p[c]; }
+    const float se = slu_exp_sum_inplace(p, C, m);
 #pragma unroll
     for (int c = 0; c < CMAX; ++c) p[c] = c < C ? p[c] / se : 0.0f;
   } else if (act == kActLogProbs) {
@@ -45,10 +37,9 @@ __global__ __launch_bounds__(256) void tversky_sums_kernel(const float* __restri
   for (int c = 0; c < CMAX; ++c) ls[c] = 0.0f;
   for (size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x; pix < npix; pix += (size_t)gridDim.x * blockDim.x) {
     const int64_t y = labels[pix];
-    if (!(y >= 0 && y < C) || (has_ignore && y == ignore)) continue;
-    const int b = (int)(pix / HW);
+    if (!slu_label_in_range(y, C) || slu_label_ignored(y, has_ignore, ignore)) continue;
     float p[CMAX];
-    load_probs<CMAX>(x + (size_t)b * C * HW + (pix - (size_t)b * HW), C, (size_t)HW, act, p);
+    load_probs<CMAX>(x + slu_pixel(pix, C, HW).col, C, (size_t)HW, act, p);
     float py = 0.0f;
 #pragma unroll
     for (int c = 0; c < CMAX; ++c) {
@@ -102,11 +93,10 @@ __global__ __launch_bounds__(256) void tversky_bwd_kernel(const float* __restric
   const size_t npix = (size_t)B * HW;
   const size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (pix >= npix) return;
-  const int b = (int)(pix / HW);
-  const size_t hw = pix - (size_t)b * HW;
-  float* dst = grad_x + (size_t)b * C * HW + hw;
+  const size_t col = slu_pixel(pix, C, HW).col;
+  float* dst = grad_x + col;
   const int64_t y = labels[pix];
-  const bool valid = (y >= 0 && y < C) && !(has_ignore && y == ignore);
+  const bool valid = slu_label_in_range(y, C) && !slu_label_ignored(y, has_ignore, ignore);
   if (!valid) {
 #pragma unroll
     for (int c = 0; c < CMAX; ++c)
@@ -114,7 +104,7 @@ __global__ __launch_bounds__(256) void tversky_bwd_kernel(const float* __restric
     return;
   }
   float p[CMAX], g[CMAX];
-  load_probs<CMAX>(x + (size_t)b * C * HW + hw, C, (size_t)HW, act, p);
+  load_probs<CMAX>(x + col, C, (size_t)HW, act, p);
   float dot = 0.0f;
 #pragma unroll
   for (int c = 0; c < CMAX; ++c) {
@@ -148,13 +138,10 @@ extern "C" int slu_tversky_fwd(const float* x, const int64_t* labels, int B, int
   if (C > 32) return SLU_EUNSUPPORTED;
   hipStream_t st = slu_stream(stream);
   if (hipMemsetAsync(sums, 0, (size_t)3 * C * sizeof(double), st) != hipSuccess) return SLU_ELAUNCH;
-  const size_t npix = (size_t)B * HW;
-  size_t nb = (npix + 255) / 256;
-  if (nb > 2048) nb = 2048;
-  if (C <= 20)
-    hipLaunchKernelGGL(tversky_sums_kernel<20>, dim3((unsigned)nb), dim3(256), 0, st, x, labels, B, C, HW, model_act, has_ignore, ignore_index, sums);
-  else
-    hipLaunchKernelGGL(tversky_sums_kernel<32>, dim3((unsigned)nb), dim3(256), 0, st, x, labels, B, C, HW, model_act, has_ignore, ignore_index, sums);
+  const unsigned nb = slu_grid_1d((size_t)B * HW, 2048);
+  slu_class_cap(C, [&](auto cmax) {
+    hipLaunchKernelGGL(tversky_sums_kernel<decltype(cmax)::value>, dim3(nb), dim3(256), 0, st, x, labels, B, C, HW, model_act, has_ignore, ignore_index, sums);
+  });
   hipLaunchKernelGGL(tversky_finalize_kernel, dim3(1), dim3(64), 0, st, sums, C, alpha, beta, smooth, reduction, loss, coef, any_valid);
   SLU_CHECK_LAUNCH();
 }
@@ -164,13 +151,10 @@ extern "C" int slu_tversky_bwd(const float* x, const int64_t* labels, int B, int
                                slu_stream_t stream) {
   if (!x || !labels || !coef || !grad_x || B <= 0 || C <= 0 || HW <= 0 || model_act < 0 || model_act > 2) return SLU_EINVAL;
   if (C > 32) return SLU_EUNSUPPORTED;
-  const size_t npix = (size_t)B * HW;
-  const unsigned nb = (unsigned)((npix + 255) / 256);
-  if (C <= 20)
-    hipLaunchKernelGGL(tversky_bwd_kernel<20>, dim3(nb), dim3(256), 0, slu_stream(stream), x, labels, B, C, HW, model_act, has_ignore, ignore_index,
-                       alpha, beta, coef, grad_out, grad_out_per_class, grad_x);
-  else
-    hipLaunchKernelGGL(tversky_bwd_kernel<32>, dim3(nb), dim3(256), 0, slu_stream(stream), x, labels, B, C, HW, model_act, has_ignore, ignore_index,
-                       alpha, beta, coef, grad_out, grad_out_per_class, grad_x);
+  const unsigned nb = slu_grid_per_pixel((size_t)B * HW);
+  slu_class_cap(C, [&](auto cmax) {
+    hipLaunchKernelGGL(tversky_bwd_kernel<decltype(cmax)::value>, dim3(nb), dim3(256), 0, slu_stream(stream), x, labels, B, C, HW, model_act, has_ignore,
+                       ignore_index, alpha, beta, coef, grad_out, grad_out_per_class, grad_x);
+  });
   SLU_CHECK_LAUNCH();
 }

@@ -19,11 +19,13 @@ import torch
 from oracle import dirichlet as odir
 from oracle import losses as olosses
 from oracle import metrics as ometrics
+from oracle import uncertainty as ounc
 from semanticlidarunc_amd import ops
 from semanticlidarunc_amd.loss import salsanext_loss
 from semanticlidarunc_amd.losses.regularizers import KL_offClasses_to_uniform
 from semanticlidarunc_amd.metrics.ece import ECEAggregator
 from semanticlidarunc_amd.models.evaluator import IoUEvaluator
+from semanticlidarunc_amd.models import probability_helper as ph
 from semanticlidarunc_amd.models.losses import CrossEntropyLoss, TverskyLoss
 from test_gpu_dirichlet_losses import _modules
 
@@ -346,3 +348,55 @@ def test_confusion_matrix(cuda, c, shape):
         ev.update(p.to(cuda), t.to(cuda))
         want += ometrics.confusion_matrix(p.numpy(), t.numpy(), c)
     assert np.array_equal(ev.confmat.cpu().numpy(), want)
+
+
+# ---- single-pass softmax / entropy map: softmax_entropy_kernel ---------------------------------------------------------------------------
+@pytest.mark.parametrize("shape", SHAPES, ids=_ids)
+@pytest.mark.parametrize("c", CLASSES)
+def test_softmax_entropy(cuda, c, shape):
+    """Bars of test_gpu_uncertainty's test_single_pass_golden: probs 1e-6, H 1e-5, argmax exact (the fp32 oracle's must equal the
+    fp64 one).  Unit-scale logits: at twice that the fp32 oracle's own probabilities are 3.0e-7 from fp64, over a quarter of the bar."""
+    gen = _gen(c, shape, 12)
+    logits = torch.randn(shape[0], c, shape[1], shape[2], generator=gen)
+    p64, h64, a64 = ounc.single_pass(logits.double())
+    p32, h32, a32 = ounc.single_pass(logits)
+    probs, h, preds = ops.softmax_entropy(logits.to(cuda))
+    assert torch.equal(a64, a32)
+    assert torch.equal(preds.cpu(), a64)
+    _cmp(f"softmax_entropy C={c} {shape} probs", probs, p64, p32, 1e-6)
+    _cmp(f"softmax_entropy C={c} {shape} H", h, h64, h32, 1e-5)
+
+
+# ---- Dirichlet head and alpha-based measures: dirichlet_kernel<., true> and <., false> -----------------------------------------------------
+def _rel(t, want64):
+    return torch.as_tensor(t).detach().double().cpu() / want64
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=_ids)
+@pytest.mark.parametrize("c", CLASSES)
+def test_dirichlet_head(cuda, c, shape):
+    """Bars of test_gpu_dirichlet: alpha 2e-6 and p_hat 3e-6 relative, H_norm 1e-5, AU and EU 3e-5, argmax exact (the fp32 oracle's
+    must equal the fp64 one).  The scale logit is centred at 3 so that no pixel is evidence-free (alpha = 1 + eps in every class ties
+    the argmax); three pixels carry 25, past the softplus threshold of 20, where the shape has room."""
+    gen = _gen(c, shape, 13)
+    outs = torch.randn(shape[0], c + 1, shape[1], shape[2], generator=gen) * 2.0
+    outs[:, c] = torch.randn(shape, generator=gen) * 3.0 + 3.0
+    if outs[:, c].numel() > 1:
+        pos = torch.randperm(outs[:, c].numel(), generator=gen)[:3]
+        scale = outs[:, c].reshape(-1)
+        scale[pos] = 25.0
+        outs[:, c] = scale.reshape(shape)
+    a64, p64, hn64, pr64 = odir.head(outs.double(), c)
+    a32, p32, hn32, pr32 = odir.head(outs, c)
+    assert torch.equal(pr64, pr32)
+    tag = f"dirichlet head C={c} {shape}"
+    alpha, p_hat, h_norm, preds = ph.dirichlet_head(outs.to(cuda), c)
+    assert torch.equal(preds.cpu(), pr64)
+    one = torch.ones_like(a64)
+    _cmp(tag + " alpha (relative)", _rel(alpha, a64), one, _rel(a32, a64), 2e-6)
+    _cmp(tag + " p_hat (relative)", _rel(p_hat, p64), one, _rel(p32, p64), 3e-6)
+    _cmp(tag + " H_norm", h_norm, hn64, hn32, 1e-5)
+    # dirichlet_uncertainty: the alpha-based measures of the device's alpha, as the reference calls them
+    _cmp(tag + " H_norm from alpha", ph.get_predictive_entropy_norm(alpha), hn64, hn32, 1e-5)
+    _cmp(tag + " AU", ph.get_aleatoric_uncertainty(alpha), odir.aleatoric(a64), odir.aleatoric(a32), 3e-5)
+    _cmp(tag + " EU", ph.get_epistemic_uncertainty(alpha), odir.epistemic(a64), odir.epistemic(a32), 3e-5)
