@@ -39,7 +39,11 @@ def decode(bin_bytes, label_bytes, id_map: dict):
 
 def resize_nearest(img, out_h, out_w):
     """cv2.resize(img, (out_w, out_h), interpolation=cv2.INTER_NEAREST) restated from OpenCV's definition (resizeNN: source index
-    min(floor(dst * src_size / dst_size), src_size - 1) per axis) -- cv2 is absent from this image: PARITY UNPINNED, like the normals."""
+    min(floor(dst * src_size / dst_size), src_size - 1) per axis) -- cv2 is absent from this image: PARITY UNPINNED, like the normals.
+    The ratio here (and in resize_nearest_kernel) is ``src / dst``; OpenCV's resizeNN computes it as ``1. / (dst / src)``.  The two forms
+    give the same index tables for every size the reference dataloaders resize (rows 16 / 32 / 40 / 64 / 128 -> 128, columns 256 / 512 /
+    1024 / 1800 / 2000 / 2048 / 2083 / 4000 -> 2048) and different ones for 4204 of the (src, dst) pairs below 300, e.g. 6 -> 34
+    (tests/test_projection_cases_cpu.py asserts both)."""
     h, w = img.shape[:2]
     ys = np.minimum(np.floor(np.arange(out_h) * (h / out_h)).astype(np.int64), h - 1)
     xs = np.minimum(np.floor(np.arange(out_w) * (w / out_w)).astype(np.int64), w - 1)

@@ -12,11 +12,15 @@ namespace {
 constexpr double kPi = 3.141592653589793238462643383279502884;
 
 // numpy.linspace(start, stop, n)[i]: arange(n) * step + start with step = (stop - start) / (n - 1); the last sample is `stop` exactly
+// No fused multiply-add: numpy rounds the product and the sum separately, and with one rounding the middle edge of linspace(-pi, pi, W)
+// changes sign for W = 23, 35, 43, ... (a point at phi = 0 then changes its column).  HIP's __dmul_rn / __dadd_rn are the plain
+// operators and contract like them, so contraction is switched off by pragma here, in angles() and in the yaw rotation.
 __device__ __forceinline__ double linspace_at(double start, double stop, int n, int i) {
+#pragma clang fp contract(off)
   if (n == 1) return start;
   if (i == n - 1) return stop;
   const double step = (stop - start) / (double)(n - 1);
-  return __dadd_rn(__dmul_rn((double)i, step), start);          // no fused multiply-add: numpy rounds twice
+  return (double)i * step + start;
 }
 
 // numpy.digitize(v, bins) - 1 for the DECREASING bins  b[k] = linspace(lo, hi, n)[n - 1 - k]  (right = False):
@@ -32,9 +36,10 @@ __device__ __forceinline__ int digitize_desc(double v, double lo, double hi, int
 }
 
 __device__ __forceinline__ void angles(const double* p, double& phi, double& theta, double& r) {
+#pragma clang fp contract(off)            // (x^2 + y^2) + z^2 as numpy sums it: points with swapped x, y have bit-equal ranges (the tie rule)
   const double x = p[0], y = p[1], z = p[2];
-  const double xy = __dadd_rn(__dmul_rn(x, x), __dmul_rn(y, y));
-  r = sqrt(__dadd_rn(xy, __dmul_rn(z, z)));
+  const double xy = x * x + y * y;
+  r = sqrt(xy + z * z);
   phi = atan2(y, x);
   theta = -atan2(sqrt(xy), z) + kPi / 2;
 }
@@ -197,13 +202,14 @@ namespace {
 __global__ __launch_bounds__(256) void kitti_decode_kernel(const float* __restrict__ xyzi, const unsigned* __restrict__ label, int N,
                                                            const int* __restrict__ lut, int lut_size, int rotate, double ca, double sa,
                                                            double* __restrict__ pc, int* __restrict__ bad) {
+#pragma clang fp contract(off)
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
   const float4 p = reinterpret_cast<const float4*>(xyzi)[i];
   double x = (double)p.x, y = (double)p.y, z = (double)p.z;
   if (rotate) {                           // [x y z] @ [[c, -s, 0], [s, c, 0], [0, 0, 1]]: plain products and sums, no fused multiply-add
-    const double xr = __dadd_rn(__dadd_rn(__dmul_rn(x, ca), __dmul_rn(y, sa)), __dmul_rn(z, 0.0));
-    const double yr = __dadd_rn(__dadd_rn(__dmul_rn(x, -sa), __dmul_rn(y, ca)), __dmul_rn(z, 0.0));
+    const double xr = (x * ca + y * sa) + z * 0.0;
+    const double yr = (x * -sa + y * ca) + z * 0.0;
     x = xr;
     y = yr;
   }
