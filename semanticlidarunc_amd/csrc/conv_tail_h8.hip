@@ -15,6 +15,8 @@
 // C = 32 MB WM channels, 8 waves = WM x WN, a wave owns MB channel blocks and RPW output rows: (C, TH) = (32, 16), (64, 8), (128, 4)
 // -- the a3 image takes C * TH * 128 B = 64 KB in each.  W3RES: the 1x1 weights over a3 stay resident in LDS (C <= 64); otherwise
 // they stream through the chunk pipeline as NKS more (weights-only) chunks, for which the LDS has no room at C = 128.
+// At C = 128 this form is LDS-bound (2x2 register tile) and slower than the two launches; launches of 256 tiles or more go to the member of
+// the version-2 family in conv_tail128_h8.h instead, and this kernel keeps the smaller ones.
 #include "h8_common.h"
 
 namespace {
@@ -606,6 +608,25 @@ int launch_tail2(TailArgs& a, const SluEmit& e) {
   return slu_launch_lds(tail2_h8_kernel<MB, RPW, D, RES>, dim3((unsigned)gx), dim3(512), lds, e.st, grant, a);
 }
 
+#include "conv_tail128_h8.h"      // tail128_h8_kernel, reported as tail2_h8_kernel<4, 2, 3, RES>: the C = 128 member, a body of its own (inside this namespace)
+
+// tiles of 8 rows x 64 columns
+inline long long tail128_tiles(int N, int H, int W) { return (long long)((W + 63) / 64) * ((H + 7) / 8) * N; }
+
+template <int RES>
+int launch_tail128(TailArgs& a, const SluEmit& e) {
+  static_assert(tail128_lds_bytes() + 6 * 128 * 4 <= 160 * 1024, "image and weight ring do not fit in LDS");
+  a.tiles_x = (a.W + 63) / 64;
+  a.tiles_y = (a.H + 7) / 8;
+  const long long nt = tail128_tiles(a.N, a.H, a.W);
+  if (nt <= 0 || nt > 0x7fffffffLL) return SLU_EUNSUPPORTED;
+  long long gx = 256;
+  if (gx > nt) gx = nt;
+  if (e.name) return slu_emit_name(e, "tail2_h8_kernel<%d, %d, %d, %d>", 4, 2, 3, RES);
+  static SluLdsGrant grant;
+  return slu_launch_lds(tail128_h8_kernel<RES == 1>, dim3((unsigned)gx), dim3(512), tail128_lds_bytes(), e.st, grant, a);
+}
+
 template <int MB, int WM, int WN, int RPW, bool W3RES>
 int launch_tail(TailArgs& a, const SluEmit& e) {
   constexpr int TH = WN * RPW, MBLK = MB * WM, C = 32 * MBLK, NKS = 2 * MBLK;
@@ -629,6 +650,13 @@ int launch_tail(TailArgs& a, const SluEmit& e) {
 extern "C" int slu_conv_tail_h8_shortcut_supported(int C, int sc_cin) { return C == 64 && sc_cin == 32 ? 1 : 0; }
 
 extern "C" int slu_conv_tail_h8_supported(int C, int H, int W) { return (C == 32 || C == 64 || C == 128) && H > 0 && W > 0 ? 1 : 0; }
+
+// C = 128: the counted-wait kernel where the launch fills at least one round of 256 workgroups with its 8 x 64 tiles (and an image lies
+// within its 32-bit record offsets); smaller launches keep the round-1 kernel, whose 4-row tiles spread them over more CUs
+static bool tail128_chosen(int C, int N, int H, int W) {
+  static const int min_tiles = slu_env_int("SLU_TAIL128_MIN_TILES", 256);      // A/B switch: the launch size from which the kernel is chosen
+  return C == 128 && N > 0 && H > 0 && W > 0 && tail128_tiles(N, H, W) >= (min_tiles > 256 ? min_tiles : 256) && tail128_fits(C / 8, H, W);
+}
 
 // the one traversal of the tail dispatch: slu_conv_tail_h8_fwd launches at its leaf, slu_conv_tail_h8_kernel_name has the leaf name itself
 static int conv_tail_dispatch(const slu_conv_tail_h8_desc* d, const SluEmit& e) {
@@ -666,6 +694,7 @@ static int conv_tail_dispatch(const slu_conv_tail_h8_desc* d, const SluEmit& e) 
   }
   if (!v1 && d->C == 32) return a.resid ? launch_tail2<1, 2, 3, 1>(a, e) : launch_tail2<1, 2, 3, 0>(a, e);
   if (!v1 && d->C == 64) return a.resid ? launch_tail2<2, 1, 4, 1>(a, e) : launch_tail2<2, 1, 4, 0>(a, e);
+  if (!v1 && tail128_chosen(d->C, d->N, d->H, d->W)) return a.resid ? launch_tail128<1>(a, e) : launch_tail128<0>(a, e);
   if (d->C == 32) return launch_tail<1, 1, 8, 2, true>(a, e);
   if (d->C == 64) return launch_tail<2, 1, 8, 1, true>(a, e);
   return launch_tail<2, 2, 4, 1, false>(a, e);

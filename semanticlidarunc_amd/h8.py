@@ -228,6 +228,25 @@ def conv_tail_supported(channels: int, h: int, w: int) -> bool:
     return bool(_lib.load().slu_conv_tail_h8_supported(int(channels), int(h), int(w)))
 
 
+_TAIL_NAMES: dict = {}
+
+
+def conv_tail_kernel_name(channels: int, n: int, h: int, w: int, resid: bool) -> str:
+    """The kernel instantiation conv_tail_h8 launches for this shape, by the library's own dispatch (slu_conv_tail_h8_kernel_name walked
+    with placeholder addresses; no launch)."""
+    key = (int(channels), int(n), int(h), int(w), bool(resid))
+    name = _TAIL_NAMES.get(key)
+    if name is None:
+        d = _lib.ConvTailH8Desc()
+        d.a1 = d.a2 = d.w2x2 = d.w1x1 = d.out = 0x1000
+        d.resid = 0x1000 if resid else None
+        d.C, d.N, d.H, d.W = key[:4]
+        buf = C.create_string_buffer(96)
+        check(_lib.load().slu_conv_tail_h8_kernel_name(C.byref(d), buf, 96), "slu_conv_tail_h8_kernel_name")
+        name = _TAIL_NAMES[key] = buf.value.decode()
+    return name
+
+
 def conv_tail_shortcut_supported(channels: int, cin: int) -> bool:
     return bool(_lib.load().slu_conv_tail_h8_shortcut_supported(int(channels), int(cin)))
 
@@ -235,12 +254,13 @@ def conv_tail_shortcut_supported(channels: int, cin: int) -> bool:
 def conv_tail_h8(a1: torch.Tensor, a2: torch.Tensor, w2x2: torch.Tensor, w1x1: torch.Tensor,
                  bias_a: Optional[torch.Tensor], slope_a: Optional[float], bn_a: Optional[tuple],
                  bias_b: Optional[torch.Tensor], slope_b: Optional[float], bn_b: Optional[tuple],
-                 resid: Optional[torch.Tensor] = None, shortcut: Optional[tuple] = None) -> torch.Tensor:
+                 resid: Optional[torch.Tensor] = None, shortcut: Optional[tuple] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The fused tail of a SalsaNext block (slu_conv_tail_h8_fwd):
         a3  = bn_a(leaky(conv2x2_dil2(a2) + bias_a));   out = [resid +] bn_b(leaky(conv1x1(cat(a1, a2, a3)) + bias_b))
     a1 / a2 / resid: h8 [N, C/8, H, W, 8]; w2x2 / w1x1: pack_conv_weight_h8 of [C, C, 2, 2] / [C, 3C, 1, 1]; bn_*: (scale, shift) or None.
     shortcut = (x, wpack, bias, slope, cin) instead of resid: resid = leaky(conv1x1(x) + bias) computed inside the kernel from the block's input
-    x (h8 [N, cin/8, H, W, 8], wpack = pack_conv_weight_h8 of [C, cin, 1, 1]); conv_tail_shortcut_supported(C, cin)."""
+    x (h8 [N, cin/8, H, W, 8], wpack = pack_conv_weight_h8 of [C, cin, 1, 1]); conv_tail_shortcut_supported(C, cin).
+    out: an h8 tensor of a1's shape to write into (default: a new one)."""
     lib = _lib.load()
     _req_h8(a1, "a1")
     _req_h8(a2, "a2")
@@ -279,7 +299,12 @@ def conv_tail_h8(a1: torch.Tensor, a2: torch.Tensor, w2x2: torch.Tensor, w1x1: t
             _req(sb, "shortcut.bias")
             if sb.numel() != c:
                 raise RuntimeError(f"shortcut.bias: expected {c} elements, got {sb.numel()}")
-    out = torch.empty_like(a1)
+    if out is None:
+        out = torch.empty_like(a1)
+    else:
+        _req_h8(out, "out")
+        if out.shape != a1.shape:
+            raise RuntimeError(f"out: expected {tuple(a1.shape)}, got {tuple(out.shape)}")
     d.a1, d.a2, d.N, d.H, d.W, d.C = a1.data_ptr(), a2.data_ptr(), n, h, w, c
     if shortcut is not None:
         d.sc_x, d.sc_w, d.sc_bias, d.sc_cin = sx.data_ptr(), sw.data_ptr(), _ptr(sb), int(scin)

@@ -41,7 +41,8 @@ _CONV_PRECISION = os.environ.get("SLU_CONV_PRECISION", "fp32")
 _TRAIN_CONV_PRECISION = os.environ.get("SLU_TRAIN_CONV_PRECISION", "fp32")
 # half-precision inference: run a block's 2x2-dilated conv and its concat 1x1 conv as one launch (0: two launches; A/B switch)
 _FUSE_TAIL = os.environ.get("SLU_FUSE_TAIL", "1") != "0"
-# the fused kernel also covers 128 channels, but there (MFMA-bound layers, 4-row tiles) it measured slower than the two launches
+# the round-1 fused kernel also covers 128 channels, but there (LDS-bound 2x2 register tile, full waits) it is slower than the two
+# launches; 128-channel tails are fused where the library dispatches them to tail2_h8_kernel<4, ...> (_tail_is_fused)
 _FUSE_TAIL_MAX_C = int(os.environ.get("SLU_FUSE_TAIL_MAX_C", "64"))
 # half-precision inference: a ResContextBlock (1x1 -> 3x3 -> 3x3 dilated + shortcut) as one launch (0: three launches; A/B switch)
 _FUSE_SHORTCUT = os.environ.get("SLU_FUSE_SHORTCUT", "1") != "0"      # A/B: ResBlock shortcut conv inside the fused tail
@@ -156,13 +157,17 @@ class _FusedBlock(nn.Module):
 
     def _tail_is_fused(self, conv_a: nn.Conv2d, conv_b: nn.Conv2d, a1) -> bool:
         c = conv_a.out_channels
-        return bool(_FUSE_TAIL and a1.dtype == torch.float16 and a1.dim() == 5 and conv_a.kernel_size == (2, 2) and conv_a.dilation == (2, 2)
-                    and conv_b.kernel_size == (1, 1) and conv_b.in_channels == 3 * c and conv_b.out_channels == c
-                    and c <= _FUSE_TAIL_MAX_C and h8.conv_tail_supported(c, a1.shape[2], a1.shape[3]))
+        if not (_FUSE_TAIL and a1.dtype == torch.float16 and a1.dim() == 5 and conv_a.kernel_size == (2, 2) and conv_a.dilation == (2, 2)
+                and conv_b.kernel_size == (1, 1) and conv_b.in_channels == 3 * c and conv_b.out_channels == c
+                and h8.conv_tail_supported(c, a1.shape[2], a1.shape[3])):
+            return False
+        # above _FUSE_TAIL_MAX_C (the round-1 kernel's limit): only where the library's dispatch picks a counted-wait kernel for this launch
+        return c <= _FUSE_TAIL_MAX_C or h8.conv_tail_kernel_name(c, a1.shape[0], a1.shape[2], a1.shape[3], False).startswith("tail2_h8_kernel<")
 
     def _run_tail(self, conv_a: nn.Conv2d, bn_a, conv_b: nn.Conv2d, bn_b, a1, a2, resid=None, shortcut=None, out_perm=False):
         """The last two layers of a block, `conv_b(cat(a1, a2, conv_a(a2)))`, each followed by LeakyReLU and eval BatchNorm.
-        Half-precision inference with 32 / 64 channels: one fused launch that keeps conv_a's output on chip (csrc/conv_tail_h8.hip);
+        Half-precision inference with 32 / 64 channels, and with 128 where the launch is large enough for the counted-wait kernel
+        (_tail_is_fused): one fused launch that keeps conv_a's output on chip (csrc/conv_tail_h8.hip, csrc/conv_tail128_h8.h);
         otherwise the two layers one after the other.  out_perm (half precision, no residual): the block's output channels are stored in
         shuffle order for a consumer that reads them through PixelShuffle in place."""
         if out_perm and a1.dtype != torch.float16:

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Guard for the counted-wait kernels (tail2_h8_kernel, ring3_h8_kernel: DESIGN 3.1g).  Their speed -- not their results -- depends on two
+"""Guard for the counted-wait kernels (tail2_h8_kernel and its C = 128 member tail128_h8_kernel, ring3_h8_kernel: DESIGN 3.1g).  Their speed -- not their results -- depends on two
 things the compiler is free to change: that it leaves the `s_waitcnt vmcnt(N)` of the source alone, and that it does not add its own
 `vmcnt(0)` inside the tile loop (it does for LDS reads without a TBAA tag and for tracked global loads once LDS-DMAs are interleaved).  This
 script disassembles the gfx950 code objects of libslu_hip.so and reports, per instantiation, the vmcnt values in the tile loop; it exits
@@ -82,7 +82,7 @@ with tempfile.TemporaryDirectory() as tmp:
             m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
             if m:
                 flush()
-                name = m.group(1) if ("tail2_h8_kernel" in m.group(1) or "ring3_h8_kernel" in m.group(1)) else None
+                name = m.group(1) if any(k in m.group(1) for k in ("tail2_h8_kernel", "tail128_h8_kernel", "ring3_h8_kernel")) else None
                 if name is None and EXTRA and EXTRA.search(m.group(1)):
                     name = m.group(1)
                 gemm = GEMM.search(name) if name and EXTRA else None
