@@ -63,8 +63,7 @@ __global__ __launch_bounds__(256) void dropout_draw_kernel(const slu_dropout_sit
 extern "C" int slu_dropout_draw(const slu_dropout_site* sites, int nsites, const slu_dropout_out* outs, int nout, int N, unsigned long long seed,
                                 unsigned long long offset, float* buf, long long total, slu_stream_t stream) {
   if (!sites || !outs || !buf || nsites <= 0 || nout <= 0 || N <= 0 || total <= 0) return SLU_EINVAL;
-  const long long nb = (total + 255) / 256;
-  hipLaunchKernelGGL(dropout_draw_kernel, dim3((unsigned)(nb > 4096 ? 4096 : nb)), dim3(256), 0, slu_stream(stream), sites, outs, nout, N, seed, offset,
+  hipLaunchKernelGGL(dropout_draw_kernel, dim3(slu_grid_1d((size_t)total, 4096)), dim3(256), 0, slu_stream(stream), sites, outs, nout, N, seed, offset,
                      buf, total);
   SLU_CHECK_LAUNCH();
 }

@@ -7,32 +7,27 @@
 //   se_gate_kernel        fc1 -> SiLU -> fc2 -> sigmoid on the pooled vector: one workgroup per sample (<= 1536 channels x <= 96 squeezed)
 //   dwconv3x3_wgrad_kernel  training: dL/dw[c][tap] = sum over (sample, pixel) of dy * shifted x -- one workgroup per channel, nine fp64 block sums
 //                           (the data gradient of the stride-1 depthwise conv is the forward kernel with the taps reversed)
-#include "slu_common.h"
+#include "pixel_common.h"
 
 namespace {
-
-__device__ __forceinline__ float silu(float v) { return v / (1.0f + expf(-v)); }
 
 template <int STRIDE>
 __global__ __launch_bounds__(256) void dwconv3x3_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
                                                         float* __restrict__ y, int NC, int C, int H, int W, int OH, int OW, int act) {
   const size_t total = (size_t)NC * OH * OW;
-  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-    const int ox = (int)(e % OW);
-    const size_t r = e / OW;
-    const int oy = (int)(r % OH);
-    const size_t nc = r / OH;
-    const int c = (int)(nc % C);
-    const float* p = x + nc * (size_t)H * W;
+  PIX_GRID_STRIDE(e, total) {
+    const PixXY o = pix_xy(e, OW, OH);
+    const int c = (int)(o.plane % C);
+    const float* p = x + o.plane * (size_t)H * W;
     const float* wc = w + (size_t)c * 9;
     float acc = bias ? bias[c] : 0.0f;
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      const int iy = oy * STRIDE + i - 1;
+    for (int i = 0; i < 3; ++i) {      // own copy of the window walk: in the pooling kernels' form (FOR_WINDOW3X3) both instantiations changed
+      const int iy = o.y * STRIDE + i - 1;
       if (iy < 0 || iy >= H) continue;
 #pragma unroll
       for (int j = 0; j < 3; ++j) {
-        const int ix = ox * STRIDE + j - 1;
+        const int ix = o.x * STRIDE + j - 1;
         if (ix >= 0 && ix < W) acc = fmaf(wc[i * 3 + j], p[(size_t)iy * W + ix], acc);
       }
     }
@@ -69,7 +64,7 @@ __global__ __launch_bounds__(256) void se_gate_kernel(const float* __restrict__ 
   for (int c = threadIdx.x; c < C; c += blockDim.x) {
     float acc = b2 ? b2[c] : 0.0f;
     for (int s = 0; s < S; ++s) acc = fmaf(w2[(size_t)c * S + s], s_hid[s], acc);
-    scale[(size_t)n * C + c] = 1.0f / (1.0f + expf(-acc));
+    scale[(size_t)n * C + c] = sigmoid(acc);
   }
 }
 
@@ -90,7 +85,7 @@ __global__ __launch_bounds__(256) void dwconv3x3_wgrad_kernel(const float* __res
       const int xx = (int)(e % W), yy = (int)(e / W);
       const float g = pg[e];
 #pragma unroll
-      for (int i = 0; i < 3; ++i) {
+      for (int i = 0; i < 3; ++i) {      // own copy, as dwconv3x3_kernel
         const int iy = yy + i - 1;
         if (iy < 0 || iy >= H) continue;
 #pragma unroll
@@ -104,7 +99,7 @@ __global__ __launch_bounds__(256) void dwconv3x3_wgrad_kernel(const float* __res
     for (int t = 0; t < 9; ++t) acc[t] += (double)part[t];      // fp32 within one plane and lane (<= HW / 256 terms), fp64 across planes and lanes
   }
   __shared__ double s_red[4][9];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;      // own copy of the workgroup sum: nine values per wave, slots wave-major
 #pragma unroll
   for (int t = 0; t < 9; ++t) {
     const double v = wave_sum(acc[t]);
@@ -112,11 +107,6 @@ __global__ __launch_bounds__(256) void dwconv3x3_wgrad_kernel(const float* __res
   }
   __syncthreads();
   if (threadIdx.x < 9) dw[(size_t)c * 9 + threadIdx.x] = (float)(s_red[0][threadIdx.x] + s_red[1][threadIdx.x] + s_red[2][threadIdx.x] + s_red[3][threadIdx.x]);
-}
-
-inline unsigned grid1d(size_t total) {
-  const size_t nb = (total + 255) / 256;
-  return (unsigned)(nb > 65535 ? 65535 : (nb ? nb : 1));
 }
 
 }  // namespace
@@ -127,9 +117,9 @@ extern "C" int slu_dwconv3x3_fwd(const float* x, const float* w, const float* bi
   const int OH = (H + stride - 1) / stride, OW = (W + stride - 1) / stride;      // floor((H + 2 - 3) / stride) + 1
   const size_t total = (size_t)N * C * OH * OW;
   if (stride == 1)
-    hipLaunchKernelGGL(dwconv3x3_kernel<1>, dim3(grid1d(total)), dim3(256), 0, slu_stream(stream), x, w, bias, y, N * C, C, H, W, OH, OW, act);
+    hipLaunchKernelGGL(dwconv3x3_kernel<1>, dim3(slu_grid_1d(total, 65535)), dim3(256), 0, slu_stream(stream), x, w, bias, y, N * C, C, H, W, OH, OW, act);
   else
-    hipLaunchKernelGGL(dwconv3x3_kernel<2>, dim3(grid1d(total)), dim3(256), 0, slu_stream(stream), x, w, bias, y, N * C, C, H, W, OH, OW, act);
+    hipLaunchKernelGGL(dwconv3x3_kernel<2>, dim3(slu_grid_1d(total, 65535)), dim3(256), 0, slu_stream(stream), x, w, bias, y, N * C, C, H, W, OH, OW, act);
   SLU_CHECK_LAUNCH();
 }
 

@@ -83,12 +83,6 @@ __global__ __launch_bounds__(256) void space_to_depth2_h8_kernel(const uint4* __
 // 2^-10 relative)
 __device__ __forceinline__ float att_tanh(float v) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(__expf(2.0f * v) + 1.0f); }
 
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 constexpr int ATT_MAX_W = 4096;
 
 // One workgroup (4 waves) per image row (n, h).  Pass 1: thread t owns pixels w = t, t + 256, ...: the row's t records block by block (lanes on

@@ -8,19 +8,10 @@
 //   groupnorm_apply_h8_kernel      out = (x - mean) * rstd * gamma[c] + beta[c] [-> ReLU], into a block slice
 //   spatial_softmax_stats_h8_kernel / spatial_gate_h8_kernel    w = softmax(score over H * W); out = x * w + x     SpatialAttention :80-85
 #include "h8_common.h"
+#include "pixel_common.h"      // bilinear_taps
 #include <math.h>
 
 namespace {
-
-// source index of ATen's area_pixel_compute_source_index (align_corners = False): max(0, (dst + 0.5) / s - 0.5), exact for s = 2, 4, 8
-__device__ __forceinline__ void bilinear_taps(int dst, float inv_s, int n_in, int& i0, int& i1, float& l0, float& l1) {
-  float src = ((float)dst + 0.5f) * inv_s - 0.5f;
-  src = src < 0.0f ? 0.0f : src;
-  i0 = (int)src;
-  i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
-  l1 = src - (float)i0;
-  l0 = 1.0f - l1;
-}
 
 // One thread per output record, as depth_to_space_h8_kernel: grid x = (block g, 256 output columns), y = output row, z = image; y and z
 // stride.  The four source records of a pixel are whole records too; s consecutive lanes share them.  The sum is written as

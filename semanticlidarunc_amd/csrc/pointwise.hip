@@ -1,6 +1,6 @@
 // BatchNorm fold (one thread per channel) and the 3x3 / stride-2 average pool (grid-stride over output elements, optionally
 // broadcasting one source image to several outputs): HBM-bound.
-#include "slu_common.h"
+#include "pixel_common.h"
 
 namespace {
 
@@ -19,26 +19,14 @@ __global__ void bn_fold_kernel(const float* __restrict__ gamma, const float* __r
 __global__ void avgpool3s2_kernel(const float* __restrict__ x, const float* __restrict__ scale, float* __restrict__ y,
                                   int NC, int H, int W, int OH, int OW, int C, int in_batch) {
   const size_t total = (size_t)NC * OH * OW;
-  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-    const int ox = (int)(e % OW);
-    const size_t r = e / OW;
-    const int oy = (int)(r % OH);
-    const size_t nc = r / OH;
+  PIX_GRID_STRIDE(e, total) {
+    const PixXY o = pix_xy(e, OW, OH);
+    const size_t nc = o.plane;
     const float s = scale ? scale[nc] : 1.0f;
     const size_t nc_in = in_batch ? ((nc / C) % in_batch) * C + nc % C : nc;   // broadcast source image
     const float* p = x + nc_in * (size_t)H * W;
     float acc = 0.0f;
-#pragma unroll
-    for (int i = -1; i <= 1; ++i) {
-      const int iy = 2 * oy + i;
-      if (iy < 0 || iy >= H) continue;
-#pragma unroll
-      for (int j = -1; j <= 1; ++j) {
-        const int ix = 2 * ox + j;
-        if (ix < 0 || ix >= W) continue;
-        acc += p[(size_t)iy * W + ix] * s;
-      }
-    }
+    FOR_WINDOW3X3(tap, iy, ix, 2, o.y, o.x, H, W) acc += p[(size_t)iy * W + ix] * s;
     y[e] = acc / 9.0f;
   }
 }
@@ -57,8 +45,7 @@ extern "C" int slu_avgpool3s2_fwd(const float* x, const float* scale, float* y, 
   if (!x || !y || N <= 0 || C <= 0 || H <= 0 || W <= 0) return SLU_EINVAL;
   const int OH = (H + 1) / 2, OW = (W + 1) / 2;
   const size_t total = (size_t)N * C * OH * OW;
-  const size_t nb = (total + 255) / 256;
-  hipLaunchKernelGGL(avgpool3s2_kernel, dim3((unsigned)(nb > 16384 ? 16384 : nb)), dim3(256), 0, slu_stream(stream), x, scale, y,
+  hipLaunchKernelGGL(avgpool3s2_kernel, dim3(slu_grid_1d(total, 16384)), dim3(256), 0, slu_stream(stream), x, scale, y,
                      N * C, H, W, OH, OW, C, 0);
   SLU_CHECK_LAUNCH();
 }
@@ -68,8 +55,7 @@ extern "C" int slu_avgpool3s2_bcast_fwd(const float* x, const float* scale, floa
   if (!x || !y || N <= 0 || in_batch <= 0 || C <= 0 || H <= 0 || W <= 0) return SLU_EINVAL;
   const int OH = (H + 1) / 2, OW = (W + 1) / 2;
   const size_t total = (size_t)N * C * OH * OW;
-  const size_t nb = (total + 255) / 256;
-  hipLaunchKernelGGL(avgpool3s2_kernel, dim3((unsigned)(nb > 16384 ? 16384 : nb)), dim3(256), 0, slu_stream(stream), x, scale, y,
+  hipLaunchKernelGGL(avgpool3s2_kernel, dim3(slu_grid_1d(total, 16384)), dim3(256), 0, slu_stream(stream), x, scale, y,
                      N * C, H, W, OH, OW, C, in_batch);
   SLU_CHECK_LAUNCH();
 }

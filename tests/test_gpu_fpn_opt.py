@@ -53,6 +53,29 @@ def test_new_kernels_against_torch(cuda):
     assert float((ops.spatial_softmax_gate(v.to(cuda), sc.to(cuda)).cpu() - (v * w + v)).abs().max()) <= 1e-6
 
 
+@pytest.mark.parametrize("shape", [(1, 2, 1, 3), (1, 2, 3, 1), (2, 1, 2, 2)])
+def test_bilinear_taps_where_the_clamp_decides(cuda, shape):
+    """The shared bilinear taps (pixel_common.h) at sizes of 1 and 2 along an axis, where `i0 < n_in - 1` picks the second tap of every output
+    pixel: the forward against F.interpolate in fp64 (bound of test_new_kernels_against_torch), the backward of a random cotangent against the
+    fp64 autograd gradient (bound of the bilinear node in test_gpu_fpn_train.py: 1e-5 * max(1, max |gradient|))."""
+    g = torch.Generator().manual_seed(11)
+    x = torch.randn(*shape, generator=g)
+    for s in (2, 4, 8):
+        x64 = x.double().requires_grad_(True)
+        want = F.interpolate(x64, scale_factor=s, mode="bilinear", align_corners=False)
+        got = ops.bilinear_upsample(x.to(cuda), s).cpu()
+        assert got.shape == want.shape
+        err = float((got.double() - want.detach()).abs().max())
+        cot = torch.randn(want.shape, generator=g)
+        dwant, = torch.autograd.grad(want, x64, cot.double())
+        dgot = ops.bilinear_upsample_bwd(cot.to(cuda), s).cpu()
+        assert dgot.shape == x.shape
+        derr, bound = float((dgot.double() - dwant).abs().max()), 1e-5 * max(1.0, float(dwant.abs().max()))
+        print(f"bilinear {shape} x{s}: forward max|err| {err:.3e} (<= 1e-6), backward {derr:.3e} (<= {bound:.3e})")
+        assert err <= 1e-6
+        assert derr <= bound
+
+
 @pytest.mark.parametrize("tag", list(CASES))
 @pytest.mark.parametrize("prec", ["fp32", "f16x3"])
 def test_against_the_reference_golden(cuda, tag, prec):
