@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SLU_ABI_VERSION 38
+#define SLU_ABI_VERSION 39
 
 #define SLU_OK            0
 #define SLU_EINVAL       -1   /* null pointer / non-positive size / inconsistent descriptor   */
@@ -631,6 +631,45 @@ int slu_kitti_decode(const float* xyzi, const uint32_t* label, int N, const int3
 int slu_resize_nearest_hwc(const float* img, int H, int W, int C, float* out, int OH, int OW, int flip, slu_stream_t stream);
 int slu_range_image_split(const float* img, const float* normals, int H, int W, int C, float* range, float* refl, float* xyz, float* normals_chw,
                           int64_t* labels, slu_stream_t stream);
+
+/* ---- the other four dataloaders around the same projection (dataset/dataloader_semantic_{STF,THAB,CUDAL,WADS}.py) ------------------
+ * slu_point_decode: slu_kitti_decode with every step optional.  records float32 [N][stride], stride 4 or 5 (STF reads 5-float records and
+ *   uses the first 4, dataloader_semantic_STF.py:37); intensity_div > 0: intensity / intensity_div as a float32 division (:38), 0: none;
+ *   mask_labels: label & 0xFFFF (KITTI / CUDAL / WADS) or the raw uint32 word (STF :43); lut NULL: the class is the label itself;
+ *   remap_from >= 0: a class equal to it becomes remap_to, after the lut (STF remap_adverse_label, :55-56); clip != 0: valid[i] uint8 [N] = the
+ *   float32 norm of np.linalg.norm(xyzi[:, 0:3], axis=-1) is >= clip_min (STF :49-54: taken BEFORE the rotation) -- the cloud keeps all N
+ *   rows in file order, slu_spherical_projection_valid skips the rows whose flag is 0; rotate / cos_a / sin_a / pc / bad_count as in
+ *   slu_kitti_decode.
+ * slu_spherical_projection_valid: slu_spherical_projection_ex (nearest point, linspace rows) over the points with valid[i] != 0 only: the
+ *   others take no part in the data theta range and win no pixel; empty_count int32[1] or NULL: += 1 when the data theta range is asked
+ *   for and no point is valid (numpy's theta.min() raises there, dataset/utils.py:323). */
+int slu_point_decode(const float* records, int stride, const uint32_t* label, int N, float intensity_div, int mask_labels, const int32_t* lut,
+                     int lut_size, int remap_from, int remap_to, int clip, float clip_min, int rotate, double cos_a, double sin_a, double* pc,
+                     uint8_t* valid, int32_t* bad_count, slu_stream_t stream);
+int slu_spherical_projection_valid(const double* pc, const uint8_t* valid, int N, int C, int H, int W, int use_data_theta_range, double theta_min,
+                                   double theta_max, int flip, void* workspace, size_t workspace_bytes, float* img, int32_t* empty_count,
+                                   slu_stream_t stream);
+/* slu_organised_scan: SemanticTHAB.__getitem__ up to the image (dataloader_semantic_THAB.py:35-59): records float32 [H*W][4] (16-byte
+ *   aligned) and label uint32 [H*W] of an organised scan -> img float32 [H][W][5] = (x, y, z, intensity, lut[label & 0xFFFF]).  In the
+ *   loader's order and precision: float64 image, flip (columns reversed, y negated, :52-55), np.roll by `shift` columns (any integer;
+ *   rotate_equirectangular_image, dataset/utils.py:21-28), xyz @ Rz in float64 (:59), one rounding to float32.  range float32 [H][W] or
+ *   NULL: the float64 norm of the float64 xyz rounded to float32, which is what the loader returns (:67,77). */
+int slu_organised_scan(const float* records, const uint32_t* label, int H, int W, const int32_t* lut, int lut_size, int flip, long long shift,
+                       int rotate, double cos_a, double sin_a, float* img, float* range, int32_t* bad_count, slu_stream_t stream);
+/* slu_nonempty_rows: img[~np.all(np.linalg.norm(img, axis=-1) == 0, axis=1)] as a table (dataloader_semantic_WADS.py:125).  rows int32
+ *   [2 H + 1]: rows[0] = H' = number of rows with a non-zero pixel, rows[1 .. H'] = their indices in ascending order (rows[H + 1 ..] scratch).
+ * slu_resize_nearest_rows_hwc: slu_resize_nearest_hwc of the H' kept rows (:126-127): source row rows[1 + min(floor(dst * H' / OH), H' - 1)],
+ *   H' read on the device; flip as there.  H' = 0 (cv2.resize raises): *no_row_count += 1 and the output is zeros. */
+int slu_nonempty_rows(const float* img, int H, int W, int C, int32_t* rows, slu_stream_t stream);
+int slu_resize_nearest_rows_hwc(const float* img, int H, int W, int C, const int32_t* rows, float* out, int OH, int OW, int flip,
+                                int32_t* no_row_count, slu_stream_t stream);
+/* slu_channel_max: key uint32[1] = the maximum of img[..., channel] over an [H][W][C] float32 image in an order-preserving integer form.
+ * slu_range_image_split_ex: slu_range_image_split with range_in float32 [H][W] or NULL (given: copied instead of |xyz|, the THAB range) and
+ *   refl_max_key (slu_channel_max of channel 3) or NULL (given: reflectivity / max(maximum, 1.0f) as a float32 division,
+ *   dataloader_semantic_CUDAL.py:107). */
+int slu_channel_max(const float* img, int H, int W, int C, int channel, uint32_t* key, slu_stream_t stream);
+int slu_range_image_split_ex(const float* img, const float* normals, int H, int W, int C, const float* range_in, const uint32_t* refl_max_key,
+                             float* range, float* refl, float* xyz, float* normals_chw, int64_t* labels, slu_stream_t stream);
 
 /* ---- surface normals of the projected image (dataset/utils.py:30-58 build_normal_xyz; inference_ouster.py:70) ------
  * xyz: fp32 [H][W][channels >= 3] (x, y, z first); normals: fp32 [H][W][3] = -(d xyz/d col x d xyz/d row) / (|.| + 1e-10) with the 3x3

@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-ABI_VERSION = 38
+ABI_VERSION = 39
 MAX_SRC = 3
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libslu_hip.so")
@@ -241,6 +241,17 @@ SIGNATURES = {
                                               C.c_int, C.c_void_p, C.c_size_t, c_f32p, c_f64p, c_stream]),
     "slu_kitti_decode": (C.c_int, [c_f32p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, c_f64p, C.c_void_p, c_stream]),
     "slu_range_image_split": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_i64p, c_stream]),
+    "slu_point_decode": (C.c_int, [c_f32p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                   C.c_int, C.c_double, C.c_double, c_f64p, C.c_void_p, C.c_void_p, c_stream]),
+    "slu_spherical_projection_valid": (C.c_int, [c_f64p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
+                                                 C.c_void_p, C.c_size_t, c_f32p, C.c_void_p, c_stream]),
+    "slu_organised_scan": (C.c_int, [c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_double, C.c_double,
+                                     c_f32p, c_f32p, C.c_void_p, c_stream]),
+    "slu_nonempty_rows": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_void_p, c_stream]),
+    "slu_resize_nearest_rows_hwc": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_void_p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_void_p, c_stream]),
+    "slu_channel_max": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, c_stream]),
+    "slu_range_image_split_ex": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, c_f32p, C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, c_i64p,
+                                           c_stream]),
     "slu_pointwise_fwd": (C.c_int, [c_f32p, c_f32p, C.c_size_t, C.c_int, C.c_float, c_stream]),
     "slu_pointwise_bwd": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_size_t, C.c_int, C.c_float, c_stream]),
     "slu_maxpool3s2_bwd": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_stream]),

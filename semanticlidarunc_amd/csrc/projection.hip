@@ -49,9 +49,15 @@ __device__ __forceinline__ unsigned long long orderable(double v) {         // m
   return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
 }
 
-__global__ __launch_bounds__(256) void theta_minmax_kernel(const double* __restrict__ pc, int N, int C, unsigned long long* __restrict__ mm) {
+// kValid (here and in the two point passes below): the clouds of slu_point_decode's range clip carry a per-point keep flag; a point whose
+// flag is 0 takes no part in the data theta range and wins no pixel, and the kept points keep their indices, so the tie rule of the second
+// pass is that of the compacted cloud.  The flag is a template parameter: the instances without it are the kernels they were.
+template <bool kValid>
+__global__ __launch_bounds__(256) void theta_minmax_kernel(const double* __restrict__ pc, const unsigned char* __restrict__ valid, int N, int C,
+                                                           unsigned long long* __restrict__ mm) {
   unsigned long long lo = ~0ull, hi = 0ull;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < N; i += gridDim.x * blockDim.x) {
+    if constexpr (kValid) { if (!valid[i]) continue; }
     double phi, theta, r;
     angles(pc + (size_t)i * C, phi, theta, r);
     const unsigned long long k = orderable(theta);
@@ -86,11 +92,16 @@ __device__ __forceinline__ int digitize_bins(double v, const double* __restrict_
 }
 
 // pass 1: pixel of every point, nearest (or, keep_farthest, farthest) range per pixel
-__global__ __launch_bounds__(256) void project_kernel(const double* __restrict__ pc, int N, int C, int H, int W, int use_data_range, double tmin, double tmax,
-                                                      const unsigned long long* __restrict__ mm, const double* __restrict__ bins_h, int bins_increasing,
-                                                      int keep_farthest, int* __restrict__ pixel, unsigned long long* __restrict__ best_r) {
+template <bool kValid>
+__global__ __launch_bounds__(256) void project_kernel(const double* __restrict__ pc, const unsigned char* __restrict__ valid, int N, int C, int H, int W,
+                                                      int use_data_range, double tmin, double tmax, const unsigned long long* __restrict__ mm,
+                                                      const double* __restrict__ bins_h, int bins_increasing, int keep_farthest, int* __restrict__ pixel,
+                                                      unsigned long long* __restrict__ best_r) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
+  if constexpr (kValid) {
+    if (!valid[i]) { pixel[i] = -1; return; }
+  }
   if (use_data_range) { tmin = from_orderable(mm[0]); tmax = from_orderable(mm[1]); }
   double phi, theta, r;
   angles(pc + (size_t)i * C, phi, theta, r);
@@ -104,10 +115,12 @@ __global__ __launch_bounds__(256) void project_kernel(const double* __restrict__
 
 // pass 2: among the points at the winning range of their pixel, the smallest index (nearest mode: the reference's descending argsort
 // keeps an unspecified one of them) / the largest index (farthest mode)
+template <bool kValid>
 __global__ __launch_bounds__(256) void winner_kernel(const double* __restrict__ pc, int N, int C, const int* __restrict__ pixel,
                                                      const unsigned long long* __restrict__ best_r, int keep_farthest, int* __restrict__ winner) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
+  if constexpr (kValid) { if (pixel[i] < 0) return; }
   double phi, theta, r;
   angles(pc + (size_t)i * C, phi, theta, r);
   if ((unsigned long long)__double_as_longlong(r) == best_r[pixel[i]]) {
@@ -136,6 +149,11 @@ __global__ void theta_range_kernel(const unsigned long long* __restrict__ mm, in
   out[1] = use_data_range ? from_orderable(mm[1]) : tmax;
 }
 
+// the data theta range of a cloud without a kept point: numpy's theta.min() raises there (dataset/utils.py:323); counted for the host
+__global__ void empty_cloud_kernel(const unsigned long long* __restrict__ mm, int* __restrict__ empty_count) {
+  if (mm[0] == ~0ull && mm[1] == 0ull) atomicAdd(empty_count, 1);
+}
+
 size_t carve_proj(char* base, int N, int HW, unsigned long long** mm, int** pixel, unsigned long long** best, int** winner) {
   size_t off = 0;
   auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += (bytes + 255) & ~(size_t)255; return p; };
@@ -154,9 +172,12 @@ extern "C" size_t slu_spherical_projection_workspace_bytes(int N, int H, int W) 
   return carve_proj(nullptr, N, H * W, nullptr, nullptr, nullptr, nullptr);
 }
 
-extern "C" int slu_spherical_projection_ex(const double* pc, int N, int C, int H, int W, int use_data_theta_range, double theta_min, double theta_max,
-                                           const double* bins_h, int bins_increasing, int keep_farthest, int flip, void* workspace,
-                                           size_t workspace_bytes, float* img, double* theta_range_out, slu_stream_t stream) {
+namespace {
+
+template <bool kValid>
+int project_cloud(const double* pc, const unsigned char* valid, int N, int C, int H, int W, int use_data_theta_range, double theta_min, double theta_max,
+                  const double* bins_h, int bins_increasing, int keep_farthest, int flip, void* workspace, size_t workspace_bytes, float* img,
+                  double* theta_range_out, int* empty_count, slu_stream_t stream) {
   if (!pc || !workspace || !img || N <= 0 || C < 3 || H <= 0 || W <= 0 || (long long)H * W > 0x7ffffffe) return SLU_EINVAL;
   unsigned long long *mm, *best;
   int *pixel, *winner;
@@ -174,14 +195,32 @@ extern "C" int slu_spherical_projection_ex(const double* pc, int N, int C, int H
   if (hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(winner), none, (size_t)HW, st) != hipSuccess) return SLU_ELAUNCH;
   const int data_range = use_data_theta_range && !bins_h;
   if (use_data_theta_range)
-    hipLaunchKernelGGL(theta_minmax_kernel, dim3(nbp > 256 ? 256 : nbp), dim3(256), 0, st, pc, N, C, mm);
-  hipLaunchKernelGGL(project_kernel, dim3(nbp), dim3(256), 0, st, pc, N, C, H, W, data_range, theta_min, theta_max, mm, bins_h, bins_increasing,
-                     keep_farthest, pixel, best);
-  hipLaunchKernelGGL(winner_kernel, dim3(nbp), dim3(256), 0, st, pc, N, C, pixel, best, keep_farthest, winner);
+    hipLaunchKernelGGL(theta_minmax_kernel<kValid>, dim3(nbp > 256 ? 256 : nbp), dim3(256), 0, st, pc, valid, N, C, mm);
+  if (kValid && use_data_theta_range && empty_count) hipLaunchKernelGGL(empty_cloud_kernel, dim3(1), dim3(1), 0, st, mm, empty_count);
+  hipLaunchKernelGGL(project_kernel<kValid>, dim3(nbp), dim3(256), 0, st, pc, valid, N, C, H, W, data_range, theta_min, theta_max, mm, bins_h,
+                     bins_increasing, keep_farthest, pixel, best);
+  hipLaunchKernelGGL(winner_kernel<kValid>, dim3(nbp), dim3(256), 0, st, pc, N, C, pixel, best, keep_farthest, winner);
   hipLaunchKernelGGL(gather_kernel, dim3(nbx), dim3(256), 0, st, pc, C, H, W, winner, none, flip, img);
   if (theta_range_out)
     hipLaunchKernelGGL(theta_range_kernel, dim3(1), dim3(1), 0, st, mm, use_data_theta_range, theta_min, theta_max, theta_range_out);
   SLU_CHECK_LAUNCH();
+}
+
+}  // namespace
+
+extern "C" int slu_spherical_projection_ex(const double* pc, int N, int C, int H, int W, int use_data_theta_range, double theta_min, double theta_max,
+                                           const double* bins_h, int bins_increasing, int keep_farthest, int flip, void* workspace,
+                                           size_t workspace_bytes, float* img, double* theta_range_out, slu_stream_t stream) {
+  return project_cloud<false>(pc, nullptr, N, C, H, W, use_data_theta_range, theta_min, theta_max, bins_h, bins_increasing, keep_farthest, flip, workspace,
+                              workspace_bytes, img, theta_range_out, nullptr, stream);
+}
+
+extern "C" int slu_spherical_projection_valid(const double* pc, const uint8_t* valid, int N, int C, int H, int W, int use_data_theta_range, double theta_min,
+                                              double theta_max, int flip, void* workspace, size_t workspace_bytes, float* img, int32_t* empty_count,
+                                              slu_stream_t stream) {
+  if (!valid) return SLU_EINVAL;
+  return project_cloud<true>(pc, valid, N, C, H, W, use_data_theta_range, theta_min, theta_max, nullptr, 0, 0, flip, workspace, workspace_bytes, img,
+                             nullptr, empty_count, stream);
 }
 
 extern "C" int slu_spherical_projection(const double* pc, int N, int C, int H, int W, int use_data_theta_range, double theta_min, double theta_max,

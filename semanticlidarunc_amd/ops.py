@@ -1559,6 +1559,157 @@ def range_image_split(img: torch.Tensor, normals: Optional[torch.Tensor], range_
                                             _ptr(normals_out) if normals is not None else None, labels_out.data_ptr(), _stream()), "slu_range_image_split")
 
 
+def _yaw(rotate_deg):
+    """(flag, cos, sin) of dataset.utils.rotate_z: numpy's cos / sin of np.radians(angle), as the reference builds its matrix."""
+    if rotate_deg is None:
+        return 0, 1.0, 0.0
+    import numpy as np
+    ang = float(np.radians(float(rotate_deg)))
+    return 1, float(np.cos(ang)), float(np.sin(ang))
+
+
+def point_decode(records: torch.Tensor, label: torch.Tensor, bad_count: torch.Tensor, lut: Optional[torch.Tensor] = None, intensity_div: float = 0.0,
+                 mask_labels: bool = True, remap=None, clip_min: Optional[float] = None, rotate_deg: Optional[float] = None):
+    """File contents fp32 [N, 4 or 5] + label int32 [N] (the uint32 words) -> (cloud float64 [N, 5] = (x, y, z, i, class), valid uint8 [N] or
+    None).  intensity_div: float32 division of the intensity (0: none); mask_labels: label & 0xFFFF; lut: int32 id_map table (None: raw
+    labels); remap: (from, to) applied to the class; clip_min: valid[i] = float32 |xyz| >= clip_min, taken before the yaw `rotate_deg`."""
+    _req(records, "records")
+    _req(label, "label", torch.int32)
+    _req(bad_count, "bad_count", torch.int32)
+    if lut is not None:
+        _req(lut, "lut", torch.int32)
+    if records.dim() != 2 or records.shape[1] not in (4, 5) or label.dim() != 1 or label.numel() != records.shape[0] or records.shape[0] == 0:
+        raise RuntimeError(f"point_decode: records [N, 4 or 5] / label [N] expected, got {tuple(records.shape)} / {tuple(label.shape)}")
+    if bad_count.numel() < 1 or not float(intensity_div) >= 0.0:
+        raise RuntimeError("point_decode: bad_count needs one element and intensity_div must be >= 0")
+    if remap is not None and (len(remap) != 2 or int(remap[0]) < 0):
+        raise RuntimeError(f"point_decode: remap is (from >= 0, to), got {remap!r}")
+    n, stride = records.shape
+    pc = torch.empty((n, 5), dtype=torch.float64, device=records.device)
+    valid = None if clip_min is None else torch.empty(n, dtype=torch.uint8, device=records.device)
+    rot, ca, sa = _yaw(rotate_deg)
+    rf, rt = (-1, 0) if remap is None else (int(remap[0]), int(remap[1]))
+    check(_lib.load().slu_point_decode(records.data_ptr(), stride, label.data_ptr(), n, float(intensity_div), 1 if mask_labels else 0, _ptr(lut),
+                                       0 if lut is None else lut.numel(), rf, rt, 0 if clip_min is None else 1,
+                                       0.0 if clip_min is None else float(clip_min), rot, ca, sa, pc.data_ptr(), _ptr(valid), bad_count.data_ptr(),
+                                       _stream()), "slu_point_decode")
+    return pc, valid
+
+
+def spherical_projection_valid(pc: torch.Tensor, valid: torch.Tensor, height: int, width: int, theta_range=None, flip: bool = False,
+                               empty_count: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """spherical_projection over the points with valid[i] != 0 (the others take no part in the data theta range and win no pixel) -> img fp32
+    [H, W, C].  empty_count int32 [1]: += 1 when theta_range is None and no point is valid (the reference's theta.min() raises there)."""
+    _req(pc, "pc", torch.float64)
+    _req(valid, "valid", torch.uint8)
+    if pc.dim() != 2 or pc.shape[1] < 3 or pc.shape[0] == 0 or valid.dim() != 1 or valid.numel() != pc.shape[0]:
+        raise RuntimeError(f"spherical_projection_valid: pc [N, C >= 3] / valid [N] expected, got {tuple(pc.shape)} / {tuple(valid.shape)}")
+    if empty_count is not None:
+        _req(empty_count, "empty_count", torch.int32)
+    n, c = pc.shape
+    lib = _lib.load()
+    ws = torch.empty(lib.slu_spherical_projection_workspace_bytes(n, int(height), int(width)), dtype=torch.uint8, device=pc.device)
+    img = torch.empty((int(height), int(width), c), dtype=torch.float32, device=pc.device)
+    use_data = theta_range is None
+    tmin, tmax = (0.0, 0.0) if use_data else (float(theta_range[0]), float(theta_range[1]))
+    check(lib.slu_spherical_projection_valid(pc.data_ptr(), valid.data_ptr(), n, c, int(height), int(width), 1 if use_data else 0, tmin, tmax,
+                                             1 if flip else 0, ws.data_ptr(), ws.numel(), img.data_ptr(), _ptr(empty_count), _stream()),
+          "slu_spherical_projection_valid")
+    return img
+
+
+def organised_scan(records: torch.Tensor, label: torch.Tensor, lut: torch.Tensor, bad_count: torch.Tensor, height: int, width: int, flip: bool = False,
+                   shift: int = 0, rotate_deg: Optional[float] = None):
+    """An organised scan's file contents fp32 [H*W, 4] + label int32 [H*W] -> (img fp32 [H, W, 5], range fp32 [H, W]): id_map, flip, np.roll by
+    `shift` columns, yaw, in float64 and in that order; range is the float64 norm rounded to float32 (SemanticTHAB.__getitem__)."""
+    _req(records, "records")
+    _req(label, "label", torch.int32)
+    _req(lut, "lut", torch.int32)
+    _req(bad_count, "bad_count", torch.int32)
+    h, w = int(height), int(width)
+    if h < 1 or w < 1 or records.dim() != 2 or tuple(records.shape) != (h * w, 4) or label.dim() != 1 or label.numel() != h * w:
+        raise RuntimeError(f"organised_scan: records [{h * w}, 4] / label [{h * w}] expected for a {h} x {w} scan, got {tuple(records.shape)} / "
+                           f"{tuple(label.shape)}")
+    img = torch.empty((h, w, 5), dtype=torch.float32, device=records.device)
+    rng = torch.empty((h, w), dtype=torch.float32, device=records.device)
+    rot, ca, sa = _yaw(rotate_deg)
+    check(_lib.load().slu_organised_scan(records.data_ptr(), label.data_ptr(), h, w, lut.data_ptr(), lut.numel(), 1 if flip else 0, int(shift), rot, ca,
+                                         sa, img.data_ptr(), rng.data_ptr(), bad_count.data_ptr(), _stream()), "slu_organised_scan")
+    return img, rng
+
+
+def nonempty_rows(img: torch.Tensor) -> torch.Tensor:
+    """[H, W, C] fp32 image -> int32 [2 H + 1] on the device: [0] = H' = number of rows with a non-zero pixel, [1 .. H'] = their indices."""
+    _req(img, "img")
+    if img.dim() != 3 or img.numel() == 0:
+        raise RuntimeError(f"nonempty_rows: a non-empty [H, W, C] image expected, got {tuple(img.shape)}")
+    h, w, c = img.shape
+    rows = torch.empty(2 * h + 1, dtype=torch.int32, device=img.device)
+    check(_lib.load().slu_nonempty_rows(img.data_ptr(), h, w, c, rows.data_ptr(), _stream()), "slu_nonempty_rows")
+    return rows
+
+
+def resize_nearest_rows_hwc(img: torch.Tensor, rows: torch.Tensor, out_h: int, out_w: int, no_row_count: torch.Tensor, flip: bool = False) -> torch.Tensor:
+    """resize_nearest_hwc of the rows `nonempty_rows` kept [+ flip]; the kept-row count is read on the device.  No row kept: no_row_count
+    int32 [1] += 1 and zeros come back (the reference's cv2.resize raises; the caller raises when it reads the counter)."""
+    _req(img, "img")
+    _req(rows, "rows", torch.int32)
+    _req(no_row_count, "no_row_count", torch.int32)
+    if img.dim() != 3 or rows.numel() != 2 * img.shape[0] + 1 or no_row_count.numel() < 1 or int(out_h) < 1 or int(out_w) < 1:
+        raise RuntimeError(f"resize_nearest_rows_hwc: [H, W, C] image and its nonempty_rows table expected, got {tuple(img.shape)} / {tuple(rows.shape)}")
+    h, w, c = img.shape
+    out = torch.empty((int(out_h), int(out_w), c), dtype=torch.float32, device=img.device)
+    check(_lib.load().slu_resize_nearest_rows_hwc(img.data_ptr(), h, w, c, rows.data_ptr(), out.data_ptr(), int(out_h), int(out_w), 1 if flip else 0,
+                                                  no_row_count.data_ptr(), _stream()), "slu_resize_nearest_rows_hwc")
+    return out
+
+
+def channel_max(img: torch.Tensor, channel: int) -> torch.Tensor:
+    """Maximum of img[..., channel] of an [H, W, C] fp32 image as the uint32 key (held in an int32 [1] tensor) range_image_split takes."""
+    _req(img, "img")
+    if img.dim() != 3 or img.numel() == 0 or not 0 <= int(channel) < img.shape[2]:
+        raise RuntimeError(f"channel_max: a non-empty [H, W, C] image and a channel below C expected, got {tuple(img.shape)} / {channel}")
+    h, w, c = img.shape
+    key = torch.empty(1, dtype=torch.int32, device=img.device)
+    check(_lib.load().slu_channel_max(img.data_ptr(), h, w, c, int(channel), key.data_ptr(), _stream()), "slu_channel_max")
+    return key
+
+
+def channel_max_value(key: torch.Tensor) -> float:
+    """The float32 value a channel_max key stands for (a host read: for tests and tools)."""
+    import numpy as np
+    k = np.array([int(key.item()) & 0xFFFFFFFF], dtype=np.uint32)
+    u = np.where(k >> 31, k & np.uint32(0x7FFFFFFF), ~k)
+    return float(u.astype(np.uint32).view(np.float32)[0])
+
+
+def range_image_split_ex(img: torch.Tensor, normals: Optional[torch.Tensor], range_out, refl_out, xyz_out, normals_out, labels_out,
+                         range_in: Optional[torch.Tensor] = None, refl_max_key: Optional[torch.Tensor] = None) -> None:
+    """range_image_split with range_in fp32 [H, W] (copied instead of |xyz|: organised_scan's range) and / or refl_max_key (channel_max of
+    channel 3: reflectivity / max(maximum, 1) as a float32 division, SemanticCUDAL)."""
+    _req(img, "img")
+    h, w, c = img.shape
+    for t, nme, shape, dt in ((range_out, "range_out", (1, h, w), torch.float32), (refl_out, "refl_out", (1, h, w), torch.float32),
+                              (xyz_out, "xyz_out", (3, h, w), torch.float32), (labels_out, "labels_out", (1, h, w), torch.int64)):
+        _req(t, nme, dt)
+        if tuple(t.shape) != shape:
+            raise RuntimeError(f"{nme}: expected {shape}, got {tuple(t.shape)}")
+    if normals is not None:
+        _req(normals, "normals")
+        _req(normals_out, "normals_out")
+        if tuple(normals.shape) != (h, w, 3) or tuple(normals_out.shape) != (3, h, w):
+            raise RuntimeError("normals: expected [H, W, 3] in and [3, H, W] out")
+    if range_in is not None:
+        _req(range_in, "range_in")
+        if tuple(range_in.shape) != (h, w):
+            raise RuntimeError(f"range_in: expected {(h, w)}, got {tuple(range_in.shape)}")
+    if refl_max_key is not None:
+        _req(refl_max_key, "refl_max_key", torch.int32)
+    check(_lib.load().slu_range_image_split_ex(img.data_ptr(), _ptr(normals), h, w, c, _ptr(range_in), _ptr(refl_max_key), range_out.data_ptr(),
+                                               refl_out.data_ptr(), xyz_out.data_ptr(), _ptr(normals_out) if normals is not None else None,
+                                               labels_out.data_ptr(), _stream()), "slu_range_image_split_ex")
+
+
 # ------------------------------------------------------------------------------------------------
 # Dropout2d multipliers of a whole MC evaluation in one launch (csrc/dropout_draw.hip)
 # ------------------------------------------------------------------------------------------------

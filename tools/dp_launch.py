@@ -42,8 +42,9 @@ def parse(argv=None):
     ap.add_argument("--backend", default=None, help="torch.distributed backend (default: nccl = RCCL with a GPU, gloo without)")
     ap.add_argument("--seed", type=int, default=0, help="seed of the sharded permutation")
     ap.add_argument("--gpu-projection", action="store_true",
-                    help="SemanticKitti loaders: workers only read files, the main process decodes / projects whole batches on the GPU "
-                         "(semanticlidarunc_amd/dataset/gpu_pipeline.py); other datasets keep the stock loader")
+                    help="SemanticKitti / SemanticSTF / SemanticTHAB / SemanticCUDAL / SemanticWADS loaders: workers only read files, the main process "
+                         "decodes / projects whole batches on the GPU (semanticlidarunc_amd/dataset/gpu_pipeline.py); any other dataset keeps "
+                         "the stock loader")
     ap.add_argument("--trainer-module", default="models.trainer", help="module that defines Trainer (imported with the script's directory on sys.path)")
     # the script's own four flags (train_semantics.py:343-364); its `type=bool` flags treat every non-empty string as True
     ap.add_argument("--visualization", type=_str2bool, default=False)
@@ -126,7 +127,7 @@ def main(argv=None):
         # DataLoader workers only read the .bin / .label files; decode, id_map, rotation, spherical projection, flip,
         # range and normals run as HIP kernels on whole batches in this (the rank's main) process
         from semanticlidarunc_amd.dataset import gpu_pipeline
-        # duck-typed: in drop-in mode the script's dataset class comes from the module named `dataset.dataloader_semantic_KITTI`
+        # duck-typed: in drop-in mode the script's dataset class comes from a module named `dataset.dataloader_semantic_<NAME>`
         # (this repo's mirror under the reference's import path), a different module object than the package-qualified one
         base = gpu_pipeline.projecting_loader_class(lambda ds: ds.projector(torch.device("cuda", local_rank) if torch.cuda.is_available() else "cpu"),
                                                     lambda ds: getattr(ds, "_raw", None) if hasattr(ds, "projector") else None)
