@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SLU_ABI_VERSION 39
+#define SLU_ABI_VERSION 40
 
 #define SLU_OK            0
 #define SLU_EINVAL       -1   /* null pointer / non-positive size / inconsistent descriptor   */
@@ -777,6 +777,45 @@ typedef struct slu_shuffle_tail_desc {   /* HOST struct */
 size_t slu_shuffle_tail_packed_floats(int co, int c);
 int slu_shuffle_tail_pack(const float* w, int co, int c, float* out, slu_stream_t stream);
 int slu_shuffle_tail_fwd(const slu_shuffle_tail_desc* d, slu_stream_t stream);
+
+/* ---- SqueezeNet Fire module (models/semanticFCN.py:121-123,155-169 and baselines/Reichert/semanticFCN_opt.py:167-169,201-215 build torchvision's
+ * squeezenet1_0; the unit is torchvision's Fire, and the network has no BatchNorm) -----------------------------------------------------------
+ * slu_fire_fwd: squeeze 1x1 -> ReLU -> {expand 1x1, expand 3x3 / pad 1} -> ReLU -> concat in one launch:
+ *
+ *   s[n,k]        = relu( bsq[k] + sum_c wsq[k,c] * src[n,c] )                                       k < S
+ *   out[n,j]      = relu( b1[j] + sum_k w1[j,k] * s[n,k] )                                           j < E1
+ *   out[n,E1 + j] = relu( b3[j] + sum_{k,a,b} w3[j,k,a,b] * s[n,k, y-1+a, x-1+b] )                   j < E3
+ *
+ * src is the channel concatenation  src0[:, coff0 : coff0 + c0]  (+)  src1[:, :c1]  of dense NCHW fp32 tensors with ct0 / ct1 stored channels at
+ * H x W (src1 NULL, c1 = 0: one source); Cin = c0 + c1.  out is [N][E1 + E3][H][W].  The squeeze map lives in LDS with a one-pixel halo around a
+ * 4 x 32 output tile and never goes to global memory; outside the image it is 0 (the padding of the 3x3 -- not relu(bsq), not the squeeze of a
+ * clamped input), inside the image but outside the tile it is computed from the real input.  Every product is exact fp32
+ * (v_mfma_f32_32x32x2_f32) whatever the conv precision of the surrounding model; no atomics, so results are bit-identical run to run.
+ * wpack = slu_fire_pack of wsq [S][Cin], w1 [E1][S], w3 [E3][S][3][3] (slu_fire_packed_floats(Cin, S, E1, E3) floats, zero-filled outside the
+ * matrices; 0 = unsupported).  Any Cin >= 1, 1 <= S <= 64, 1 <= E1, E3 <= 256, N <= 65535, H W < 2^31; anything else is SLU_EUNSUPPORTED.
+ * out must not overlap an input (SLU_EINVAL).
+ * slu_maxpool3s2_ceil_fwd: nn.MaxPool2d(3, 2, padding=0, ceil_mode=True) over the same two-source concatenation -> y [N][c0 + c1][Ho][Wo],
+ * Ho = ceil((H - 3) / 2) + 1, Wo likewise; windows start at (2 oy, 2 ox) and are clipped at the far edge; H, W >= 3 (SLU_EINVAL below).  Not
+ * slu_maxpool3s2_fwd (padding 1): for even H the output size is the same and the windows are shifted by one. */
+typedef struct slu_fire_desc {   /* HOST struct */
+  const float* src0;
+  const float* src1;
+  int32_t ct0, coff0, c0;
+  int32_t ct1, c1;
+  int32_t N, H, W;
+  int32_t S, E1, E3;
+  int32_t reserved;
+  const float* wpack;
+  const float* bsq;      /* [S]  */
+  const float* b1;       /* [E1] */
+  const float* b3;       /* [E3] */
+  float* out;
+} slu_fire_desc;
+size_t slu_fire_packed_floats(int cin, int s, int e1, int e3);
+int slu_fire_pack(const float* wsq, const float* w1, const float* w3, int cin, int s, int e1, int e3, float* out, slu_stream_t stream);
+int slu_fire_fwd(const slu_fire_desc* d, slu_stream_t stream);
+int slu_maxpool3s2_ceil_fwd(const float* src0, int ct0, int coff0, int c0, const float* src1, int ct1, int c1, float* y, int N, int H, int W,
+                            slu_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-ABI_VERSION = 39
+ABI_VERSION = 40
 MAX_SRC = 3
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libslu_hip.so")
@@ -106,6 +106,19 @@ class ShuffleTailDesc(C.Structure):
         ("pass_ct", C.c_int32),
         ("wdw", C.c_void_p), ("bdw", C.c_void_p), ("wpack", C.c_void_p), ("bpw", C.c_void_p),
         ("pass_", C.c_void_p), ("out", C.c_void_p),
+    ]
+
+
+class FireDesc(C.Structure):
+    _fields_ = [
+        ("src0", C.c_void_p), ("src1", C.c_void_p),
+        ("ct0", C.c_int32), ("coff0", C.c_int32), ("c0", C.c_int32),
+        ("ct1", C.c_int32), ("c1", C.c_int32),
+        ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+        ("S", C.c_int32), ("E1", C.c_int32), ("E3", C.c_int32),
+        ("reserved", C.c_int32),
+        ("wpack", C.c_void_p), ("bsq", C.c_void_p), ("b1", C.c_void_p), ("b3", C.c_void_p),
+        ("out", C.c_void_p),
     ]
 
 
@@ -272,6 +285,10 @@ SIGNATURES = {
     "slu_shuffle_tail_packed_floats": (C.c_size_t, [C.c_int, C.c_int]),
     "slu_shuffle_tail_pack": (C.c_int, [c_f32p, C.c_int, C.c_int, c_f32p, c_stream]),
     "slu_shuffle_tail_fwd": (C.c_int, [C.POINTER(ShuffleTailDesc), c_stream]),
+    "slu_fire_packed_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "slu_fire_pack": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_stream]),
+    "slu_fire_fwd": (C.c_int, [C.POINTER(FireDesc), c_stream]),
+    "slu_maxpool3s2_ceil_fwd": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, C.c_int, c_f32p, C.c_int, C.c_int, C.c_int, c_stream]),
     "slu_resize_nearest_hwc": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, C.c_int, C.c_int, c_stream]),
     "slu_lovasz_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "slu_lovasz_fwd": (C.c_int, [c_f32p, c_i64p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_uint, C.c_void_p, C.c_size_t, c_f32p,

@@ -5,7 +5,7 @@ Contract kept: constructor keywords (plus the stale `resnet_type=` alias that sr
 `forward(x[B,cin,H,W], meta[B,m,H,W]) -> [B,num_classes,H,W]` (ELU + 1 > 0), and the `state_dict` layout including the
 aliased `stem.0.* / layerN.*` duplicates of `backbone.*` and the never-used `backbone.bn1.* / backbone.fc.*`
 (semanticFCN.py:146-153).  torchvision is not needed: the backbone container below re-creates the public
-resnet18/34 BasicBlock architecture (names, shapes), shufflenet.py the ShuffleNetV2 one; `pretrained` weights are not downloaded -- load a checkpoint.
+resnet18/34 BasicBlock architecture (names, shapes), shufflenet.py the ShuffleNetV2 one, squeezenet.py SqueezeNet 1.0; `pretrained` weights are not downloaded -- load a checkpoint.
 
 How the layers map onto kernels (inference; BatchNorm folded into the preceding conv's weights and bias):
   conv3x3/s1 + BN + ReLU ........ one fused conv launch (ReLU = leaky slope 0)
@@ -24,6 +24,13 @@ k4s4 / k4s4 / k2s2.  A unit (InvertedResidual) is the fused conv for branch2's f
 slu_shuffle_tail_fwd for depthwise 3x3 -> BN -> 1x1 -> BN -> ReLU -> concat -> channel shuffle (and the pass-through copy): 2 launches per
 stride-1 unit, 3 per stride-2 unit.  The tail's pointwise product is the exact-fp32 MFMA under "fp32" and "f16x3" alike; "f16" is refused.
 
+SqueezeNet 1.0 encoder (squeezenet1_0, inference only; container in squeezenet.py): stem = features[0:4] (conv + ReLU at stride 1, ceil-mode
+MaxPool, Fire), layer1 = features[4:6], layer2 = features[6:8] (MaxPool, Fire), layer3 = features[8:10], layer4 = features[10:] (Fire, MaxPool,
+Fire), so x1 .. x4 have 256 / 256 / 384 / 512 channels at 1/2, 1/4, 1/4, 1/8 resolution and the head's transposed convs are k4s4 / k2s2 / k2s2.  The
+meta channels are injected into layer2 (ahead of its pool) and layer3 only.  The stem conv is the fused conv; a Fire is ONE slu_fire_fwd launch
+(squeeze -> ReLU -> {1x1, 3x3} -> ReLU -> concat, the squeeze map in LDS), the pool slu_maxpool3s2_ceil_fwd; both read cat(x[:, :-m], meta_k) in
+place.  The Fire's products are the exact-fp32 MFMA under "fp32" and "f16x3" alike; "f16" is refused.
+
 Conv precision "f16" (resnet18 / resnet34, inference): the same layers on the half-precision storage path (h8.py) -- activations stay
 [N, G, H, W, 8] fp16 from the stem's input to the last conv's output (`_forward_h8`).  What differs from the list above: the space-to-depth
 kernel reads the meta channels from the full-resolution tensor itself (no down-sampled copies) and also writes phase (0,0) as a tensor of its
@@ -41,6 +48,7 @@ from . import h8 as _h8
 from . import ops
 from . import salsanext as _sn
 from . import shufflenet as _shf
+from . import squeezenet as _sqz
 from .ops import ConvSource
 
 
@@ -136,11 +144,12 @@ class SemanticNetworkWithFPN(nn.Module):
         if resnet_type is not None:          # stale keyword of src/inference_ouster.py:35
             backbone = resnet_type
         self.is_shuffle = backbone in _shf.BASE_CHANNELS
-        if backbone not in _RESNETS and not self.is_shuffle:
-            if backbone in ("regnet_y_400mf", "regnet_y_800mf", "regnet_y_1_6gf", "regnet_y_3_2gf", "squeezenet1_0", "efficientnet_v2_s",
-                            "efficientnet_v2_m", "efficientnet_v2_l"):
-                raise NotImplementedError(f"backbone '{backbone}' is not implemented on the HIP path yet (resnet18 / resnet34 / resnet50 and "
-                                          "shufflenet_v2_x0_5 / x1_0 / x1_5 / x2_0 are)")
+        self.is_squeeze = backbone in _sqz.BASE_CHANNELS
+        if backbone not in _RESNETS and not self.is_shuffle and not self.is_squeeze:
+            if backbone in ("regnet_y_400mf", "regnet_y_800mf", "regnet_y_1_6gf", "regnet_y_3_2gf", "efficientnet_v2_s", "efficientnet_v2_m",
+                            "efficientnet_v2_l"):
+                raise NotImplementedError(f"backbone '{backbone}' is not implemented on the HIP path yet (resnet18 / resnet34 / resnet50, "
+                                          "shufflenet_v2_x0_5 / x1_0 / x1_5 / x2_0 and squeezenet1_0 are)")
             raise ValueError("Invalid ResNet type. Supported types: 'resnet18', 'resnet34', 'resnet50', 'regnet_y_400mf','regnet_y_800mf', "
                              "'regnet_y_1_6gf', 'regnet_y_3_2gf', 'shufflenet_v2_x0_5', 'shufflenet_v2_x1_0', 'shufflenet_v2_x1_5', "
                              "'shufflenet_v2_x2_0.")
@@ -148,16 +157,23 @@ class SemanticNetworkWithFPN(nn.Module):
             raise NotImplementedError("only interpolation_mode='nearest' (the reference default) runs on the HIP path")
         self.backbone_name, self.interpolation_mode = backbone, interpolation_mode
         self.num_classes, self.attention, self.multi_scale_meta = num_classes, attention, multi_scale_meta
-        bc = self._build_shufflenet(backbone, input_channels, meta_channel_dim) if self.is_shuffle else self._build_encoder(backbone, input_channels, meta_channel_dim)
+        if self.is_shuffle:
+            bc = self._build_shufflenet(backbone, input_channels, meta_channel_dim)
+        elif self.is_squeeze:
+            bc = self._build_squeezenet(backbone, input_channels, meta_channel_dim)
+        else:
+            bc = self._build_encoder(backbone, input_channels, meta_channel_dim)
         self.attention4, self.attention3 = AttentionModule(bc[1], bc[1]), AttentionModule(bc[2], bc[2])
         self.attention2, self.attention1 = AttentionModule(bc[3], bc[3]), AttentionModule(bc[4], bc[4])
         self.fpn_block4, self.fpn_block3 = self._fpn(bc[0], bc[1]), self._fpn(bc[1], bc[2])
         self.fpn_block2, self.fpn_block1 = self._fpn(bc[2], bc[3]), self._fpn(bc[3], bc[4])
-        s4 = 4 if self.is_shuffle else 8      # semanticFCN.py:217-221: x3 and x4 both sit at 1/8 resolution under a ShuffleNetV2 encoder
+        # semanticFCN.py:217-233: x3 and x4 both sit at 1/8 resolution under a ShuffleNetV2 encoder, x2 and x3 both at 1/4 under SqueezeNet
+        s4 = 4 if self.is_shuffle or self.is_squeeze else 8
+        s3 = 2 if self.is_squeeze else 4
         self.upsample_layer_x4 = nn.ConvTranspose2d(bc[1], bc[1] // s4, s4, s4, 0)
-        self.upsample_layer_x3 = nn.ConvTranspose2d(bc[2], bc[2] // 4, 4, 4, 0)
+        self.upsample_layer_x3 = nn.ConvTranspose2d(bc[2], bc[2] // s3, s3, s3, 0)
         self.upsample_layer_x2 = nn.ConvTranspose2d(bc[3], bc[3] // 2, 2, 2, 0)
-        up = bc[1] // s4 + bc[2] // 4 + bc[3] // 2
+        up = bc[1] // s4 + bc[2] // s3 + bc[3] // 2
         self.decoder_semantic = nn.Sequential(
             nn.Conv2d(up + bc[4], bc[4], 3, 1, 1), nn.BatchNorm2d(bc[4]), nn.ReLU(inplace=True),
             nn.Conv2d(bc[4], bc[4], 3, 1, 1), nn.BatchNorm2d(bc[4]), nn.ReLU(inplace=True),
@@ -186,6 +202,17 @@ class SemanticNetworkWithFPN(nn.Module):
         self.stem = self.backbone.conv1
         self.layer1, self.layer2, self.layer3, self.layer4 = self.backbone.stage2, self.backbone.stage3, self.backbone.stage4, self.backbone.conv5
         return list(_shf.BASE_CHANNELS[backbone])
+
+    def _build_squeezenet(self, backbone, input_channels, meta_channel_dim):
+        """The torchvision-shaped SqueezeNet 1.0 with the reference's surgery (semanticFCN.py:155-169): features[0] replaced by a 3x3 / stride-1
+        conv over 2 + meta channels (the reference hard-codes the 2), `stem` = features[0:4], layer1..4 = features[4:6] / [6:8] / [8:10] / [10:].
+        Returns the channel ladder."""
+        self.meta_channel_dim = meta_channel_dim
+        self.backbone = _sqz.SqueezeNetContainer(backbone)
+        f = self.backbone.features
+        f[0] = nn.Conv2d(2 + meta_channel_dim, 96, kernel_size=3, stride=1, padding=1, bias=False)
+        self.stem, self.layer1, self.layer2, self.layer3, self.layer4 = f[0:4], f[4:6], f[6:8], f[8:10], f[10:]
+        return list(_sqz.BASE_CHANNELS[backbone])
 
     def _check_inputs(self, x, meta_channel):
         if not (isinstance(x, torch.Tensor) and isinstance(meta_channel, torch.Tensor)) or x.dim() != 4 or meta_channel.dim() != 4:
@@ -274,6 +301,61 @@ class SemanticNetworkWithFPN(nn.Module):
         if self._wants_autograd(x, meta):
             raise NotImplementedError(f"{cls} with the {self.backbone_name} backbone is inference only on the HIP path: call model.eval() and run "
                                       "under torch.no_grad() (the ShuffleNetV2 units have no backward kernels)")
+        if _sn.get_conv_precision() == "f16":
+            raise RuntimeError(f"{cls} with the {self.backbone_name} backbone does not run with conv precision 'f16': the half-precision "
+                               "storage path covers the BasicBlock backbones (resnet18 / resnet34) only; use set_conv_precision('fp32')")
+
+    # ---------------- SqueezeNet 1.0 encoder (semanticFCN.py:155-169, :287-295; squeezenet.py) ----------------
+    def _fire_params(self, name, fire):
+        """(wpack, bsq, b1, b3) of a Fire module, cached per parameter version like `_shf_tail` (every product is the exact-fp32 MFMA under
+        'fp32' and 'f16x3' alike)."""
+        cache = self.__dict__.setdefault("_fire_cache", {})
+        sq, e1, e3 = fire.squeeze, fire.expand1x1, fire.expand3x3
+        k = _key(sq.weight, sq.bias, e1.weight, e1.bias, e3.weight, e3.bias)
+        hit = cache.get(name)
+        if hit is None or hit[0] != k:
+            def f(t):
+                return t.detach().float().contiguous()
+            wpack = ops.pack_fire_weight(f(sq.weight).reshape(sq.out_channels, sq.in_channels), f(e1.weight).reshape(e1.out_channels, e1.in_channels),
+                                         f(e3.weight))
+            hit = cache[name] = (k, wpack, f(sq.bias), f(e1.bias), f(e3.bias))
+        return hit[1:]
+
+    def _sqz_modules(self, lname, modules, x, meta_k):
+        """A run of `features`: Fire = one slu_fire_fwd, MaxPool = slu_maxpool3s2_ceil_fwd.  meta_k: the meta channels that replace the last m
+        channels of x on the way into the first module (read in place as a second source)."""
+        for i, mod in enumerate(modules):
+            kw = {}
+            if i == 0 and meta_k is not None:
+                kw = dict(cuse=x.shape[1] - meta_k.shape[1], src2=meta_k)
+            if isinstance(mod, _sqz.Fire):
+                x = ops.fire(x, *self._fire_params(f"{lname}.{i}", mod), **kw)
+            elif isinstance(mod, nn.MaxPool2d):
+                x = ops.maxpool3s2_ceil(x, **kw)
+            else:
+                raise NotImplementedError(f"{type(mod).__name__} inside a SqueezeNet stage is not on the HIP path")
+        return x
+
+    def _encode_squeezenet(self, x, meta):
+        """(x1, x2, x3, x4) with 256 / 256 / 384 / 512 channels at 1/2, 1/4, 1/4, 1/8 resolution; the meta channels go into layer2 (ahead of its
+        pool) and layer3 only, meta3 is unused (semanticFCN.py:287-295)."""
+        m1 = m2 = None
+        if self.multi_scale_meta:
+            m1, m2 = ops.nearest_down(meta, 2), ops.nearest_down(meta, 4)
+        h = self._conv("stem", self.stem[0], None, [ConvSource(x), ConvSource(meta)])
+        xs = self._sqz_modules("stem", list(self.stem)[2:], h, None)
+        x1 = self._sqz_modules("layer1", self.layer1, xs, None)
+        x2 = self._sqz_modules("layer2", self.layer2, x1, m1)
+        x3 = self._sqz_modules("layer3", self.layer3, x2, m2)
+        x4 = self._sqz_modules("layer4", self.layer4, x3, None)
+        return x1, x2, x3, x4
+
+    def _squeezenet_guard(self, x, meta, cls: str):
+        """What the SqueezeNet encoder does not run: training / gradients (the Fire kernel and the ceil pool have no backward) and the
+        half-precision storage path."""
+        if self._wants_autograd(x, meta) or self.training:
+            raise NotImplementedError(f"{cls} with the {self.backbone_name} backbone is inference only on the HIP path: call model.eval() and run "
+                                      "under torch.no_grad() (the Fire module kernel has no backward)")
         if _sn.get_conv_precision() == "f16":
             raise RuntimeError(f"{cls} with the {self.backbone_name} backbone does not run with conv precision 'f16': the half-precision "
                                "storage path covers the BasicBlock backbones (resnet18 / resnet34) only; use set_conv_precision('fp32')")
@@ -627,6 +709,8 @@ class SemanticNetworkWithFPN(nn.Module):
         x, meta = self._check_inputs(x, meta_channel)
         if self.is_shuffle:
             self._shufflenet_guard(x, meta, "models/semanticFCN")
+        if self.is_squeeze:
+            self._squeezenet_guard(x, meta, "models/semanticFCN")
         if self._wants_autograd(x, meta):
             return self._forward_train(x, meta)
         if self.backbone_name == "resnet50" and _sn.get_conv_precision() == "f16x3":
@@ -637,7 +721,12 @@ class SemanticNetworkWithFPN(nn.Module):
                 raise RuntimeError("models/semanticFCN with the resnet50 backbone does not run with conv precision 'f16': the half-precision "
                                    "storage path covers the BasicBlock backbones (resnet18 / resnet34) only; use set_conv_precision('fp32')")
             return self._forward_h8(x, meta)
-        x1, x2, x3, x4 = self._encode_shufflenet(x, meta) if self.is_shuffle else self._encode(x, meta)
+        if self.is_shuffle:
+            x1, x2, x3, x4 = self._encode_shufflenet(x, meta)
+        elif self.is_squeeze:
+            x1, x2, x3, x4 = self._encode_squeezenet(x, meta)
+        else:
+            x1, x2, x3, x4 = self._encode(x, meta)
         f4 = self._conv("fpn4", self.fpn_block4[0], self.fpn_block4[1], [ConvSource(x4)])
         f3 = self._conv("fpn3", self.fpn_block3[0], self.fpn_block3[1], [ConvSource(x3)])
         f2 = self._conv("fpn2", self.fpn_block2[0], self.fpn_block2[1], [ConvSource(x2)])

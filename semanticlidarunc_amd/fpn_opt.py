@@ -1,6 +1,6 @@
 """The `semanticFCN_opt` variant of the ResNet-FPN segmenter on MI355X -- what the reference's `train_semantics.py:134` builds for
 `baseline: Reichert` (src/baselines/Reichert/semanticFCN_opt.py:109-455) -- for the resnet18 / resnet34 / resnet50, efficientnet_v2_s / m / l
-and (inference only, MC dropout on the stacked schedule) shufflenet_v2_x0_5 / x1_0 / x1_5 / x2_0 backbones.
+and (inference only, MC dropout on the stacked schedule) shufflenet_v2_x0_5 / x1_0 / x1_5 / x2_0 and squeezenet1_0 backbones.
 
 Same encoder as `fpn.SemanticNetworkWithFPN` (shared code); the head differs:
   SpatialAttention (:73-85)   1x1 (C -> C/8, no bias) + ReLU -> 1x1 (-> 1) -> softmax over H*W -> x * w + x
@@ -30,6 +30,7 @@ from . import h8 as _h8
 from . import ops
 from . import salsanext as _sn
 from . import shufflenet as _shf
+from . import squeezenet as _sqz
 from .fpn import SemanticNetworkWithFPN as _FPNBase
 from .fpn import _RESNETS
 from .ops import ConvSource
@@ -69,11 +70,12 @@ class SemanticNetworkWithFPN(_FPNBase):
         nn.Module.__init__(self)
         self.is_effnet = backbone in _eff.BASE_CHANNELS
         self.is_shuffle = backbone in _shf.BASE_CHANNELS
-        if backbone not in _RESNETS and not self.is_effnet and not self.is_shuffle:
-            known = ("regnet_y_400mf", "regnet_y_800mf", "regnet_y_1_6gf", "regnet_y_3_2gf", "squeezenet1_0")
+        self.is_squeeze = backbone in _sqz.BASE_CHANNELS
+        if backbone not in _RESNETS and not self.is_effnet and not self.is_shuffle and not self.is_squeeze:
+            known = ("regnet_y_400mf", "regnet_y_800mf", "regnet_y_1_6gf", "regnet_y_3_2gf")
             if backbone in known:
-                raise NotImplementedError(f"backbone '{backbone}' is not implemented on the HIP path yet (resnet18 / 34 / 50, efficientnet_v2_s / m / l "
-                                          "and shufflenet_v2_x0_5 / x1_0 / x1_5 / x2_0 are)")
+                raise NotImplementedError(f"backbone '{backbone}' is not implemented on the HIP path yet (resnet18 / 34 / 50, efficientnet_v2_s / m / l, "
+                                          "shufflenet_v2_x0_5 / x1_0 / x1_5 / x2_0 and squeezenet1_0 are)")
             raise ValueError("Invalid ResNet type. Supported types: 'resnet18', 'resnet34', 'resnet50', 'regnet_y_400mf','regnet_y_800mf', "
                              "'regnet_y_1_6gf', 'regnet_y_3_2gf', 'shufflenet_v2_x0_5', 'shufflenet_v2_x1_0', 'shufflenet_v2_x1_5', "
                              "'shufflenet_v2_x2_0.")
@@ -85,6 +87,8 @@ class SemanticNetworkWithFPN(_FPNBase):
             bc = self._build_effnet(backbone, input_channels, meta_channel_dim)
         elif self.is_shuffle:
             bc = self._build_shufflenet(backbone, input_channels, meta_channel_dim)
+        elif self.is_squeeze:
+            bc = self._build_squeezenet(backbone, input_channels, meta_channel_dim)
         else:
             bc = self._build_encoder(backbone, input_channels, meta_channel_dim)
         self.attention4, self.attention3 = SpatialAttention(bc[1]), SpatialAttention(bc[2])
@@ -93,7 +97,13 @@ class SemanticNetworkWithFPN(_FPNBase):
         self.fpn_block2, self.fpn_block1 = self._fpn(bc[2], bc[3]), self._fpn(bc[3], bc[4])
         self.dropout_pyramid = nn.Dropout2d(p=0.1)
         # semanticFCN_opt.py:270-285: the shufflenet and efficientnet branches set is_shuffle (x4 and x3 both sit at 1/8 resolution there)
-        scales, out_chs = ([4, 4, 2], [bc[1] // 4, bc[2] // 4, bc[3] // 2]) if self.is_effnet or self.is_shuffle else ([8, 4, 2], [bc[1] // 8, bc[2] // 4, bc[3] // 2])
+        # (and :274-278: x2 and x3 both sit at 1/4 resolution under SqueezeNet)
+        if self.is_effnet or self.is_shuffle:
+            scales, out_chs = [4, 4, 2], [bc[1] // 4, bc[2] // 4, bc[3] // 2]
+        elif self.is_squeeze:
+            scales, out_chs = [4, 2, 2], [bc[1] // 4, bc[2] // 2, bc[3] // 2]
+        else:
+            scales, out_chs = [8, 4, 2], [bc[1] // 8, bc[2] // 4, bc[3] // 2]
         self.upsample_layer_x4 = UpsampleBlock(bc[1], out_chs[0], scale=scales[0], mode="bilinear")
         self.upsample_layer_x3 = UpsampleBlock(bc[2], out_chs[1], scale=scales[1], mode="bilinear")
         self.upsample_layer_x2 = UpsampleBlock(bc[3], out_chs[2], scale=scales[2], mode="bilinear")
@@ -347,6 +357,8 @@ class SemanticNetworkWithFPN(_FPNBase):
             x1, x2, x3, x4 = self._encode_effnet(x, meta)
         elif self.is_shuffle:
             x1, x2, x3, x4 = self._encode_shufflenet(x, meta)
+        elif self.is_squeeze:
+            x1, x2, x3, x4 = self._encode_squeezenet(x, meta)
         else:
             x1, x2, x3, x4 = self._encode(x, meta)
         f4 = self._conv("fpn4", self.fpn_block4[0], self.fpn_block4[1], [ConvSource(x4)])
@@ -468,6 +480,8 @@ class SemanticNetworkWithFPN(_FPNBase):
         x, meta = self._check_inputs(x, meta_channel)
         if self.is_shuffle:
             self._shufflenet_guard(x, meta, "semanticFCN_opt")
+        if self.is_squeeze:
+            self._squeezenet_guard(x, meta, "semanticFCN_opt")
         if self._wants_autograd(x, meta):
             return self._forward_train_opt(x, meta, drop_scale)
         if self._use_h8():
@@ -483,7 +497,7 @@ class SemanticNetworkWithFPN(_FPNBase):
     def _mc_shared(self, x, meta_channel, T: int, scale, raw_head_input: bool):
         if self.training:
             raise RuntimeError("forward_mc needs the model in eval mode (use utils.mc_dropout.mc_forward)")
-        if self.is_shuffle:
+        if self.is_shuffle or self.is_squeeze:
             # the shared-prefix schedule runs the encoder at N = B and the stacked one at N = T B: equal to rounding, not verified bit for bit
             # for these encoders, so it is refused rather than allowed to differ silently
             raise RuntimeError(f"semanticFCN_opt with the {self.backbone_name} backbone runs MC dropout on the stacked schedule only: "

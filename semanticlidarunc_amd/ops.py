@@ -1890,3 +1890,95 @@ def shuffle_tail(src: torch.Tensor, wdw: torch.Tensor, bdw: torch.Tensor, wpack:
     d.wdw, d.bdw, d.wpack, d.bpw, d.out = wdw.data_ptr(), bdw.data_ptr(), wpack.data_ptr(), bpw.data_ptr(), out.data_ptr()
     check(lib.slu_shuffle_tail_fwd(C.byref(d), _stream()), "slu_shuffle_tail_fwd")
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# SqueezeNet Fire module and ceil-mode max-pool (csrc/fire_unit.hip)
+# ------------------------------------------------------------------------------------------------
+def _two_sources(src: torch.Tensor, coff: int, cuse: int, src2: Optional[torch.Tensor]):
+    """(n, h, w, ct0, coff, c0, ct1, c1) of cat(src[:, coff:coff + cuse], src2) (cuse = 0: every channel from coff on), checked."""
+    _req(src, "src")
+    if src.dim() != 4:
+        raise RuntimeError(f"src: expected NCHW, got {tuple(src.shape)}")
+    n, ct0, h, w = src.shape
+    coff, cuse = int(coff), int(cuse)
+    c0 = cuse if cuse else ct0 - coff
+    if coff < 0 or c0 <= 0 or coff + c0 > ct0:
+        raise RuntimeError(f"src: channel range [{coff}, {coff + c0}) is outside the tensor's {ct0} channels")
+    ct1 = c1 = 0
+    if src2 is not None:
+        _req(src2, "src2")
+        if src2.dim() != 4 or (src2.shape[0], src2.shape[2], src2.shape[3]) != (n, h, w) or src2.shape[1] == 0:
+            raise RuntimeError(f"src2: expected [{n}, > 0, {h}, {w}], got {tuple(src2.shape)}")
+        ct1 = c1 = src2.shape[1]
+    return n, h, w, ct0, coff, c0, ct1, c1
+
+
+def _overlaps(a: torch.Tensor, b: torch.Tensor) -> bool:
+    return a.data_ptr() < b.data_ptr() + b.numel() * b.element_size() and b.data_ptr() < a.data_ptr() + a.numel() * a.element_size()
+
+
+def pack_fire_weight(wsq: torch.Tensor, w1: torch.Tensor, w3: torch.Tensor) -> torch.Tensor:
+    """wsq [S, Cin], w1 [E1, S], w3 [E3, S, 3, 3] fp32 -> the MFMA A-fragment images slu_fire_fwd streams (re-run after every weight update)."""
+    for t, nme in ((wsq, "wsq"), (w1, "w1"), (w3, "w3")):
+        _req(t, nme)
+    if wsq.dim() != 2 or w1.dim() != 2 or w3.dim() != 4:
+        raise RuntimeError(f"pack_fire_weight: expected [S, Cin], [E1, S], [E3, S, 3, 3], got {tuple(wsq.shape)}, {tuple(w1.shape)}, {tuple(w3.shape)}")
+    s, cin = wsq.shape
+    e1, e3 = w1.shape[0], w3.shape[0]
+    if w1.shape[1] != s or tuple(w3.shape[1:]) != (s, 3, 3):
+        raise RuntimeError(f"pack_fire_weight: w1 {tuple(w1.shape)} / w3 {tuple(w3.shape)} do not match S = {s}")
+    lib = _lib.load()
+    n = lib.slu_fire_packed_floats(cin, s, e1, e3)
+    if n == 0:
+        raise _lib.SluError(f"slu_fire_pack: {lib.slu_strerror(-2).decode()} (code -2): Cin={cin} S={s} E1={e1} E3={e3}")
+    out = torch.empty(n, dtype=torch.float32, device=wsq.device)
+    check(lib.slu_fire_pack(wsq.data_ptr(), w1.data_ptr(), w3.data_ptr(), cin, s, e1, e3, out.data_ptr(), _stream()), "slu_fire_pack")
+    return out
+
+
+def fire(src: torch.Tensor, wpack: torch.Tensor, bsq: torch.Tensor, b1: torch.Tensor, b3: torch.Tensor, out: Optional[torch.Tensor] = None,
+         coff: int = 0, cuse: int = 0, src2: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One SqueezeNet Fire module in one launch (slu_fire_fwd): s = relu(squeeze 1x1), out = cat(relu(expand 1x1 (s)), relu(expand 3x3 / pad 1 (s)));
+    the squeeze map stays in LDS.  src is cat(src[:, coff:coff + cuse], src2) (cuse = 0: every channel from coff on; src2 optional),
+    wpack = pack_fire_weight(wsq, w1, w3), bsq [S], b1 [E1], b3 [E3].  out [N, E1 + E3, H, W] is allocated when not given and must not overlap an
+    input.  Every product is the exact-fp32 MFMA under every conv precision ('fp32' and 'f16x3' alike)."""
+    n, h, w, ct0, coff, c0, ct1, c1 = _two_sources(src, coff, cuse, src2)
+    for t, nme in ((bsq, "bsq"), (b1, "b1"), (b3, "b3")):
+        _req(t, nme)
+        if t.dim() != 1 or t.numel() == 0:
+            raise RuntimeError(f"{nme}: expected a non-empty vector, got {tuple(t.shape)}")
+    s, e1, e3 = bsq.numel(), b1.numel(), b3.numel()
+    lib = _lib.load()
+    _req(wpack, "wpack")
+    want = lib.slu_fire_packed_floats(c0 + c1, s, e1, e3)
+    if want == 0:
+        raise RuntimeError(f"fire: Cin={c0 + c1} S={s} E1={e1} E3={e3} is outside what slu_fire_fwd takes (S <= 64, E1 and E3 <= 256)")
+    if wpack.numel() != want:
+        raise RuntimeError(f"wpack: {wpack.numel()} floats does not match Cin={c0 + c1} S={s} E1={e1} E3={e3}")
+    if out is None:
+        out = torch.empty((n, e1 + e3, h, w), dtype=torch.float32, device=src.device)
+    else:
+        _req(out, "out")
+        if tuple(out.shape) != (n, e1 + e3, h, w):
+            raise RuntimeError(f"out: expected {(n, e1 + e3, h, w)}, got {tuple(out.shape)}")
+        if _overlaps(out, src) or (src2 is not None and _overlaps(out, src2)):
+            raise RuntimeError("fire: out must not overlap an input")
+    d = _lib.FireDesc()
+    d.src0, d.src1 = src.data_ptr(), _ptr(src2)
+    d.ct0, d.coff0, d.c0, d.ct1, d.c1 = ct0, coff, c0, ct1, c1
+    d.N, d.H, d.W, d.S, d.E1, d.E3 = n, h, w, s, e1, e3
+    d.wpack, d.bsq, d.b1, d.b3, d.out = wpack.data_ptr(), bsq.data_ptr(), b1.data_ptr(), b3.data_ptr(), out.data_ptr()
+    check(lib.slu_fire_fwd(C.byref(d), _stream()), "slu_fire_fwd")
+    return out
+
+
+def maxpool3s2_ceil(src: torch.Tensor, coff: int = 0, cuse: int = 0, src2: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """nn.MaxPool2d(3, 2, padding=0, ceil_mode=True) of cat(src[:, coff:coff + cuse], src2) -> [N, C, ceil((H - 3) / 2) + 1, ceil((W - 3) / 2) + 1]."""
+    n, h, w, ct0, coff, c0, ct1, c1 = _two_sources(src, coff, cuse, src2)
+    if h < 3 or w < 3:
+        raise RuntimeError(f"maxpool3s2_ceil: H and W must be at least 3, got {h} x {w}")
+    y = torch.empty((n, c0 + c1, (h - 2) // 2 + 1, (w - 2) // 2 + 1), dtype=torch.float32, device=src.device)
+    check(_lib.load().slu_maxpool3s2_ceil_fwd(src.data_ptr(), ct0, coff, c0, _ptr(src2), ct1, c1, y.data_ptr(), n, h, w, _stream()),
+          "slu_maxpool3s2_ceil_fwd")
+    return y
