@@ -39,7 +39,9 @@ __global__ __launch_bounds__(256) void pointwise_bwd_kernel(const float* __restr
   }
 }
 
-// first maximum of the 3x3 / stride 2 / pad 1 window of output (oy, ox) in row-major order (ATen keeps the first: `val > maxval`)
+// first maximum of the 3x3 / stride 2 / pad 1 window of output (oy, ox) in row-major order (ATen keeps the first: `val > maxval`).
+// Known divergence, untested: for a window whose values are all -inf no tap passes `v > m`, so -1 is returned and the window's gradient goes
+// nowhere, while ATen sends it to the window's first element.  The stem's pool follows a ReLU, so such a window does not occur.
 __device__ __forceinline__ int window_argmax(const float* __restrict__ p, int H, int W, int oy, int ox) {
   float m = -INFINITY;
   int arg = -1;

@@ -83,8 +83,10 @@ __device__ __forceinline__ float spatial_softmax_weight(float score, const float
 }
 
 // ---- bilinear taps: source index of ATen's area_pixel_compute_source_index (align_corners = False, not cubic): max(0, (dst + 0.5) / s - 0.5)
-// with inv_s = 1.0f / (float)s, exact for s = 2, 4, 8.  i1 = min(i0 + 1, n_in - 1), weights l0 = 1 - l1, l1 = src - i0.  The forward kernels and
-// the backward (which re-derives the forward's taps) call this one copy.
+// with inv_s = 1.0f / (float)s, exact for a power-of-two s.  i1 = min(i0 + 1, n_in - 1), weights l0 = 1 - l1, l1 = src - i0.  The forward kernels and
+// the backward (which re-derives the forward's taps) call this one copy.  The tests' 1e-6 bar on the forward holds for power-of-two scales only:
+// at s = 3, 5, 6 inv_s is rounded, and torch's own fp32 path is 1.2e-5 to 2.4e-5 from fp64 there (tests/test_gpu_pixel_kernel_edges.py).  s = 1
+// gives l1 = 0 and the input back bit for bit.
 __device__ __forceinline__ void bilinear_taps(int dst, float inv_s, int n_in, int& i0, int& i1, float& l0, float& l1) {
   float src = ((float)dst + 0.5f) * inv_s - 0.5f;
   src = src < 0.0f ? 0.0f : src;
