@@ -13,13 +13,19 @@ __global__ __launch_bounds__(256) void nchw_to_h8_kernel(const float* __restrict
     const size_t ng = e / HW;
     const int g = (int)(ng % G);
     const size_t n = ng / G;
-    float v[8];
+    // Without a multiplier the value is converted as it is: x * 1.0f and the conversion fuse into fma(x, 1, +0) -> fp16, which turns -0 into +0.
+    // (With a multiplier that fused form stays, one rounding of the exact product; it still stores +0 where x * scale is -0.)
+    const auto fill = [&](auto scaled) {
+      float v[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int c = g * 8 + k;
-      v[k] = c < C ? x[(n * C + c) * HW + pix] * (scale ? scale[n * C + c] : 1.0f) : 0.0f;
-    }
-    y[e] = h8_pack8(v);
+      for (int k = 0; k < 8; ++k) {
+        const int c = g * 8 + k;
+        v[k] = c >= C ? 0.0f : scaled ? x[(n * C + c) * HW + pix] * scale[n * C + c] : x[(n * C + c) * HW + pix];
+      }
+      y[e] = h8_pack8(v);
+    };
+    if (scale) fill(std::true_type{});
+    else fill(std::false_type{});
   }
 }
 

@@ -10,7 +10,8 @@ A *family* is one kernel (or a forward / backward pair) with
   bars    case -> {result: (coefficient, mode)}.
 Modes: ``exact`` torch.equal; ``abs`` the coefficient itself; ``rel`` coefficient * max(1, max|want|); ``elem`` the difference of each
 element divided by max(1, |want|) of that element against the coefficient; ``gap4`` four times the distance of the fp32 torch result
-from the fp64 one (the two GroupNorm offset inputs only, the ``_bar`` convention of test_gpu_fpn_train.py).  The coefficients are
+from the fp64 one (the two GroupNorm offset inputs only, the ``_bar`` convention of test_gpu_fpn_train.py).  ``ulp16`` / ``h16_worst`` /
+``same_bits`` are the half-ulp bar and the bit-pattern equality of the fp16-storing kernels' table (tests/h8_pixel_edge_cases.py).  The coefficients are
 those of the tests the project already has for the same ops (test_gpu_fpn.py, test_gpu_conv.py, test_gpu_fpn_train.py,
 test_gpu_fpn_opt.py, test_gpu_effnet.py).  A result key ``name#elem`` is a second look at result ``name``.
 
@@ -110,6 +111,34 @@ def cmp(tag, got, want64, want32, bar):
     assert diff <= bar, f"{tag}: {diff:.3e} > {bar:.3e}"
 
 
+# the bar mode of the fp16-storing kernels (tests/h8_pixel_edge_cases.py): |got - want64| <= ulp16(want64) / 2 + tol, an overflowing reference
+# value must come back as the infinity; and equality by bit pattern, which tells -0 from +0
+def ulp16(v):
+    a = v.double().abs()
+    a = torch.where(torch.isfinite(a) & (a > 0), a, torch.full_like(a, 2.0 ** -14))
+    e = torch.frexp(a)[1].double() - 1.0
+    return torch.exp2(e.clamp_min(-14.0) - 10.0)
+
+
+def h16_worst(got, want64, tol):
+    """(ok, worst error / allowed over the finite part, elements that should be an infinity and are not)"""
+    got, want64 = got.double(), want64.double()
+    over = want64.abs() >= 65520.0
+    allowed = ulp16(want64) / 2 + tol
+    err = torch.where(over, torch.zeros_like(want64), (got - want64).abs())
+    ratio = torch.where(over, torch.zeros_like(want64), err / allowed)
+    fine = bool((ratio <= 1.0).all())          # a NaN fails
+    bad_inf = int((over & (got != torch.sign(want64) * float("inf"))).sum())
+    worst = float(ratio.nan_to_num(nan=float("inf")).max()) if ratio.numel() else 0.0
+    return fine and bad_inf == 0, worst, bad_inf
+
+
+def same_bits(a, b):
+    """equality of two fp32 tensors of fp16 or fp32 values including the sign of zero"""
+    a, b = a.float().contiguous(), b.float().contiguous()
+    return a.shape == b.shape and torch.equal(a.view(torch.int32), b.view(torch.int32))
+
+
 def check(case: Case, got: Dict[str, torch.Tensor], want64, want32):
     """Every result of `got` against the references.  A key ``name@variant`` of `got` is held to reference ``name``."""
     seen = set()
@@ -156,9 +185,9 @@ def conditioning(case: Case, want64, want32):
     return out
 
 
-def evaluate(case: Case):
-    """(inputs, fp64 results, fp32 results)"""
-    fam = FAMILIES[case.family]
+def evaluate(case: Case, families=None):
+    """(inputs, fp64 results, fp32 results); families: another table than this module's"""
+    fam = (FAMILIES if families is None else families)[case.family]
     inputs = fam.build(case)
     with torch.enable_grad():
         return inputs, fam.ref(case, inputs, torch.float64), fam.ref(case, inputs, torch.float32)
