@@ -110,7 +110,8 @@ __global__ __launch_bounds__(256) void dirichlet_loss_kernel(const float* __rest
           if (c < C) {
             const float pc = a[c] / d, e = (c == y ? 1.0f : 0.0f) - pc;
             // d nn / d alpha_c = sum_j d[alpha_j (a0 - alpha_j)] = (a0 - alpha_c) - alpha_c + sum_{j} alpha_j = 2 a0 - 2 alpha_c
-            dst[(size_t)c * HW] = gs * (-2.0f * (e - cross) / d + ((2.0f * a0 - 2.0f * a[c]) * G - nn * dG) / (G * G));
+            // ((2 a0 - 2 alpha_c) G - nn dG) / G^2 divided through by G: G^2 leaves fp32 at alpha0 = 4e9, and the quotient became inf / inf
+            dst[(size_t)c * HW] = gs * (-2.0f * (e - cross) / d + ((2.0f * a0 - 2.0f * a[c]) - nn * (dG / G)) / G);
           }
       }
     } else if (kind == 5) {
@@ -121,43 +122,84 @@ __global__ __launch_bounds__(256) void dirichlet_loss_kernel(const float* __rest
         const float py_raw = ay / d, py = fmaxf(py_raw, eps);
         const float den_raw = 1.0f - py, den = fmaxf(den_raw, eps);
         const float lc1 = logf((float)(C - 1));
-        float kl = lc1, gt = 0.0f;                                  // gt = sum_c g_c tilde_c  (g_c = d kl / d tilde_c)
-#pragma unroll
-        for (int c = 0; c < CMAX; ++c)
-          if (c < C && c != y) {
-            const float tl = (a[c] / d) / den;
-            const float lt = logf(fmaxf(tl, eps));
-            kl += tl * lt;
-            gt += (lt + (tl >= eps ? 1.0f : 0.0f)) * tl;
-          }
         const float nrm = normalize ? 1.0f / lc1 : 1.0f;
-        kl *= nrm;
-        const float sg = sigmoidf((tau - py) / sigma);
-        const float wu = powf(1.0f - py, gamma) * sg;
         const float we = s_t >= 0.0f ? s_t / (d + s_t) : 1.0f;
-        v = wu * we * kl;
-        if constexpr (BWD) {
-          const float w = wu * we * nrm;
-          // d/d p_y: through denom = 1 - py (both clamps must be inactive), plus the gate when it is not detached
-          float Gy = (py_raw >= eps && den_raw >= eps) ? w * gt / den : 0.0f;
-          if (!detach && py_raw >= eps) {
-            const float dwu = -gamma * powf(1.0f - py, gamma - 1.0f) * sg - powf(1.0f - py, gamma) * sg * (1.0f - sg) / sigma;
-            Gy += dwu * we * kl;
-          }
-          float dot = Gy * py_raw;                                  // sum_c G_c p_c
+        const float sg = sigmoidf((tau - py) / sigma);
+        if (py_raw >= eps && den_raw >= eps) {
+          // Neither clamp of p_y is active: (1 - p_y) d is r = sum_{c != y} alpha_c + eps, summed without the true class, and the off-class
+          // conditional is tl_c = alpha_c / r.  With l_c = log(tl_c (C - 1)), which is 0 on a uniform column,
+          //   sum_c tl_c log tl_c + ln(C - 1) = A + ln(C - 1) rem + B,   A = sum_{tl >= eps} tl l,  rem = 1 - sum_{tl >= eps} tl,  B = sum_{tl < eps} tl ln eps
+          // and no term is a difference of rounded sums (the written-out form lost a near-uniform column's KL and gradient, 1e-9 at
+          // alpha = 1, in roundings of 1e-7).  r does not depend on alpha_y, so d kl / d alpha_y is 0 and
+          //   d kl / d alpha_c = (g_c - sum_j g_j tl_j) / r,   g_c = log max(tl_c, eps) + [tl_c >= eps].
+          float rest = 0.0f;
+#pragma unroll
+          for (int c = 0; c < CMAX; ++c) rest += (c < C && c != y) ? a[c] : 0.0f;
+          const float r = rest + eps, leps = logf(eps), cm1 = (float)(C - 1);
+          float A = 0.0f, B = 0.0f, low = eps;                        // low = eps + sum of the clamped alpha_c = rem * r
 #pragma unroll
           for (int c = 0; c < CMAX; ++c)
             if (c < C && c != y) {
-              const float pc = a[c] / d, tl = pc / den;
-              dot += w * (logf(fmaxf(tl, eps)) + (tl >= eps ? 1.0f : 0.0f)) / den * pc;
+              const float tl = a[c] / r;
+              if (tl >= eps) A += tl * logf(a[c] * cm1 / r);
+              else { B += tl * leps; low += a[c]; }
             }
+          const float rem = low / r;
+          const float kl = (A + lc1 * rem + B) * nrm;
+          const float om = r / d;                                     // 1 - p_y
+          const float wu = powf(om, gamma) * sg;
+          v = wu * we * kl;
+          if constexpr (BWD) {
+            const float w = wu * we * nrm;
+            const float dwy = detach ? 0.0f : (-gamma * powf(om, gamma - 1.0f) * sg - powf(om, gamma) * sg * (1.0f - sg) / sigma) * we * kl / d;
+            const float live_off = (1.0f - lc1) * rem - A - B;        // g_c - sum_j g_j tl_j of an entry with tl >= eps, less its l_c
+            const float dead_off = leps - A - B - (1.0f - lc1) * (1.0f - rem);
+#pragma unroll
+            for (int c = 0; c < CMAX; ++c)
+              if (c < C) {
+                float g;
+                if (c == y) g = dwy * om;
+                else {
+                  const float tl = a[c] / r;
+                  g = w * (tl >= eps ? logf(a[c] * cm1 / r) + live_off : dead_off) / r - dwy * py_raw;
+                }
+                dst[(size_t)c * HW] = gs * g;
+              }
+          }
+        } else {
+          // a clamp of p_y is active (py_raw < eps, or 1 - p_y < eps): the reference's form as written; d kl / d p_y is switched off
+          float kl = lc1;
 #pragma unroll
           for (int c = 0; c < CMAX; ++c)
-            if (c < C) {
-              const float pc = a[c] / d, tl = pc / den;
-              const float Gc = c == y ? Gy : w * (logf(fmaxf(tl, eps)) + (tl >= eps ? 1.0f : 0.0f)) / den;
-              dst[(size_t)c * HW] = gs * (Gc - dot) / d;
+            if (c < C && c != y) {
+              const float tl = (a[c] / d) / den;
+              kl += tl * logf(fmaxf(tl, eps));
             }
+          kl *= nrm;
+          const float wu = powf(1.0f - py, gamma) * sg;
+          v = wu * we * kl;
+          if constexpr (BWD) {
+            const float w = wu * we * nrm;
+            float Gy = 0.0f;                                          // the gate's own derivative, when it is not detached
+            if (!detach && py_raw >= eps) {
+              const float dwu = -gamma * powf(1.0f - py, gamma - 1.0f) * sg - powf(1.0f - py, gamma) * sg * (1.0f - sg) / sigma;
+              Gy += dwu * we * kl;
+            }
+            float dot = Gy * py_raw;                                  // sum_c G_c p_c
+#pragma unroll
+            for (int c = 0; c < CMAX; ++c)
+              if (c < C && c != y) {
+                const float pc = a[c] / d, tl = pc / den;
+                dot += w * (logf(fmaxf(tl, eps)) + (tl >= eps ? 1.0f : 0.0f)) / den * pc;
+              }
+#pragma unroll
+            for (int c = 0; c < CMAX; ++c)
+              if (c < C) {
+                const float pc = a[c] / d, tl = pc / den;
+                const float Gc = c == y ? Gy : w * (logf(fmaxf(tl, eps)) + (tl >= eps ? 1.0f : 0.0f)) / den;
+                dst[(size_t)c * HW] = gs * (Gc - dot) / d;
+              }
+          }
         }
       } else if constexpr (BWD) {
 #pragma unroll
