@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SLU_ABI_VERSION 40
+#define SLU_ABI_VERSION 41
 
 #define SLU_OK            0
 #define SLU_EINVAL       -1   /* null pointer / non-positive size / inconsistent descriptor   */
@@ -816,6 +816,33 @@ int slu_fire_pack(const float* wsq, const float* w1, const float* w3, int cin, i
 int slu_fire_fwd(const slu_fire_desc* d, slu_stream_t stream);
 int slu_maxpool3s2_ceil_fwd(const float* src0, int ct0, int coff0, int c0, const float* src1, int ct1, int c1, float* y, int N, int H, int W,
                             slu_stream_t stream);
+
+/* ---- RegNetY block (models/semanticFCN.py:97-108,171-179 and baselines/Reichert/semanticFCN_opt.py:143-154 build torchvision's
+ * regnet_y_{400mf,800mf,1_6gf,3_2gf}; the unit is torchvision's ResBottleneckBlock with a ReLU SqueezeExcitation) ---------------------------
+ * slu_regnet_gconv_fwd: f.b -- grouped 3x3 conv, pad 1, stride 1 or 2, gw = 8 / 16 / 24 channels per group, with the eval BatchNorm folded
+ * into the weights and bias, + ReLU, and the partial sums of the spatial mean of what it stores:
+ *
+ *   y[n, g gw + o, oy, ox] = relu( bias[g gw + o] + sum_{c < gw, a, b} w[g gw + o, c, a, b] * x[n, g gw + c, s oy - 1 + a, s ox - 1 + b] )
+ *   psum[n, c, t]          = sum of y[n, c] over the pixels of output tile t            t < T = slu_regnet_gconv_tiles(H, W, stride)
+ *
+ * x is channels [coff, coff + C) of a dense NCHW fp32 tensor with ct stored channels at H x W; y is [N][C][Ho][Wo], Ho = ceil(H / stride), Wo
+ * likewise; a stride-2 launch reads only the rows and columns it needs.  wg holds the weights as [C / gw][gw (c)][9 (tap)][gw (o)]: the
+ * 9 gw weights that one input channel of a group feeds are consecutive.  Exact fp32 (fmaf chains) whatever the conv precision of the
+ * surrounding model; no atomics: a tile's sum is reduced inside its workgroup in a fixed order, so y and psum are bit-identical run to run.
+ * C a multiple of gw, N <= 65535, H W < 2^31; any other gw is SLU_EUNSUPPORTED.
+ * slu_regnet_se_gate: mean[n, c] = inv_count * sum_t psum[n, c, t] (tile order), gate[n, c] = sigmoid(b2[c] + sum_s w2[c, s] *
+ * relu(b1[s] + sum_c' w1[s, c'] * mean[n, c'])) -- fc1 [S][C], ReLU, fc2 [C][S], sigmoid of torchvision's SqueezeExcitation as RegNet builds
+ * it (slu_se_gate is the SiLU form of EfficientNet).  psum [N][C][T]; T = 1 and inv_count = 1 take a plain [N][C] mean.  mean (optional,
+ * [N][C]) receives the means.  Any S >= 1 and C >= 1 with (C + S) * 4 <= 64 KiB.  The gate reaches f.c as slu_conv_src.scale.
+ * slu_regnet_sample2: y [N][c0 + c1][ceil(H / 2)][ceil(W / 2)] = cat(src0[:, coff0 : coff0 + c0], src1[:, :c1])[:, :, ::2, ::2] -- what the
+ * 1x1 / stride-2 projection of a stage's first block reads, with the meta channels in place. */
+int slu_regnet_gconv_tiles(int H, int W, int stride);
+int slu_regnet_gconv_fwd(const float* x, int ct, int coff, const float* wg, const float* bias, float* y, float* psum, int N, int C, int gw, int H, int W,
+                         int stride, slu_stream_t stream);
+int slu_regnet_se_gate(const float* psum, int T, float inv_count, const float* w1, const float* b1, const float* w2, const float* b2, float* gate,
+                       float* mean, int N, int C, int S, slu_stream_t stream);
+int slu_regnet_sample2(const float* src0, int ct0, int coff0, int c0, const float* src1, int ct1, int c1, float* y, int N, int H, int W,
+                       slu_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -5,7 +5,7 @@ Contract kept: constructor keywords (plus the stale `resnet_type=` alias that sr
 `forward(x[B,cin,H,W], meta[B,m,H,W]) -> [B,num_classes,H,W]` (ELU + 1 > 0), and the `state_dict` layout including the
 aliased `stem.0.* / layerN.*` duplicates of `backbone.*` and the never-used `backbone.bn1.* / backbone.fc.*`
 (semanticFCN.py:146-153).  torchvision is not needed: the backbone container below re-creates the public
-resnet18/34 BasicBlock architecture (names, shapes), shufflenet.py the ShuffleNetV2 one, squeezenet.py SqueezeNet 1.0; `pretrained` weights are not downloaded -- load a checkpoint.
+resnet18/34 BasicBlock architecture (names, shapes), shufflenet.py the ShuffleNetV2 one, squeezenet.py SqueezeNet 1.0, regnet.py RegNetY; `pretrained` weights are not downloaded -- load a checkpoint.
 
 How the layers map onto kernels (inference; BatchNorm folded into the preceding conv's weights and bias):
   conv3x3/s1 + BN + ReLU ........ one fused conv launch (ReLU = leaky slope 0)
@@ -31,6 +31,15 @@ meta channels are injected into layer2 (ahead of its pool) and layer3 only.  The
 (squeeze -> ReLU -> {1x1, 3x3} -> ReLU -> concat, the squeeze map in LDS), the pool slu_maxpool3s2_ceil_fwd; both read cat(x[:, :-m], meta_k) in
 place.  The Fire's products are the exact-fp32 MFMA under "fp32" and "f16x3" alike; "f16" is refused.
 
+RegNetY encoders (regnet_y_1_6gf / regnet_y_3_2gf, inference only; container and the block forward in regnet.py): stem = stem (conv + BN + ReLU at
+stride 1), layer1..4 = trunk_output[0..3], so x1 .. x4 sit at 1/2, 1/4, 1/8, 1/16 resolution with the four stage widths and the head is the
+default one (k8s8 / k4s4 / k2s2); the meta channels go into layer2, layer3 and layer4.  A Y block is the fused conv for f.a (reading
+(meta_k, x[:, :-m]) in place), slu_regnet_gconv_fwd for f.b (grouped 3x3 / stride + BN + ReLU + the tile sums of the SE's mean),
+slu_regnet_se_gate (mean -> fc1 -> ReLU -> fc2 -> sigmoid), and the fused conv for f.c with the gate as its per-(sample, channel) input multiplier,
+the identity (or proj over slu_regnet_sample2's stride-2 sampling) added before the ReLU: 4 launches per stride-1 block, 6 per stage entry.  The
+grouped conv is exact fp32 under "fp32" and "f16x3" alike; "f16" is refused.  regnet_y_400mf / regnet_y_800mf are built and tested up to the
+block forward but stay refused by name here.
+
 Conv precision "f16" (resnet18 / resnet34, inference): the same layers on the half-precision storage path (h8.py) -- activations stay
 [N, G, H, W, 8] fp16 from the stem's input to the last conv's output (`_forward_h8`).  What differs from the list above: the space-to-depth
 kernel reads the meta channels from the full-resolution tensor itself (no down-sampled copies) and also writes phase (0,0) as a tensor of its
@@ -46,6 +55,7 @@ import torch.nn as nn
 
 from . import h8 as _h8
 from . import ops
+from . import regnet as _rgn
 from . import salsanext as _sn
 from . import shufflenet as _shf
 from . import squeezenet as _sqz
@@ -145,11 +155,12 @@ class SemanticNetworkWithFPN(nn.Module):
             backbone = resnet_type
         self.is_shuffle = backbone in _shf.BASE_CHANNELS
         self.is_squeeze = backbone in _sqz.BASE_CHANNELS
-        if backbone not in _RESNETS and not self.is_shuffle and not self.is_squeeze:
+        self.is_regnet = backbone in _rgn.ENABLED
+        if backbone not in _RESNETS and not self.is_shuffle and not self.is_squeeze and not self.is_regnet:
             if backbone in ("regnet_y_400mf", "regnet_y_800mf", "regnet_y_1_6gf", "regnet_y_3_2gf", "efficientnet_v2_s", "efficientnet_v2_m",
                             "efficientnet_v2_l"):
                 raise NotImplementedError(f"backbone '{backbone}' is not implemented on the HIP path yet (resnet18 / resnet34 / resnet50, "
-                                          "shufflenet_v2_x0_5 / x1_0 / x1_5 / x2_0 and squeezenet1_0 are)")
+                                          "shufflenet_v2_x0_5 / x1_0 / x1_5 / x2_0 and squeezenet1_0 are, and so are regnet_y_1_6gf / regnet_y_3_2gf)")
             raise ValueError("Invalid ResNet type. Supported types: 'resnet18', 'resnet34', 'resnet50', 'regnet_y_400mf','regnet_y_800mf', "
                              "'regnet_y_1_6gf', 'regnet_y_3_2gf', 'shufflenet_v2_x0_5', 'shufflenet_v2_x1_0', 'shufflenet_v2_x1_5', "
                              "'shufflenet_v2_x2_0.")
@@ -161,6 +172,8 @@ class SemanticNetworkWithFPN(nn.Module):
             bc = self._build_shufflenet(backbone, input_channels, meta_channel_dim)
         elif self.is_squeeze:
             bc = self._build_squeezenet(backbone, input_channels, meta_channel_dim)
+        elif self.is_regnet:
+            bc = self._build_regnet(backbone, input_channels, meta_channel_dim)
         else:
             bc = self._build_encoder(backbone, input_channels, meta_channel_dim)
         self.attention4, self.attention3 = AttentionModule(bc[1], bc[1]), AttentionModule(bc[2], bc[2])
@@ -213,6 +226,18 @@ class SemanticNetworkWithFPN(nn.Module):
         f[0] = nn.Conv2d(2 + meta_channel_dim, 96, kernel_size=3, stride=1, padding=1, bias=False)
         self.stem, self.layer1, self.layer2, self.layer3, self.layer4 = f[0:4], f[4:6], f[6:8], f[8:10], f[10:]
         return list(_sqz.BASE_CHANNELS[backbone])
+
+    def _build_regnet(self, backbone, input_channels, meta_channel_dim):
+        """The torchvision-shaped RegNetY with the reference's surgery (semanticFCN.py:171-179): stem[0] replaced by a 3x3 / stride-1 conv over
+        input + meta channels, `stem` = stem (conv + BN + ReLU), layer1..4 = trunk_output[0..3].  Returns the channel ladder."""
+        self.meta_channel_dim = meta_channel_dim
+        self.backbone = _rgn.RegNetYContainer(backbone)
+        self.backbone.stem[0] = nn.Conv2d(input_channels + meta_channel_dim, self.backbone.stem[0].out_channels, kernel_size=3, stride=1, padding=1,
+                                          bias=False)
+        self.stem = self.backbone.stem
+        t = self.backbone.trunk_output
+        self.layer1, self.layer2, self.layer3, self.layer4 = t[0], t[1], t[2], t[3]
+        return list(_rgn.BASE_CHANNELS[backbone])
 
     def _check_inputs(self, x, meta_channel):
         if not (isinstance(x, torch.Tensor) and isinstance(meta_channel, torch.Tensor)) or x.dim() != 4 or meta_channel.dim() != 4:
@@ -356,6 +381,43 @@ class SemanticNetworkWithFPN(nn.Module):
         if self._wants_autograd(x, meta) or self.training:
             raise NotImplementedError(f"{cls} with the {self.backbone_name} backbone is inference only on the HIP path: call model.eval() and run "
                                       "under torch.no_grad() (the Fire module kernel has no backward)")
+        if _sn.get_conv_precision() == "f16":
+            raise RuntimeError(f"{cls} with the {self.backbone_name} backbone does not run with conv precision 'f16': the half-precision "
+                               "storage path covers the BasicBlock backbones (resnet18 / resnet34) only; use set_conv_precision('fp32')")
+
+    # ---------------- RegNetY encoder (semanticFCN.py:171-179, :305-314; regnet.py) ----------------
+    def _regnet_fb(self, name, conv: nn.Conv2d, bn):
+        """(wg, bias) of a Y block's grouped 3x3 conv with its BatchNorm folded in, in the order slu_regnet_gconv_fwd reads, cached per parameter
+        version like `_shf_tail` (the products are exact fp32 under 'fp32' and 'f16x3' alike)."""
+        cache = self.__dict__.setdefault("_regnet_cache", {})
+        k = _key(conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var)
+        hit = cache.get(name)
+        if hit is None or hit[0] != k:
+            w, b = self._fold(conv.weight, None, bn)
+            hit = cache[name] = (k, ops.pack_regnet_gconv_weight(w.detach().float().contiguous(), conv.in_channels // conv.groups),
+                                 b.detach().float().contiguous())
+        return hit[1:]
+
+    def _encode_regnet(self, x, meta):
+        """(x1, x2, x3, x4) at 1/2, 1/4, 1/8, 1/16 resolution: stem (conv + BN + ReLU, stride 1), the four stages of Y blocks
+        (regnet.y_block_forward), with the multi-scale meta injection on the way into layer2 / layer3 / layer4 (semanticFCN.py:305-314)."""
+        m1 = m2 = m3 = None
+        if self.multi_scale_meta:
+            m1, m2, m3 = ops.nearest_down(meta, 2), ops.nearest_down(meta, 4), ops.nearest_down(meta, 8)
+        h = self._conv("stem", self.stem[0], self.stem[1], [ConvSource(x), ConvSource(meta)])
+        outs = []
+        for lname, stage, mk in (("layer1", self.layer1, None), ("layer2", self.layer2, m1), ("layer3", self.layer3, m2), ("layer4", self.layer4, m3)):
+            for bi, blk in enumerate(stage):
+                h = _rgn.y_block_forward(self, f"{lname}.{bi}", blk, h, mk if bi == 0 else None)
+            outs.append(h)
+        return tuple(outs)
+
+    def _regnet_guard(self, x, meta, cls: str):
+        """What a RegNetY encoder does not run: training / gradients (the grouped conv and the gate have no backward) and the half-precision
+        storage path."""
+        if self._wants_autograd(x, meta) or self.training:
+            raise NotImplementedError(f"{cls} with the {self.backbone_name} backbone is inference only on the HIP path: call model.eval() and run "
+                                      "under torch.no_grad() (the grouped conv kernel of the Y block has no backward)")
         if _sn.get_conv_precision() == "f16":
             raise RuntimeError(f"{cls} with the {self.backbone_name} backbone does not run with conv precision 'f16': the half-precision "
                                "storage path covers the BasicBlock backbones (resnet18 / resnet34) only; use set_conv_precision('fp32')")
@@ -711,6 +773,8 @@ class SemanticNetworkWithFPN(nn.Module):
             self._shufflenet_guard(x, meta, "models/semanticFCN")
         if self.is_squeeze:
             self._squeezenet_guard(x, meta, "models/semanticFCN")
+        if self.is_regnet:
+            self._regnet_guard(x, meta, "models/semanticFCN")
         if self._wants_autograd(x, meta):
             return self._forward_train(x, meta)
         if self.backbone_name == "resnet50" and _sn.get_conv_precision() == "f16x3":
@@ -725,6 +789,8 @@ class SemanticNetworkWithFPN(nn.Module):
             x1, x2, x3, x4 = self._encode_shufflenet(x, meta)
         elif self.is_squeeze:
             x1, x2, x3, x4 = self._encode_squeezenet(x, meta)
+        elif self.is_regnet:
+            x1, x2, x3, x4 = self._encode_regnet(x, meta)
         else:
             x1, x2, x3, x4 = self._encode(x, meta)
         f4 = self._conv("fpn4", self.fpn_block4[0], self.fpn_block4[1], [ConvSource(x4)])

@@ -1,6 +1,7 @@
 """The `semanticFCN_opt` variant of the ResNet-FPN segmenter on MI355X -- what the reference's `train_semantics.py:134` builds for
 `baseline: Reichert` (src/baselines/Reichert/semanticFCN_opt.py:109-455) -- for the resnet18 / resnet34 / resnet50, efficientnet_v2_s / m / l
-and (inference only, MC dropout on the stacked schedule) shufflenet_v2_x0_5 / x1_0 / x1_5 / x2_0 and squeezenet1_0 backbones.
+and (inference only, MC dropout on the stacked schedule) shufflenet_v2_x0_5 / x1_0 / x1_5 / x2_0, squeezenet1_0 and regnet_y_1_6gf / regnet_y_3_2gf
+backbones (RegNetY: the default head -- UpsampleBlock scales 8 / 4 / 2 -- over `_encode_regnet` of fpn.py; regnet_y_400mf / 800mf stay refused by name).
 
 Same encoder as `fpn.SemanticNetworkWithFPN` (shared code); the head differs:
   SpatialAttention (:73-85)   1x1 (C -> C/8, no bias) + ReLU -> 1x1 (-> 1) -> softmax over H*W -> x * w + x
@@ -28,6 +29,7 @@ import torch.nn as nn
 from . import effnet as _eff
 from . import h8 as _h8
 from . import ops
+from . import regnet as _rgn
 from . import salsanext as _sn
 from . import shufflenet as _shf
 from . import squeezenet as _sqz
@@ -71,11 +73,12 @@ class SemanticNetworkWithFPN(_FPNBase):
         self.is_effnet = backbone in _eff.BASE_CHANNELS
         self.is_shuffle = backbone in _shf.BASE_CHANNELS
         self.is_squeeze = backbone in _sqz.BASE_CHANNELS
-        if backbone not in _RESNETS and not self.is_effnet and not self.is_shuffle and not self.is_squeeze:
+        self.is_regnet = backbone in _rgn.ENABLED
+        if backbone not in _RESNETS and not self.is_effnet and not self.is_shuffle and not self.is_squeeze and not self.is_regnet:
             known = ("regnet_y_400mf", "regnet_y_800mf", "regnet_y_1_6gf", "regnet_y_3_2gf")
             if backbone in known:
                 raise NotImplementedError(f"backbone '{backbone}' is not implemented on the HIP path yet (resnet18 / 34 / 50, efficientnet_v2_s / m / l, "
-                                          "shufflenet_v2_x0_5 / x1_0 / x1_5 / x2_0 and squeezenet1_0 are)")
+                                          "shufflenet_v2_x0_5 / x1_0 / x1_5 / x2_0 and squeezenet1_0 are, and so are regnet_y_1_6gf / regnet_y_3_2gf)")
             raise ValueError("Invalid ResNet type. Supported types: 'resnet18', 'resnet34', 'resnet50', 'regnet_y_400mf','regnet_y_800mf', "
                              "'regnet_y_1_6gf', 'regnet_y_3_2gf', 'shufflenet_v2_x0_5', 'shufflenet_v2_x1_0', 'shufflenet_v2_x1_5', "
                              "'shufflenet_v2_x2_0.")
@@ -89,6 +92,8 @@ class SemanticNetworkWithFPN(_FPNBase):
             bc = self._build_shufflenet(backbone, input_channels, meta_channel_dim)
         elif self.is_squeeze:
             bc = self._build_squeezenet(backbone, input_channels, meta_channel_dim)
+        elif self.is_regnet:
+            bc = self._build_regnet(backbone, input_channels, meta_channel_dim)
         else:
             bc = self._build_encoder(backbone, input_channels, meta_channel_dim)
         self.attention4, self.attention3 = SpatialAttention(bc[1]), SpatialAttention(bc[2])
@@ -359,6 +364,8 @@ class SemanticNetworkWithFPN(_FPNBase):
             x1, x2, x3, x4 = self._encode_shufflenet(x, meta)
         elif self.is_squeeze:
             x1, x2, x3, x4 = self._encode_squeezenet(x, meta)
+        elif self.is_regnet:
+            x1, x2, x3, x4 = self._encode_regnet(x, meta)
         else:
             x1, x2, x3, x4 = self._encode(x, meta)
         f4 = self._conv("fpn4", self.fpn_block4[0], self.fpn_block4[1], [ConvSource(x4)])
@@ -482,6 +489,8 @@ class SemanticNetworkWithFPN(_FPNBase):
             self._shufflenet_guard(x, meta, "semanticFCN_opt")
         if self.is_squeeze:
             self._squeezenet_guard(x, meta, "semanticFCN_opt")
+        if self.is_regnet:
+            self._regnet_guard(x, meta, "semanticFCN_opt")
         if self._wants_autograd(x, meta):
             return self._forward_train_opt(x, meta, drop_scale)
         if self._use_h8():
@@ -497,7 +506,7 @@ class SemanticNetworkWithFPN(_FPNBase):
     def _mc_shared(self, x, meta_channel, T: int, scale, raw_head_input: bool):
         if self.training:
             raise RuntimeError("forward_mc needs the model in eval mode (use utils.mc_dropout.mc_forward)")
-        if self.is_shuffle or self.is_squeeze:
+        if self.is_shuffle or self.is_squeeze or self.is_regnet:
             # the shared-prefix schedule runs the encoder at N = B and the stacked one at N = T B: equal to rounding, not verified bit for bit
             # for these encoders, so it is refused rather than allowed to differ silently
             raise RuntimeError(f"semanticFCN_opt with the {self.backbone_name} backbone runs MC dropout on the stacked schedule only: "

@@ -1982,3 +1982,102 @@ def maxpool3s2_ceil(src: torch.Tensor, coff: int = 0, cuse: int = 0, src2: Optio
     check(_lib.load().slu_maxpool3s2_ceil_fwd(src.data_ptr(), ct0, coff, c0, _ptr(src2), ct1, c1, y.data_ptr(), n, h, w, _stream()),
           "slu_maxpool3s2_ceil_fwd")
     return y
+
+
+# ------------------------------------------------------------------------------------------------
+# RegNetY block: grouped 3x3 conv + SE mean, ReLU SE gate, stride-2 sampling (csrc/regnet_unit.hip)
+# ------------------------------------------------------------------------------------------------
+REGNET_GROUP_WIDTHS = (8, 16, 24)
+
+
+def pack_regnet_gconv_weight(w: torch.Tensor, gw: int) -> torch.Tensor:
+    """[C, gw, 3, 3] weight of a grouped 3x3 conv (groups = C / gw) -> [C / gw, gw (c), 9, gw (o)], the order slu_regnet_gconv_fwd reads: the
+    9 gw weights one input channel of a group feeds are consecutive (re-run after every weight update)."""
+    _req(w, "w")
+    gw = int(gw)
+    if gw not in REGNET_GROUP_WIDTHS:
+        raise RuntimeError(f"pack_regnet_gconv_weight: group width {gw} is not one of {REGNET_GROUP_WIDTHS}")
+    if w.dim() != 4 or tuple(w.shape[1:]) != (gw, 3, 3) or w.shape[0] % gw:
+        raise RuntimeError(f"pack_regnet_gconv_weight: expected [C, {gw}, 3, 3] with C a multiple of {gw}, got {tuple(w.shape)}")
+    return w.reshape(w.shape[0] // gw, gw, gw, 9).permute(0, 2, 3, 1).contiguous()
+
+
+def regnet_gconv(x: torch.Tensor, wg: torch.Tensor, bias: torch.Tensor, stride: int = 1, coff: int = 0, cuse: int = 0,
+                 out: Optional[torch.Tensor] = None):
+    """RegNet's f.b in one launch (slu_regnet_gconv_fwd): y = relu(grouped conv3x3 / pad 1 / stride (x[:, coff:coff + cuse]) + bias) with
+    wg = pack_regnet_gconv_weight(w, gw) (eval BatchNorm folded in by the caller), cuse = 0: every channel from coff on.  Returns (y [N, C, Ho, Wo],
+    psum [N, C, T]): psum holds the per-tile sums of y, which regnet_se_gate turns into the SqueezeExcitation's mean without reading y back.
+    Exact fp32 under every conv precision; bit-identical run to run."""
+    _req(x, "x")
+    if x.dim() != 4:
+        raise RuntimeError(f"x: expected NCHW, got {tuple(x.shape)}")
+    n, ct, h, w = x.shape
+    coff, cuse = int(coff), int(cuse)
+    c = cuse if cuse else ct - coff
+    if coff < 0 or c <= 0 or coff + c > ct:
+        raise RuntimeError(f"x: channel range [{coff}, {coff + c}) is outside the tensor's {ct} channels")
+    _req(wg, "wg")
+    if wg.dim() != 4 or wg.shape[1] != wg.shape[3] or wg.shape[2] != 9 or wg.shape[1] not in REGNET_GROUP_WIDTHS:
+        raise RuntimeError(f"wg: expected [G, gw, 9, gw] with gw in {REGNET_GROUP_WIDTHS}, got {tuple(wg.shape)}")
+    gw = wg.shape[1]
+    if wg.shape[0] * gw != c:
+        raise RuntimeError(f"wg: {wg.shape[0]} groups of {gw} do not make the {c} input channels")
+    _req(bias, "bias")
+    if tuple(bias.shape) != (c,):
+        raise RuntimeError(f"bias: expected ({c},), got {tuple(bias.shape)}")
+    if stride not in (1, 2):
+        raise RuntimeError("regnet_gconv: stride must be 1 or 2")
+    lib = _lib.load()
+    ho, wo = (h + stride - 1) // stride, (w + stride - 1) // stride
+    if out is None:
+        out = torch.empty((n, c, ho, wo), dtype=torch.float32, device=x.device)
+    else:
+        _req(out, "out")
+        if tuple(out.shape) != (n, c, ho, wo):
+            raise RuntimeError(f"out: expected {(n, c, ho, wo)}, got {tuple(out.shape)}")
+        if _overlaps(out, x):
+            raise RuntimeError("regnet_gconv: out must not overlap the input")
+    t = lib.slu_regnet_gconv_tiles(h, w, int(stride))
+    if t <= 0:
+        raise RuntimeError(f"regnet_gconv: a {h} x {w} map is outside what slu_regnet_gconv_fwd takes")
+    psum = torch.empty((n, c, t), dtype=torch.float32, device=x.device)
+    check(lib.slu_regnet_gconv_fwd(x.data_ptr(), ct, coff, wg.data_ptr(), bias.data_ptr(), out.data_ptr(), psum.data_ptr(), n, c, gw, h, w, int(stride),
+                                   _stream()), "slu_regnet_gconv_fwd")
+    return out, psum
+
+
+def regnet_se_gate(psum: torch.Tensor, count: int, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, want_mean: bool = False):
+    """RegNet's SqueezeExcitation multiplier [N, C] = sigmoid(fc2(relu(fc1(mean)))) with mean = psum.sum(-1) / count (summed in tile order on the
+    device); psum [N, C, T] from regnet_gconv with count = Ho Wo, or a plain mean as [N, C, 1] (or [N, C]) with count = 1.  w1 [S, C], b1 [S],
+    w2 [C, S], b2 [C].  want_mean: returns (gate, mean)."""
+    _req(psum, "psum")
+    if psum.dim() == 2:
+        psum = psum.unsqueeze(2)
+    if psum.dim() != 3 or psum.numel() == 0:
+        raise RuntimeError(f"psum: expected [N, C, T], got {tuple(psum.shape)}")
+    n, c, t = psum.shape
+    if int(count) < 1:
+        raise RuntimeError("regnet_se_gate: count must be positive")
+    _req(w1, "w1")
+    if w1.dim() != 2 or w1.shape[1] != c or w1.shape[0] == 0:
+        raise RuntimeError(f"w1: expected [S, {c}], got {tuple(w1.shape)}")
+    s = w1.shape[0]
+    for tns, nme, shp in ((b1, "b1", (s,)), (w2, "w2", (c, s)), (b2, "b2", (c,))):
+        _req(tns, nme)
+        if tuple(tns.shape) != shp:
+            raise RuntimeError(f"{nme}: expected {shp}, got {tuple(tns.shape)}")
+    if (c + s) * 4 > 64 * 1024:
+        raise RuntimeError(f"regnet_se_gate: C + S = {c + s} does not fit the kernel's 64 KiB of LDS")
+    gate = torch.empty((n, c), dtype=torch.float32, device=psum.device)
+    mean = torch.empty((n, c), dtype=torch.float32, device=psum.device) if want_mean else None
+    check(_lib.load().slu_regnet_se_gate(psum.data_ptr(), t, 1.0 / float(count), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
+                                         gate.data_ptr(), _ptr(mean), n, c, s, _stream()), "slu_regnet_se_gate")
+    return (gate, mean) if want_mean else gate
+
+
+def regnet_sample2(src: torch.Tensor, coff: int = 0, cuse: int = 0, src2: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """cat(src[:, coff:coff + cuse], src2)[:, :, ::2, ::2] -> [N, C, ceil(H / 2), ceil(W / 2)]: the input of a 1x1 / stride-2 projection."""
+    n, h, w, ct0, coff, c0, ct1, c1 = _two_sources(src, coff, cuse, src2)
+    y = torch.empty((n, c0 + c1, (h + 1) // 2, (w + 1) // 2), dtype=torch.float32, device=src.device)
+    check(_lib.load().slu_regnet_sample2(src.data_ptr(), ct0, coff, c0, _ptr(src2), ct1, c1, y.data_ptr(), n, h, w, _stream()), "slu_regnet_sample2")
+    return y
