@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SLU_ABI_VERSION 41
+#define SLU_ABI_VERSION 42
 
 #define SLU_OK            0
 #define SLU_EINVAL       -1   /* null pointer / non-positive size / inconsistent descriptor   */
@@ -843,6 +843,29 @@ int slu_regnet_se_gate(const float* psum, int T, float inv_count, const float* w
                        float* mean, int N, int C, int S, slu_stream_t stream);
 int slu_regnet_sample2(const float* src0, int ct0, int coff0, int c0, const float* src1, int ct1, int c1, float* y, int N, int H, int W,
                        slu_stream_t stream);
+
+/* ---- EfficientNetV2 MBConv middle (models/semanticFCN.py:124-135,192-201 builds torchvision's efficientnet_v2_{s,m,l}; the unit is torchvision's
+ * MBConv: depthwise 3x3 + BatchNorm + SiLU, then a SqueezeExcitation with SiLU between its two layers) -----------------------------------------
+ * slu_dwconv3x3_se_fwd: depthwise 3x3 conv, pad 1, stride 1 or 2, with the eval BatchNorm folded into the weights and bias, + SiLU, and the
+ * partial sums of the spatial mean of what it stores:
+ *
+ *   y[n, c, oy, ox] = silu( bias[c] + sum_{a, b} w[c, 3 a + b] * x[n, c, s oy - 1 + a, s ox - 1 + b] )
+ *   psum[n, c, t]   = sum of y[n, c] over the rows of output tile t                       t < T = slu_dwconv3x3_se_tiles(H, W, stride)
+ *
+ * x is a dense NCHW fp32 tensor at H x W, w [C][9], bias [C]; y is [N][C][Ho][Wo], Ho = ceil(H / stride), Wo likewise; psum is [N][C][T].  A tile
+ * is a run of whole output rows (about 2048 outputs: an 8 x 256 plane is one tile), reduced inside its workgroup in a fixed order: no atomics,
+ * so y and psum are bit-identical run to run.  y equals slu_dwconv3x3_fwd(act = SiLU) bit for bit.  16-byte loads where W % 4 == 0 and x is
+ * 16-byte aligned, 16-byte stores where Wo % 4 == 0 and y is; any other width takes a scalar route.  N, C <= 65535, H W < 2^31, W up to about
+ * 5000 (three input rows must fit the kernel's LDS): anything else is SLU_EUNSUPPORTED, and slu_dwconv3x3_se_tiles returns 0 for it.
+ * slu_se_gate_psum: mean[n, c] = inv_count * sum_t psum[n, c, t] (tile order), scale[n, c] = sigmoid(b2[c] + sum_s w2[c, s] *
+ * silu(b1[s] + sum_c' w1[s, c'] * mean[n, c'])) -- slu_se_gate reading the tile sums instead of a pooled vector.  fc1 [S][C], fc2 [C][S], both
+ * biases required; T = 1 and inv_count = 1 take a plain [N][C] mean.  C <= 1536 and S <= 96 as slu_se_gate; anything else is SLU_EINVAL.  The
+ * scale reaches the projection conv as slu_conv_src.scale. */
+int slu_dwconv3x3_se_tiles(int H, int W, int stride);
+int slu_dwconv3x3_se_fwd(const float* x, const float* w, const float* bias, float* y, float* psum, int N, int C, int H, int W, int stride,
+                         slu_stream_t stream);
+int slu_se_gate_psum(const float* psum, int T, float inv_count, const float* w1, const float* b1, const float* w2, const float* b2, float* scale,
+                     int N, int C, int S, slu_stream_t stream);
 
 #ifdef __cplusplus
 }

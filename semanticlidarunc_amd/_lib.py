@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-ABI_VERSION = 41
+ABI_VERSION = 42
 MAX_SRC = 3
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libslu_hip.so")
@@ -294,6 +294,9 @@ SIGNATURES = {
                                        c_stream]),
     "slu_regnet_se_gate": (C.c_int, [c_f32p, C.c_int, C.c_float, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, c_stream]),
     "slu_regnet_sample2": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, C.c_int, c_f32p, C.c_int, C.c_int, C.c_int, c_stream]),
+    "slu_dwconv3x3_se_tiles": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "slu_dwconv3x3_se_fwd": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_stream]),
+    "slu_se_gate_psum": (C.c_int, [c_f32p, C.c_int, C.c_float, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, c_stream]),
     "slu_resize_nearest_hwc": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, C.c_int, C.c_int, c_stream]),
     "slu_lovasz_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "slu_lovasz_fwd": (C.c_int, [c_f32p, c_i64p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_uint, C.c_void_p, C.c_size_t, c_f32p,

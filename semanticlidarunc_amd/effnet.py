@@ -1,9 +1,12 @@
-"""EfficientNetV2 backbone container for the `semanticFCN_opt` segmenter (reference baselines/Reichert/semanticFCN_opt.py:170-180 builds
+"""EfficientNetV2 backbone container for the FPN segmenters, and the forward of one block on the HIP kernels for `models.semanticFCN`
+(`block_forward`, fpn.py `_encode_effnet`; reference models/semanticFCN.py:124-135,192-201,296-304 wires the backbone exactly as `semanticFCN_opt`
+does).  The container was written for the `semanticFCN_opt` segmenter (reference baselines/Reichert/semanticFCN_opt.py:170-180 builds
 torchvision's `efficientnet_v2_{s,m,l}`, :238-247 replaces `features[0][0]` by a 3x3 / stride-1 conv over input + meta channels and wires
 `stem = features[0]`, `layer1..3 = features[2..4]`, `layer4 = features[6:]`; its forward (:396-404) never calls layer4 nor features[1] / [5]).
 
 torchvision is not needed: the classes below re-create the public architecture of torchvision 0.19's `efficientnet.py` -- module names,
-parameter shapes and therefore `state_dict` keys -- without a forward (the arithmetic lives in fpn_opt.py on the HIP kernels); `pretrained`
+parameter shapes and therefore `state_dict` keys -- without a module forward (the arithmetic lives in `block_forward` below and, for
+`semanticFCN_opt`, in fpn_opt.py, on the HIP kernels); `pretrained`
 weights are not downloaded, load a checkpoint.  **Parity of the block internals is unpinned** (no reference-held fixture): the
 oracle (oracle/effnet.py) restates the same public definition, and the reference's OWN head / meta-injection wiring is pinned through it."""
 from __future__ import annotations
@@ -12,6 +15,10 @@ import math
 from typing import List, Tuple
 
 import torch.nn as nn
+
+from . import ops
+from . import salsanext as _sn
+from .ops import ConvSource
 
 # (block kind, expand ratio, kernel, stride, input channels, output channels, layers) -- torchvision's _efficientnet_conf for the V2 family
 _CONFIGS = {
@@ -127,3 +134,61 @@ def stage_channels(name: str) -> Tuple[int, int, int, int]:
     """(stem, features[2], features[3], features[4]) output channels."""
     conf = _CONFIGS[name][0]
     return conf[0][4], conf[1][5], conf[2][5], conf[3][5]
+
+
+# ----------------------------------------------------------------------------------------------------------------
+def _cna(host, name, cna, srcs, resid=None, tail_first=0):
+    """Conv2dNormActivation with a dense stride-1 conv: conv -> folded BatchNorm -> SiLU (or none) [+ resid] as one fused conv launch."""
+    return host._conv(name, cna[0], cna[1], srcs, act="silu" if len(cna) > 2 else "none", resid=resid, tail_first=tail_first)
+
+
+def folded_depthwise(host, name, cna):
+    """(w [C, 9], bias [C]) of a depthwise Conv2dNormActivation with the eval BatchNorm folded in, cached on `host` per parameter version (exact
+    fp32 under every conv precision, so the precision is not part of the key's meaning -- it is kept in it as in the packed-conv cache)."""
+    conv, bn = cna[0], cna[1]
+    cache = host.__dict__.setdefault("_dw_cache", {})
+    key = tuple((t.data_ptr(), t._version) for t in (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var)) + (_sn.get_conv_precision(),)
+    hit = cache.get(name)
+    if hit is None or hit[0] != key:
+        w, b = host._fold(conv.weight, None, bn)
+        hit = cache[name] = (key, w.detach().float().reshape(w.shape[0], 9).contiguous(), b.detach().float().contiguous())
+    return hit[1], hit[2]
+
+
+def block_forward(host, name: str, blk, x, meta_k=None):
+    """One FusedMBConv / MBConv block, eval mode (StochasticDepth = identity), on the HIP kernels.  `host` is the FPN model: its `_conv` /
+    `_conv_s2` run the fused convs with their folded BatchNorm from its packed-weight cache.  meta_k: the meta channels, at the block's input
+    resolution, that replace the last m channels of x on the way in (first block of layer2 / layer3).
+
+      FusedMBConv   3x3 expansion (+ BN + SiLU): the fused conv; at stride 2 the 2x2 conv over space_to_depth2(_cat) of the input; then the 1x1
+                    projection (+ BN) with the identity added where the block has one
+      MBConv        expand   fused 1x1 conv (+ BN + SiLU); with meta_k it reads (meta_k, x[:, :-m]) in place, the weight's input channels rotated
+                    dw       slu_dwconv3x3_se_fwd: depthwise 3x3 / stride + BN + SiLU + the per-tile sums of the SE's mean, one launch
+                    gate     slu_se_gate_psum: tile sums -> mean -> fc1 -> SiLU -> fc2 -> sigmoid, one launch
+                    project  fused 1x1 conv (+ BN) with the gate as the per-(sample, channel) input multiplier, + identity
+                    -- four launches; the expanded map is written once and read once."""
+    seq = blk.block
+    cx = x.shape[1]
+    m = 0 if meta_k is None else meta_k.shape[1]
+    resid = x if blk.use_res_connect else None
+    src = [ConvSource(x)] if meta_k is None else [ConvSource(meta_k), ConvSource(x, None, False, 0, cx - m)]      # (meta, x[:, :-m])
+    if isinstance(blk, FusedMBConv):
+        first = seq[0]
+        if first[0].stride[0] == 2:
+            s2d = ops.space_to_depth2(x) if meta_k is None else ops.space_to_depth2_cat(x, cx - m, meta_k)
+            h = host._conv_s2(name + ".0", first[0], first[1], s2d, cx, act="silu" if len(first) > 2 else "none")
+        else:
+            h = _cna(host, name + ".0", first, src, resid=resid if len(seq) == 1 else None, tail_first=m)
+        return h if len(seq) == 1 else _cna(host, name + ".1", seq[1], [ConvSource(h)], resid=resid)
+    i, h = 0, x
+    if len(seq) == 4:                                               # 1x1 expansion
+        h, i = _cna(host, name + ".0", seq[0], src, tail_first=m), 1
+    elif meta_k is not None:
+        raise NotImplementedError("meta injection into an MBConv without expansion does not occur in the V2 configurations")
+    dw, se, proj = seq[i], seq[i + 1], seq[i + 2]
+    w9, b9 = folded_depthwise(host, f"{name}.{i}", dw)
+    h, psum = ops.dwconv3x3_se(h, w9, b9, dw[0].stride[0])
+    c, s = se.fc1.in_channels, se.fc1.out_channels
+    gate = ops.se_gate_psum(psum, h.shape[2] * h.shape[3], se.fc1.weight.detach().reshape(s, c), se.fc1.bias.detach(),
+                            se.fc2.weight.detach().reshape(c, s), se.fc2.bias.detach())
+    return _cna(host, f"{name}.{i + 2}", proj, [ConvSource(h, gate)], resid=resid)      # the SE multiplies the projection's input

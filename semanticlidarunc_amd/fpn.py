@@ -5,7 +5,7 @@ Contract kept: constructor keywords (plus the stale `resnet_type=` alias that sr
 `forward(x[B,cin,H,W], meta[B,m,H,W]) -> [B,num_classes,H,W]` (ELU + 1 > 0), and the `state_dict` layout including the
 aliased `stem.0.* / layerN.*` duplicates of `backbone.*` and the never-used `backbone.bn1.* / backbone.fc.*`
 (semanticFCN.py:146-153).  torchvision is not needed: the backbone container below re-creates the public
-resnet18/34 BasicBlock architecture (names, shapes), shufflenet.py the ShuffleNetV2 one, squeezenet.py SqueezeNet 1.0, regnet.py RegNetY; `pretrained` weights are not downloaded -- load a checkpoint.
+resnet18/34 BasicBlock architecture (names, shapes), shufflenet.py the ShuffleNetV2 one, squeezenet.py SqueezeNet 1.0, regnet.py RegNetY, effnet.py EfficientNetV2; `pretrained` weights are not downloaded -- load a checkpoint.
 
 How the layers map onto kernels (inference; BatchNorm folded into the preceding conv's weights and bias):
   conv3x3/s1 + BN + ReLU ........ one fused conv launch (ReLU = leaky slope 0)
@@ -40,6 +40,14 @@ the identity (or proj over slu_regnet_sample2's stride-2 sampling) added before 
 grouped conv is exact fp32 under "fp32" and "f16x3" alike; "f16" is refused.  regnet_y_400mf / regnet_y_800mf are built and tested up to the
 block forward but stay refused by name here.
 
+EfficientNetV2 encoders (efficientnet_v2_s / m / l, inference only; container and the block forward in effnet.py): stem = features[0] (conv + BN +
+SiLU at stride 1), layer1..3 = features[2..4], layer4 = features[6:] (built, in the state_dict, never applied), so x1 .. x3 sit at 1/2, 1/4, 1/8
+resolution, x4 = cat(x3[:, :-m], meta3) at 1/8 too, and the head's transposed convs are k4s4 / k4s4 / k2s2; the meta channels go into layer2 and
+layer3; multi_scale_meta=False is refused (the reference fails there).  A FusedMBConv is the fused conv twice (the 3x3 / stride-2 one over
+space_to_depth2(_cat)); an MBConv is the fused 1x1 expansion, slu_dwconv3x3_se_fwd (depthwise 3x3 / stride + BN + SiLU + the tile sums of the SE's
+mean), slu_se_gate_psum (mean -> fc1 -> SiLU -> fc2 -> sigmoid) and the fused 1x1 projection with the gate as its per-(sample, channel) input
+multiplier and the identity added: 4 launches.  The depthwise conv is exact fp32 under "fp32" and "f16x3" alike; "f16" is refused.
+
 Conv precision "f16" (resnet18 / resnet34, inference): the same layers on the half-precision storage path (h8.py) -- activations stay
 [N, G, H, W, 8] fp16 from the stem's input to the last conv's output (`_forward_h8`).  What differs from the list above: the space-to-depth
 kernel reads the meta channels from the full-resolution tensor itself (no down-sampled copies) and also writes phase (0,0) as a tensor of its
@@ -53,6 +61,7 @@ from typing import Dict, List, Optional
 import torch
 import torch.nn as nn
 
+from . import effnet as _eff
 from . import h8 as _h8
 from . import ops
 from . import regnet as _rgn
@@ -156,11 +165,12 @@ class SemanticNetworkWithFPN(nn.Module):
         self.is_shuffle = backbone in _shf.BASE_CHANNELS
         self.is_squeeze = backbone in _sqz.BASE_CHANNELS
         self.is_regnet = backbone in _rgn.ENABLED
-        if backbone not in _RESNETS and not self.is_shuffle and not self.is_squeeze and not self.is_regnet:
-            if backbone in ("regnet_y_400mf", "regnet_y_800mf", "regnet_y_1_6gf", "regnet_y_3_2gf", "efficientnet_v2_s", "efficientnet_v2_m",
-                            "efficientnet_v2_l"):
+        self.is_effnet = backbone in _eff.BASE_CHANNELS
+        if backbone not in _RESNETS and not self.is_shuffle and not self.is_squeeze and not self.is_regnet and not self.is_effnet:
+            if backbone in ("regnet_y_400mf", "regnet_y_800mf", "regnet_y_1_6gf", "regnet_y_3_2gf"):
                 raise NotImplementedError(f"backbone '{backbone}' is not implemented on the HIP path yet (resnet18 / resnet34 / resnet50, "
-                                          "shufflenet_v2_x0_5 / x1_0 / x1_5 / x2_0 and squeezenet1_0 are, and so are regnet_y_1_6gf / regnet_y_3_2gf)")
+                                          "shufflenet_v2_x0_5 / x1_0 / x1_5 / x2_0 and squeezenet1_0 are, and so are regnet_y_1_6gf / regnet_y_3_2gf "
+                                          "and efficientnet_v2_s / m / l)")
             raise ValueError("Invalid ResNet type. Supported types: 'resnet18', 'resnet34', 'resnet50', 'regnet_y_400mf','regnet_y_800mf', "
                              "'regnet_y_1_6gf', 'regnet_y_3_2gf', 'shufflenet_v2_x0_5', 'shufflenet_v2_x1_0', 'shufflenet_v2_x1_5', "
                              "'shufflenet_v2_x2_0.")
@@ -174,14 +184,17 @@ class SemanticNetworkWithFPN(nn.Module):
             bc = self._build_squeezenet(backbone, input_channels, meta_channel_dim)
         elif self.is_regnet:
             bc = self._build_regnet(backbone, input_channels, meta_channel_dim)
+        elif self.is_effnet:
+            bc = self._build_effnet(backbone, input_channels, meta_channel_dim)
         else:
             bc = self._build_encoder(backbone, input_channels, meta_channel_dim)
         self.attention4, self.attention3 = AttentionModule(bc[1], bc[1]), AttentionModule(bc[2], bc[2])
         self.attention2, self.attention1 = AttentionModule(bc[3], bc[3]), AttentionModule(bc[4], bc[4])
         self.fpn_block4, self.fpn_block3 = self._fpn(bc[0], bc[1]), self._fpn(bc[1], bc[2])
         self.fpn_block2, self.fpn_block1 = self._fpn(bc[2], bc[3]), self._fpn(bc[3], bc[4])
-        # semanticFCN.py:217-233: x3 and x4 both sit at 1/8 resolution under a ShuffleNetV2 encoder, x2 and x3 both at 1/4 under SqueezeNet
-        s4 = 4 if self.is_shuffle or self.is_squeeze else 8
+        # semanticFCN.py:217-233: x3 and x4 both sit at 1/8 resolution under a ShuffleNetV2 or EfficientNetV2 encoder (:201 sets is_shuffle for
+        # both), x2 and x3 both at 1/4 under SqueezeNet
+        s4 = 4 if self.is_shuffle or self.is_squeeze or self.is_effnet else 8
         s3 = 2 if self.is_squeeze else 4
         self.upsample_layer_x4 = nn.ConvTranspose2d(bc[1], bc[1] // s4, s4, s4, 0)
         self.upsample_layer_x3 = nn.ConvTranspose2d(bc[2], bc[2] // s3, s3, s3, 0)
@@ -238,6 +251,17 @@ class SemanticNetworkWithFPN(nn.Module):
         t = self.backbone.trunk_output
         self.layer1, self.layer2, self.layer3, self.layer4 = t[0], t[1], t[2], t[3]
         return list(_rgn.BASE_CHANNELS[backbone])
+
+    def _build_effnet(self, backbone, input_channels, meta_channel_dim):
+        """The torchvision-shaped efficientnet_v2_{s,m,l} with the reference's surgery (semanticFCN.py:192-201): features[0][0] replaced by a 3x3 /
+        stride-1 conv over input + meta channels, `stem` = features[0], layer1..3 = features[2..4], layer4 = features[6:] (a slice, which keeps the
+        children's names: built, aliased in the state_dict as layer4.6.* / layer4.7.* as in the reference, never called by forward).  Returns the channel ladder."""
+        self.meta_channel_dim = meta_channel_dim
+        self.backbone = _eff.EfficientNetContainer(backbone)
+        f = self.backbone.features
+        f[0][0] = nn.Conv2d(input_channels + meta_channel_dim, f[0][0].out_channels, kernel_size=3, stride=1, padding=1, bias=False)
+        self.stem, self.layer1, self.layer2, self.layer3, self.layer4 = f[0], f[2], f[3], f[4], f[6:]
+        return list(_eff.BASE_CHANNELS[backbone])
 
     def _check_inputs(self, x, meta_channel):
         if not (isinstance(x, torch.Tensor) and isinstance(meta_channel, torch.Tensor)) or x.dim() != 4 or meta_channel.dim() != 4:
@@ -418,6 +442,32 @@ class SemanticNetworkWithFPN(nn.Module):
         if self._wants_autograd(x, meta) or self.training:
             raise NotImplementedError(f"{cls} with the {self.backbone_name} backbone is inference only on the HIP path: call model.eval() and run "
                                       "under torch.no_grad() (the grouped conv kernel of the Y block has no backward)")
+        if _sn.get_conv_precision() == "f16":
+            raise RuntimeError(f"{cls} with the {self.backbone_name} backbone does not run with conv precision 'f16': the half-precision "
+                               "storage path covers the BasicBlock backbones (resnet18 / resnet34) only; use set_conv_precision('fp32')")
+
+    # ---------------- EfficientNetV2 encoder (semanticFCN.py:124-135,192-201, :296-304; effnet.py) ----------------
+    def _encode_effnet(self, x, meta):
+        """(x1, x2, x3, x4) at 1/2, 1/4, 1/8, 1/8 resolution: stem (conv + BN + SiLU, stride 1), features[2..4] (effnet.block_forward), the meta
+        channels injected on the way into layer2 and layer3; x4 = cat(x3[:, :-m], meta3) -- layer4 is never applied (semanticFCN.py:296-304)."""
+        if not self.multi_scale_meta:
+            raise NotImplementedError("efficientnet backbones run with multi_scale_meta=True only (the reference's other branch feeds layer4 = "
+                                      "features[6:] a tensor of the wrong channel count)")
+        m1, m2, m3 = ops.nearest_down(meta, 2), ops.nearest_down(meta, 4), ops.nearest_down(meta, 8)
+        h = self._conv("stem", self.stem[0], self.stem[1], [ConvSource(x), ConvSource(meta)], act="silu")
+        outs = []
+        for lname, stage, mk in (("layer1", self.layer1, None), ("layer2", self.layer2, m1), ("layer3", self.layer3, m2)):
+            for bi, blk in enumerate(stage):
+                h = _eff.block_forward(self, f"{lname}.{bi}", blk, h, mk if bi == 0 else None)
+            outs.append(h)
+        return outs[0], outs[1], outs[2], ops.replace_tail(outs[2], m3)
+
+    def _effnet_guard(self, x, meta, cls: str):
+        """What an EfficientNetV2 encoder does not run in this class: training / gradients (the fused depthwise kernel and the gate have no
+        backward here) and the half-precision storage path."""
+        if self._wants_autograd(x, meta) or self.training:
+            raise NotImplementedError(f"{cls} with the {self.backbone_name} backbone is inference only on the HIP path: call model.eval() and run "
+                                      "under torch.no_grad() (the fused depthwise + SE kernels of the MBConv block have no backward)")
         if _sn.get_conv_precision() == "f16":
             raise RuntimeError(f"{cls} with the {self.backbone_name} backbone does not run with conv precision 'f16': the half-precision "
                                "storage path covers the BasicBlock backbones (resnet18 / resnet34) only; use set_conv_precision('fp32')")
@@ -775,6 +825,8 @@ class SemanticNetworkWithFPN(nn.Module):
             self._squeezenet_guard(x, meta, "models/semanticFCN")
         if self.is_regnet:
             self._regnet_guard(x, meta, "models/semanticFCN")
+        if self.is_effnet:
+            self._effnet_guard(x, meta, "models/semanticFCN")
         if self._wants_autograd(x, meta):
             return self._forward_train(x, meta)
         if self.backbone_name == "resnet50" and _sn.get_conv_precision() == "f16x3":
@@ -791,6 +843,8 @@ class SemanticNetworkWithFPN(nn.Module):
             x1, x2, x3, x4 = self._encode_squeezenet(x, meta)
         elif self.is_regnet:
             x1, x2, x3, x4 = self._encode_regnet(x, meta)
+        elif self.is_effnet:
+            x1, x2, x3, x4 = self._encode_effnet(x, meta)
         else:
             x1, x2, x3, x4 = self._encode(x, meta)
         f4 = self._conv("fpn4", self.fpn_block4[0], self.fpn_block4[1], [ConvSource(x4)])

@@ -1816,6 +1816,63 @@ def se_scale(x: torch.Tensor, w1: torch.Tensor, b1: Optional[torch.Tensor], w2: 
     return scale
 
 
+def dwconv3x3_se(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, stride: int = 1):
+    """The depthwise conv of an MBConv in one launch (slu_dwconv3x3_se_fwd, csrc/mbconv_unit.hip): y = SiLU(depthwise conv3x3 / pad 1 / stride (x)
+    + bias) with w [C, 9] (eval BatchNorm folded in by the caller).  Returns (y [N, C, Ho, Wo], psum [N, C, T]): psum holds the per-tile sums of y,
+    which se_gate_psum turns into the SqueezeExcitation's mean without reading y back.  y equals dwconv3x3(x, w, bias, stride, "silu") bit for
+    bit; exact fp32 under every conv precision; bit-identical run to run."""
+    _req(x, "x")
+    if x.dim() != 4:
+        raise RuntimeError(f"x: expected NCHW, got {tuple(x.shape)}")
+    n, c, h, wd = x.shape
+    _req(w, "w")
+    _req(bias, "bias")
+    if tuple(w.shape) != (c, 9) or tuple(bias.shape) != (c,):
+        raise RuntimeError(f"dwconv3x3_se: weight {tuple(w.shape)} / bias {tuple(bias.shape)} do not match {c} channels")
+    if stride not in (1, 2):
+        raise RuntimeError("dwconv3x3_se: stride must be 1 or 2")
+    lib = _lib.load()
+    t = lib.slu_dwconv3x3_se_tiles(h, wd, int(stride))
+    if t <= 0:
+        raise RuntimeError(f"dwconv3x3_se: a {h} x {wd} map is outside what slu_dwconv3x3_se_fwd takes")
+    y = torch.empty((n, c, (h + stride - 1) // stride, (wd + stride - 1) // stride), dtype=torch.float32, device=x.device)
+    psum = torch.empty((n, c, t), dtype=torch.float32, device=x.device)
+    check(lib.slu_dwconv3x3_se_fwd(x.data_ptr(), w.data_ptr(), bias.data_ptr(), y.data_ptr(), psum.data_ptr(), n, c, h, wd, int(stride), _stream()),
+          "slu_dwconv3x3_se_fwd")
+    return y, psum
+
+
+SE_GATE_MAX_C, SE_GATE_MAX_S = 1536, 96
+
+
+def se_gate_psum(psum: torch.Tensor, count: int, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor) -> torch.Tensor:
+    """SqueezeExcitation's multiplier [N, C] = sigmoid(fc2(SiLU(fc1(mean)))) with mean = psum.sum(-1) / count (summed in tile order on the device);
+    psum [N, C, T] from dwconv3x3_se with count = Ho Wo, or a plain mean as [N, C, 1] (or [N, C]) with count = 1.  w1 [S, C], b1 [S], w2 [C, S],
+    b2 [C]; C <= 1536 and S <= 96, the range of se_scale."""
+    _req(psum, "psum")
+    if psum.dim() == 2:
+        psum = psum.unsqueeze(2)
+    if psum.dim() != 3 or psum.numel() == 0:
+        raise RuntimeError(f"psum: expected [N, C, T], got {tuple(psum.shape)}")
+    n, c, t = psum.shape
+    if int(count) < 1:
+        raise RuntimeError("se_gate_psum: count must be positive")
+    _req(w1, "w1")
+    if w1.dim() != 2 or w1.shape[1] != c or w1.shape[0] == 0:
+        raise RuntimeError(f"w1: expected [S, {c}], got {tuple(w1.shape)}")
+    s = w1.shape[0]
+    for tns, nme, shp in ((b1, "b1", (s,)), (w2, "w2", (c, s)), (b2, "b2", (c,))):
+        _req(tns, nme)
+        if tuple(tns.shape) != shp:
+            raise RuntimeError(f"{nme}: expected {shp}, got {tuple(tns.shape)}")
+    if c > SE_GATE_MAX_C or s > SE_GATE_MAX_S:
+        raise RuntimeError(f"se_gate_psum: C = {c}, S = {s} is outside the kernel's C <= {SE_GATE_MAX_C}, S <= {SE_GATE_MAX_S}")
+    scale = torch.empty((n, c), dtype=torch.float32, device=psum.device)
+    check(_lib.load().slu_se_gate_psum(psum.data_ptr(), t, 1.0 / float(count), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
+                                       scale.data_ptr(), n, c, s, _stream()), "slu_se_gate_psum")
+    return scale
+
+
 # ------------------------------------------------------------------------------------------------
 # ShuffleNetV2 unit tail (csrc/shuffle_unit.hip)
 # ------------------------------------------------------------------------------------------------
