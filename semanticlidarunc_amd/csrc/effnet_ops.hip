@@ -4,7 +4,7 @@
 // conv kernel; what is new here is HBM-bound:
 //   dwconv3x3_kernel      depthwise 3x3 (stride 1 / 2) + folded BatchNorm + SiLU: one lane per output pixel, lanes azimuth-adjacent
 //   global_avgpool_kernel SqueezeExcitation's AdaptiveAvgPool2d(1): one wave per (sample, channel) plane
-//   se_gate_kernel        fc1 -> SiLU -> fc2 -> sigmoid on the pooled vector: one workgroup per sample (<= 1536 channels x <= 96 squeezed)
+//   (the gate on the pooled vector, fc1 -> SiLU -> fc2 -> sigmoid, is slu_se_gate in se_gate.hip)
 //   dwconv3x3_wgrad_kernel  training: dL/dw[c][tap] = sum over (sample, pixel) of dy * shifted x -- one workgroup per channel, nine fp64 block sums
 //                           (the data gradient of the stride-1 depthwise conv is the forward kernel with the taps reversed)
 #include "pixel_common.h"
@@ -43,29 +43,6 @@ __global__ __launch_bounds__(256) void global_avgpool_kernel(const float* __rest
   for (int i = threadIdx.x & 63; i < HW; i += 64) s += (double)p[i];
   s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) out[plane] = (float)(s / (double)HW);
-}
-
-__global__ __launch_bounds__(256) void se_gate_kernel(const float* __restrict__ avg, const float* __restrict__ w1, const float* __restrict__ b1,
-                                                      const float* __restrict__ w2, const float* __restrict__ b2, float* __restrict__ scale, int C, int S) {
-  extern __shared__ float s_mem[];      // [C] pooled vector | [S] squeezed activations
-  float* s_avg = s_mem;
-  float* s_hid = s_mem + C;
-  const int n = blockIdx.x;
-  for (int c = threadIdx.x; c < C; c += blockDim.x) s_avg[c] = avg[(size_t)n * C + c];
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  for (int s = wave; s < S; s += nw) {      // one wave per squeezed unit: a dot product over C
-    float acc = 0.0f;
-    for (int c = lane; c < C; c += 64) acc = fmaf(w1[(size_t)s * C + c], s_avg[c], acc);
-    acc = wave_sum(acc);
-    if (lane == 0) s_hid[s] = silu(acc + (b1 ? b1[s] : 0.0f));
-  }
-  __syncthreads();
-  for (int c = threadIdx.x; c < C; c += blockDim.x) {
-    float acc = b2 ? b2[c] : 0.0f;
-    for (int s = 0; s < S; ++s) acc = fmaf(w2[(size_t)c * S + s], s_hid[s], acc);
-    scale[(size_t)n * C + c] = sigmoid(acc);
-  }
 }
 
 __global__ __launch_bounds__(256) void dwconv3x3_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ dw, int N,
@@ -133,12 +110,5 @@ extern "C" int slu_global_avgpool(const float* x, float* out, int N, int C, int 
   if (!x || !out || N <= 0 || C <= 0 || HW <= 0) return SLU_EINVAL;
   const long long planes = (long long)N * C;
   hipLaunchKernelGGL(global_avgpool_kernel, dim3((unsigned)((planes + 3) / 4)), dim3(256), 0, slu_stream(stream), x, out, (int)planes, HW);
-  SLU_CHECK_LAUNCH();
-}
-
-extern "C" int slu_se_gate(const float* avg, const float* w1, const float* b1, const float* w2, const float* b2, float* scale, int N, int C, int S,
-                           slu_stream_t stream) {
-  if (!avg || !w1 || !w2 || !scale || N <= 0 || C <= 0 || S <= 0 || (size_t)(C + S) * 4 > 64 * 1024) return SLU_EINVAL;
-  hipLaunchKernelGGL(se_gate_kernel, dim3((unsigned)N), dim3(256), (size_t)(C + S) * 4, slu_stream(stream), avg, w1, b1, w2, b2, scale, C, S);
   SLU_CHECK_LAUNCH();
 }

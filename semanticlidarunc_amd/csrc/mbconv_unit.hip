@@ -1,6 +1,7 @@
 // The middle of an EfficientNetV2 MBConv block (torchvision's MBConv: 1x1 expansion, depthwise 3x3, SqueezeExcitation with SiLU, 1x1 projection) in
 // two launches; the 1x1 convs around it are the fused conv kernel.  The composed route (effnet_ops.hip: dwconv3x3_kernel, global_avgpool_kernel,
-// se_gate_kernel) reads the expanded map -- the largest tensor of the block -- a second time only to average it.
+// then slu_se_gate) reads the expanded map -- the largest tensor of the block -- a second time only to average it.  The second launch, the gate
+// over the tile sums, is slu_se_gate_psum in se_gate.hip.
 //
 //   dwconv3x3_se_kernel<S, VEC>   y[n, c, oy, ox] = silu(bias[c] + sum_{a, b} w[c, 3 a + b] x[n, c, S oy - 1 + a, S ox - 1 + b])   (pad 1, S = 1 / 2)
 //                                 psum[n, c, t]   = sum of y[n, c] over the rows of output tile t
@@ -14,11 +15,6 @@
 //     fmaf chain of dwconv3x3_kernel in the same (a, b) order (a padding tap adds w * 0), the same silu().
 //     The sum: every lane adds what it stores in a fixed order, wave_sum, one LDS slot per wave, the four slots added in wave order by one
 //     lane, one float per tile -- no atomics and no order between workgroups, so y and psum are bit-identical run to run.
-//   se_gate_psum_kernel           mean[n, c] = inv_count * sum_t psum[n, c, t] (tile order); scale[n, c] = sigmoid(b2[c] + sum_s w2[c, s] *
-//                                 silu(b1[s] + sum_c' w1[s, c'] mean[n, c'])).  One workgroup per (image, slice of blockDim output channels); fc1
-//                                 is one wave per hidden unit with up to 16 waves per workgroup (min(16, max(4, S)) -- the 4 waves of
-//                                 regnet_se_gate_kernel made fc1 the serial part of wide blocks: 24 dot products of 1536 in a row per wave at
-//                                 S = 96; here 6), every workgroup of an image computing the whole hidden vector.
 #include "pixel_common.h"
 
 namespace {
@@ -135,37 +131,6 @@ __global__ __launch_bounds__(256) void dwconv3x3_se_kernel(const float* __restri
   if (tid == 0) psum[plane * T + t] = BLOCK_TOTAL4(s_red);
 }
 
-constexpr int SEG_MAX_C = 1536, SEG_MAX_S = 96;      // the range of slu_se_gate's users: EfficientNetV2-L's widest MBConv
-
-__global__ __launch_bounds__(1024) void se_gate_psum_kernel(const float* __restrict__ psum, int T, float inv_count, const float* __restrict__ w1,
-                                                            const float* __restrict__ b1, const float* __restrict__ w2, const float* __restrict__ b2,
-                                                            float* __restrict__ scale, int C, int S) {
-  __shared__ float s_avg[SEG_MAX_C];
-  __shared__ float s_hid[SEG_MAX_S];
-  const int n = blockIdx.x;
-  for (int c = threadIdx.x; c < C; c += blockDim.x) {
-    const float* p = psum + ((size_t)n * C + c) * T;
-    float s = 0.0f;
-    for (int t = 0; t < T; ++t) s += p[t];      // tile order
-    s_avg[c] = s * inv_count;
-  }
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  for (int s = wave; s < S; s += nw) {      // one wave per hidden unit: a dot product over C
-    float acc = 0.0f;
-    for (int c = lane; c < C; c += 64) acc = fmaf(w1[(size_t)s * C + c], s_avg[c], acc);
-    acc = wave_sum(acc);
-    if (lane == 0) s_hid[s] = silu(acc + b1[s]);
-  }
-  __syncthreads();
-  const int c = blockIdx.y * blockDim.x + threadIdx.x;
-  if (c < C) {
-    float acc = b2[c];
-    for (int s = 0; s < S; ++s) acc = fmaf(w2[(size_t)c * S + s], s_hid[s], acc);
-    scale[(size_t)n * C + c] = sigmoid(acc);
-  }
-}
-
 template <int S>
 int launch_dwse(const float* x, const float* w, const float* bias, float* y, float* psum, int N, int C, int H, int W, int OH, int OW, int rows, int T,
                 hipStream_t st) {
@@ -200,15 +165,4 @@ extern "C" int slu_dwconv3x3_se_fwd(const float* x, const float* w, const float*
   hipStream_t st = slu_stream(stream);
   return stride == 1 ? launch_dwse<1>(x, w, bias, y, psum, N, C, H, W, OH, OW, rows, T, st)
                      : launch_dwse<2>(x, w, bias, y, psum, N, C, H, W, OH, OW, rows, T, st);
-}
-
-extern "C" int slu_se_gate_psum(const float* psum, int T, float inv_count, const float* w1, const float* b1, const float* w2, const float* b2,
-                                float* scale, int N, int C, int S, slu_stream_t stream) {
-  if (!psum || !w1 || !b1 || !w2 || !b2 || !scale || T <= 0 || N <= 0 || C <= 0 || S <= 0) return SLU_EINVAL;
-  if (C > SEG_MAX_C || S > SEG_MAX_S || N > 65535) return SLU_EINVAL;
-  const int waves = S < 4 ? 4 : (S > 16 ? 16 : S);
-  const int threads = 64 * waves;
-  hipLaunchKernelGGL(se_gate_psum_kernel, dim3((unsigned)N, (unsigned)((C + threads - 1) / threads)), dim3(threads), 0, slu_stream(stream), psum, T,
-                     inv_count, w1, b1, w2, b2, scale, C, S);
-  SLU_CHECK_LAUNCH();
 }

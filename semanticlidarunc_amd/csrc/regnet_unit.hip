@@ -12,10 +12,7 @@
 //     v_pk_fma_f32 (two output channels each) as scalar operands.  So a lane does 9 LDS reads per 9 GW FMAs.  Exact fp32 (an fmaf chain per
 //     output, in (c, tap) order).
 //     The mean: wave_sum per output channel, one LDS slot per wave, the four slots added in wave order, one float per (image, channel, tile) --
-//     no atomics, so two runs give the same bits; regnet_se_gate_kernel adds the tiles in tile order.
-//   regnet_se_gate_kernel                gate[n, c] = sigmoid(b2[c] + sum_s w2[c, s] relu(b1[s] + sum_c' w1[s, c'] mean[n, c'])),
-//                                        mean[n, c] = inv_count * sum_t psum[n, c, t].  One workgroup per (image, slice of the output channels);
-//                                        every workgroup of an image computes the whole hidden vector (the fc1 weights come from L2).
+//     no atomics, so two runs give the same bits; the gate (slu_regnet_se_gate, se_gate.hip) adds the tiles in tile order.
 //   regnet_sample2_kernel                y = cat(src0[:, coff0 : coff0 + c0], src1)[:, :, ::2, ::2]: the input of a stride-2 block's 1x1 / stride-2
 //                                        projection, with the meta injection, in one pass that reads a quarter of the input.
 #include "pixel_common.h"
@@ -89,38 +86,6 @@ __global__ __launch_bounds__(256) void regnet_gconv_kernel(const float* __restri
   if (tid < GW) psum[((size_t)n * C + (size_t)g * GW + tid) * T + blockIdx.x] = (s_red[0][tid] + s_red[1][tid]) + (s_red[2][tid] + s_red[3][tid]);
 }
 
-__global__ __launch_bounds__(256) void regnet_se_gate_kernel(const float* __restrict__ psum, int T, float inv_count, const float* __restrict__ w1,
-                                                             const float* __restrict__ b1, const float* __restrict__ w2, const float* __restrict__ b2,
-                                                             float* __restrict__ gate, float* __restrict__ mean, int C, int S, int cper) {
-  extern __shared__ float s_mem[];      // [C] means | [S] hidden activations
-  float* s_avg = s_mem;
-  float* s_hid = s_mem + C;
-  const int n = blockIdx.x;
-  for (int c = threadIdx.x; c < C; c += blockDim.x) {
-    const float* p = psum + ((size_t)n * C + c) * T;
-    float s = 0.0f;
-    for (int t = 0; t < T; ++t) s += p[t];      // tile order
-    s *= inv_count;
-    s_avg[c] = s;
-    if (mean && blockIdx.y == 0) mean[(size_t)n * C + c] = s;
-  }
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  for (int s = wave; s < S; s += nw) {      // one wave per hidden unit: a dot product over C
-    float acc = 0.0f;
-    for (int c = lane; c < C; c += 64) acc = fmaf(w1[(size_t)s * C + c], s_avg[c], acc);
-    acc = wave_sum(acc) + b1[s];
-    if (lane == 0) s_hid[s] = acc > 0.0f ? acc : 0.0f;
-  }
-  __syncthreads();
-  const int c = blockIdx.y * cper + threadIdx.x;
-  if (threadIdx.x < cper && c < C) {
-    float acc = b2[c];
-    for (int s = 0; s < S; ++s) acc = fmaf(w2[(size_t)c * S + s], s_hid[s], acc);
-    gate[(size_t)n * C + c] = sigmoid(acc);
-  }
-}
-
 __global__ __launch_bounds__(256) void regnet_sample2_kernel(const float* __restrict__ s0, const float* __restrict__ s1, long long bs0, long long bs1,
                                                              int c0, int C, int N, int H, int W, int OH, int OW, float* __restrict__ y) {
   const size_t total = (size_t)N * C * OH * OW;
@@ -184,16 +149,6 @@ extern "C" int slu_regnet_gconv_fwd(const float* x, int ct, int coff, const floa
   if (gw == 8) return launch_gconv_s<8>(stride, xs, wg, bias, y, psum, bsx, N, C, H, W, OH, OW, st);
   if (gw == 16) return launch_gconv_s<16>(stride, xs, wg, bias, y, psum, bsx, N, C, H, W, OH, OW, st);
   return launch_gconv_s<24>(stride, xs, wg, bias, y, psum, bsx, N, C, H, W, OH, OW, st);
-}
-
-extern "C" int slu_regnet_se_gate(const float* psum, int T, float inv_count, const float* w1, const float* b1, const float* w2, const float* b2,
-                                  float* gate, float* mean, int N, int C, int S, slu_stream_t stream) {
-  if (!psum || !w1 || !b1 || !w2 || !b2 || !gate || T <= 0 || N <= 0 || C <= 0 || S <= 0) return SLU_EINVAL;
-  if ((size_t)(C + S) * 4 > 64 * 1024 || N > 65535) return SLU_EUNSUPPORTED;
-  const int slices = (C + 255) / 256;
-  hipLaunchKernelGGL(regnet_se_gate_kernel, dim3((unsigned)N, (unsigned)slices), dim3(256), (size_t)(C + S) * 4, slu_stream(stream), psum, T, inv_count,
-                     w1, b1, w2, b2, gate, mean, C, S, 256);
-  SLU_CHECK_LAUNCH();
 }
 
 extern "C" int slu_regnet_sample2(const float* src0, int ct0, int coff0, int c0, const float* src1, int ct1, int c1, float* y, int N, int H, int W,

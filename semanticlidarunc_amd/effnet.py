@@ -1,23 +1,24 @@
-"""EfficientNetV2 backbone container for the FPN segmenters, and the forward of one block on the HIP kernels for `models.semanticFCN`
-(`block_forward`, fpn.py `_encode_effnet`; reference models/semanticFCN.py:124-135,192-201,296-304 wires the backbone exactly as `semanticFCN_opt`
+"""EfficientNetV2 backbone container for the FPN segmenters, and the inference forward of one block and of the encoder on the HIP kernels for both
+of them (`block_forward`, `encode`; reference models/semanticFCN.py:124-135,192-201,296-304 wires the backbone exactly as `semanticFCN_opt`
 does).  The container was written for the `semanticFCN_opt` segmenter (reference baselines/Reichert/semanticFCN_opt.py:170-180 builds
 torchvision's `efficientnet_v2_{s,m,l}`, :238-247 replaces `features[0][0]` by a 3x3 / stride-1 conv over input + meta channels and wires
 `stem = features[0]`, `layer1..3 = features[2..4]`, `layer4 = features[6:]`; its forward (:396-404) never calls layer4 nor features[1] / [5]).
 
 torchvision is not needed: the classes below re-create the public architecture of torchvision 0.19's `efficientnet.py` -- module names,
 parameter shapes and therefore `state_dict` keys -- without a module forward (the arithmetic lives in `block_forward` below and, for
-`semanticFCN_opt`, in fpn_opt.py, on the HIP kernels); `pretrained`
+`semanticFCN_opt`'s training path, in fpn_opt.py, on the HIP kernels); `pretrained`
 weights are not downloaded, load a checkpoint.  **Parity of the block internals is unpinned** (no reference-held fixture): the
 oracle (oracle/effnet.py) restates the same public definition, and the reference's OWN head / meta-injection wiring is pinned through it."""
 from __future__ import annotations
 
+import functools
 import math
 from typing import List, Tuple
 
 import torch.nn as nn
 
 from . import ops
-from . import salsanext as _sn
+from .encoder_family import EncoderFamily, run_stages
 from .ops import ConvSource
 
 # (block kind, expand ratio, kernel, stride, input channels, output channels, layers) -- torchvision's _efficientnet_conf for the V2 family
@@ -137,6 +138,18 @@ def stage_channels(name: str) -> Tuple[int, int, int, int]:
 
 
 # ----------------------------------------------------------------------------------------------------------------
+def build(host, backbone, input_channels, meta_channel_dim):
+    """The torchvision-shaped efficientnet_v2_{s,m,l} with the reference's surgery (semanticFCN.py:192-201): features[0][0] replaced by a 3x3 /
+    stride-1 conv over input + meta channels, `stem` = features[0], layer1..3 = features[2..4], layer4 = features[6:] (a slice, which keeps the
+    children's names: built, aliased in the state_dict as layer4.6.* / layer4.7.* as in the reference, never called by forward).  Returns the channel ladder."""
+    host.meta_channel_dim = meta_channel_dim
+    host.backbone = EfficientNetContainer(backbone)
+    f = host.backbone.features
+    f[0][0] = nn.Conv2d(input_channels + meta_channel_dim, f[0][0].out_channels, kernel_size=3, stride=1, padding=1, bias=False)
+    host.stem, host.layer1, host.layer2, host.layer3, host.layer4 = f[0], f[2], f[3], f[4], f[6:]
+    return list(BASE_CHANNELS[backbone])
+
+
 def _cna(host, name, cna, srcs, resid=None, tail_first=0):
     """Conv2dNormActivation with a dense stride-1 conv: conv -> folded BatchNorm -> SiLU (or none) [+ resid] as one fused conv launch."""
     return host._conv(name, cna[0], cna[1], srcs, act="silu" if len(cna) > 2 else "none", resid=resid, tail_first=tail_first)
@@ -146,19 +159,19 @@ def folded_depthwise(host, name, cna):
     """(w [C, 9], bias [C]) of a depthwise Conv2dNormActivation with the eval BatchNorm folded in, cached on `host` per parameter version (exact
     fp32 under every conv precision, so the precision is not part of the key's meaning -- it is kept in it as in the packed-conv cache)."""
     conv, bn = cna[0], cna[1]
-    cache = host.__dict__.setdefault("_dw_cache", {})
-    key = tuple((t.data_ptr(), t._version) for t in (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var)) + (_sn.get_conv_precision(),)
-    hit = cache.get(name)
-    if hit is None or hit[0] != key:
+
+    def make():
         w, b = host._fold(conv.weight, None, bn)
-        hit = cache[name] = (key, w.detach().float().reshape(w.shape[0], 9).contiguous(), b.detach().float().contiguous())
-    return hit[1], hit[2]
+        return w.detach().float().reshape(w.shape[0], 9).contiguous(), b.detach().float().contiguous()
+    return host._cached("_dw_cache", name, (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var), make)
 
 
-def block_forward(host, name: str, blk, x, meta_k=None):
+def block_forward(host, name: str, blk, x, meta_k=None, fused_se: bool = True):
     """One FusedMBConv / MBConv block, eval mode (StochasticDepth = identity), on the HIP kernels.  `host` is the FPN model: its `_conv` /
     `_conv_s2` run the fused convs with their folded BatchNorm from its packed-weight cache.  meta_k: the meta channels, at the block's input
-    resolution, that replace the last m channels of x on the way in (first block of layer2 / layer3).
+    resolution, that replace the last m channels of x on the way in (first block of layer2 / layer3).  fused_se=False: the composed MBConv
+    middle -- slu_dwconv3x3_fwd, then slu_global_avgpool + slu_se_gate (ops.se_scale), three launches, the mean rounded from an fp64 sum --
+    which is what `semanticFCN_opt` launches.
 
       FusedMBConv   3x3 expansion (+ BN + SiLU): the fused conv; at stride 2 the 2x2 conv over space_to_depth2(_cat) of the input; then the 1x1
                     projection (+ BN) with the identity added where the block has one
@@ -187,8 +200,32 @@ def block_forward(host, name: str, blk, x, meta_k=None):
         raise NotImplementedError("meta injection into an MBConv without expansion does not occur in the V2 configurations")
     dw, se, proj = seq[i], seq[i + 1], seq[i + 2]
     w9, b9 = folded_depthwise(host, f"{name}.{i}", dw)
-    h, psum = ops.dwconv3x3_se(h, w9, b9, dw[0].stride[0])
     c, s = se.fc1.in_channels, se.fc1.out_channels
-    gate = ops.se_gate_psum(psum, h.shape[2] * h.shape[3], se.fc1.weight.detach().reshape(s, c), se.fc1.bias.detach(),
-                            se.fc2.weight.detach().reshape(c, s), se.fc2.bias.detach())
+    fc = (se.fc1.weight.detach().reshape(s, c), se.fc1.bias.detach(), se.fc2.weight.detach().reshape(c, s), se.fc2.bias.detach())
+    if fused_se:
+        h, psum = ops.dwconv3x3_se(h, w9, b9, dw[0].stride[0])
+        gate = ops.se_gate_psum(psum, h.shape[2] * h.shape[3], *fc)
+    else:
+        h = ops.dwconv3x3(h, w9, b9, dw[0].stride[0], "silu")
+        gate = ops.se_scale(h, *fc)
     return _cna(host, f"{name}.{i + 2}", proj, [ConvSource(h, gate)], resid=resid)      # the SE multiplies the projection's input
+
+
+def encode(host, x, meta):
+    """(x1, x2, x3, x4) at 1/2, 1/4, 1/8, 1/8 resolution: stem (conv + BN + SiLU, stride 1), features[2..4], the meta channels injected on the
+    way into layer2 and layer3; x4 = cat(x3[:, :-m], meta3) -- layer4 is never applied (semanticFCN.py:296-304).  The MBConv middle is the
+    host class's `mbconv_fused_se`."""
+    if not host.multi_scale_meta:
+        raise NotImplementedError("efficientnet backbones run with multi_scale_meta=True only (the reference's other branch feeds layer4 = "
+                                  "features[6:] a tensor of the wrong channel count)")
+    m1, m2, m3 = ops.nearest_down(meta, 2), ops.nearest_down(meta, 4), ops.nearest_down(meta, 8)
+    h = host._conv("stem", host.stem[0], host.stem[1], [ConvSource(x), ConvSource(meta)], act="silu")
+    block = functools.partial(block_forward, fused_se=host.mbconv_fused_se)
+    x1, x2, x3 = run_stages(host, block, h, (("layer1", host.layer1, None), ("layer2", host.layer2, m1), ("layer3", host.layer3, m2)))
+    return x1, x2, x3, ops.replace_tail(x3, m3)
+
+
+# `models.semanticFCN` has no backward for the fused depthwise + gate kernels; `semanticFCN_opt` trains through its own autograd nodes
+FAMILY = EncoderFamily(backbones=tuple(BASE_CHANNELS), build=build, encode=encode, head_scales=(4, 4, 2),
+                       inference_clause="the fused depthwise + SE kernels of the MBConv block have no backward", training_refuses=True,
+                       trains_in_opt=True, mc_shared_prefix=True)

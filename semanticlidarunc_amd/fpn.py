@@ -18,20 +18,20 @@ How the layers map onto kernels (inference; BatchNorm folded into the preceding 
   ConvTranspose2d k = s ......... 1x1 conv to Cout*s*s channels + depth-to-space
   ConvTranspose2d k4 s2 p1 ...... 3x3 conv to 4*classes sub-pixel channels + depth-to-space fused with ELU + 1
 
-ShuffleNetV2 encoders (shufflenet_v2_x0_5 / x1_0 / x1_5 / x2_0, inference only; container in shufflenet.py): stem = conv1 (conv + BN + ReLU at
+ShuffleNetV2 encoders (shufflenet_v2_x0_5 / x1_0 / x1_5 / x2_0, inference only; container, unit forward and encoder in shufflenet.py): stem = conv1 (conv + BN + ReLU at
 stride 1, no maxpool), layer1..3 = stage2..4, layer4 = conv5, so x1 .. x4 sit at 1/2, 1/4, 1/8, 1/8 resolution and the head's transposed convs are
 k4s4 / k4s4 / k2s2.  A unit (InvertedResidual) is the fused conv for branch2's first 1x1 -- reading x[:, C/2:] through `ConvSource.coff` -- plus
 slu_shuffle_tail_fwd for depthwise 3x3 -> BN -> 1x1 -> BN -> ReLU -> concat -> channel shuffle (and the pass-through copy): 2 launches per
 stride-1 unit, 3 per stride-2 unit.  The tail's pointwise product is the exact-fp32 MFMA under "fp32" and "f16x3" alike; "f16" is refused.
 
-SqueezeNet 1.0 encoder (squeezenet1_0, inference only; container in squeezenet.py): stem = features[0:4] (conv + ReLU at stride 1, ceil-mode
+SqueezeNet 1.0 encoder (squeezenet1_0, inference only; container, Fire forward and encoder in squeezenet.py): stem = features[0:4] (conv + ReLU at stride 1, ceil-mode
 MaxPool, Fire), layer1 = features[4:6], layer2 = features[6:8] (MaxPool, Fire), layer3 = features[8:10], layer4 = features[10:] (Fire, MaxPool,
 Fire), so x1 .. x4 have 256 / 256 / 384 / 512 channels at 1/2, 1/4, 1/4, 1/8 resolution and the head's transposed convs are k4s4 / k2s2 / k2s2.  The
 meta channels are injected into layer2 (ahead of its pool) and layer3 only.  The stem conv is the fused conv; a Fire is ONE slu_fire_fwd launch
 (squeeze -> ReLU -> {1x1, 3x3} -> ReLU -> concat, the squeeze map in LDS), the pool slu_maxpool3s2_ceil_fwd; both read cat(x[:, :-m], meta_k) in
 place.  The Fire's products are the exact-fp32 MFMA under "fp32" and "f16x3" alike; "f16" is refused.
 
-RegNetY encoders (regnet_y_1_6gf / regnet_y_3_2gf, inference only; container and the block forward in regnet.py): stem = stem (conv + BN + ReLU at
+RegNetY encoders (regnet_y_1_6gf / regnet_y_3_2gf, inference only; container, block forward and encoder in regnet.py): stem = stem (conv + BN + ReLU at
 stride 1), layer1..4 = trunk_output[0..3], so x1 .. x4 sit at 1/2, 1/4, 1/8, 1/16 resolution with the four stage widths and the head is the
 default one (k8s8 / k4s4 / k2s2); the meta channels go into layer2, layer3 and layer4.  A Y block is the fused conv for f.a (reading
 (meta_k, x[:, :-m]) in place), slu_regnet_gconv_fwd for f.b (grouped 3x3 / stride + BN + ReLU + the tile sums of the SE's mean),
@@ -40,7 +40,7 @@ the identity (or proj over slu_regnet_sample2's stride-2 sampling) added before 
 grouped conv is exact fp32 under "fp32" and "f16x3" alike; "f16" is refused.  regnet_y_400mf / regnet_y_800mf are built and tested up to the
 block forward but stay refused by name here.
 
-EfficientNetV2 encoders (efficientnet_v2_s / m / l, inference only; container and the block forward in effnet.py): stem = features[0] (conv + BN +
+EfficientNetV2 encoders (efficientnet_v2_s / m / l, inference only; container, block forward and encoder in effnet.py): stem = features[0] (conv + BN +
 SiLU at stride 1), layer1..3 = features[2..4], layer4 = features[6:] (built, in the state_dict, never applied), so x1 .. x3 sit at 1/2, 1/4, 1/8
 resolution, x4 = cat(x3[:, :-m], meta3) at 1/8 too, and the head's transposed convs are k4s4 / k4s4 / k2s2; the meta channels go into layer2 and
 layer3; multi_scale_meta=False is refused (the reference fails there).  A FusedMBConv is the fused conv twice (the 3x3 / stride-2 one over
@@ -68,6 +68,7 @@ from . import regnet as _rgn
 from . import salsanext as _sn
 from . import shufflenet as _shf
 from . import squeezenet as _sqz
+from .encoder_family import EncoderFamily
 from .ops import ConvSource
 
 
@@ -162,11 +163,8 @@ class SemanticNetworkWithFPN(nn.Module):
         super().__init__()
         if resnet_type is not None:          # stale keyword of src/inference_ouster.py:35
             backbone = resnet_type
-        self.is_shuffle = backbone in _shf.BASE_CHANNELS
-        self.is_squeeze = backbone in _sqz.BASE_CHANNELS
-        self.is_regnet = backbone in _rgn.ENABLED
-        self.is_effnet = backbone in _eff.BASE_CHANNELS
-        if backbone not in _RESNETS and not self.is_shuffle and not self.is_squeeze and not self.is_regnet and not self.is_effnet:
+        fam = family_of(backbone)
+        if fam is None:
             if backbone in ("regnet_y_400mf", "regnet_y_800mf", "regnet_y_1_6gf", "regnet_y_3_2gf"):
                 raise NotImplementedError(f"backbone '{backbone}' is not implemented on the HIP path yet (resnet18 / resnet34 / resnet50, "
                                           "shufflenet_v2_x0_5 / x1_0 / x1_5 / x2_0 and squeezenet1_0 are, and so are regnet_y_1_6gf / regnet_y_3_2gf "
@@ -178,24 +176,14 @@ class SemanticNetworkWithFPN(nn.Module):
             raise NotImplementedError("only interpolation_mode='nearest' (the reference default) runs on the HIP path")
         self.backbone_name, self.interpolation_mode = backbone, interpolation_mode
         self.num_classes, self.attention, self.multi_scale_meta = num_classes, attention, multi_scale_meta
-        if self.is_shuffle:
-            bc = self._build_shufflenet(backbone, input_channels, meta_channel_dim)
-        elif self.is_squeeze:
-            bc = self._build_squeezenet(backbone, input_channels, meta_channel_dim)
-        elif self.is_regnet:
-            bc = self._build_regnet(backbone, input_channels, meta_channel_dim)
-        elif self.is_effnet:
-            bc = self._build_effnet(backbone, input_channels, meta_channel_dim)
-        else:
-            bc = self._build_encoder(backbone, input_channels, meta_channel_dim)
+        bc = fam.build(self, backbone, input_channels, meta_channel_dim)
         self.attention4, self.attention3 = AttentionModule(bc[1], bc[1]), AttentionModule(bc[2], bc[2])
         self.attention2, self.attention1 = AttentionModule(bc[3], bc[3]), AttentionModule(bc[4], bc[4])
         self.fpn_block4, self.fpn_block3 = self._fpn(bc[0], bc[1]), self._fpn(bc[1], bc[2])
         self.fpn_block2, self.fpn_block1 = self._fpn(bc[2], bc[3]), self._fpn(bc[3], bc[4])
         # semanticFCN.py:217-233: x3 and x4 both sit at 1/8 resolution under a ShuffleNetV2 or EfficientNetV2 encoder (:201 sets is_shuffle for
-        # both), x2 and x3 both at 1/4 under SqueezeNet
-        s4 = 4 if self.is_shuffle or self.is_squeeze or self.is_effnet else 8
-        s3 = 2 if self.is_squeeze else 4
+        # both), x2 and x3 both at 1/4 under SqueezeNet; x2's scale is 2 in every family
+        s4, s3, _ = fam.head_scales
         self.upsample_layer_x4 = nn.ConvTranspose2d(bc[1], bc[1] // s4, s4, s4, 0)
         self.upsample_layer_x3 = nn.ConvTranspose2d(bc[2], bc[2] // s3, s3, s3, 0)
         self.upsample_layer_x2 = nn.ConvTranspose2d(bc[3], bc[3] // 2, 2, 2, 0)
@@ -204,6 +192,14 @@ class SemanticNetworkWithFPN(nn.Module):
             nn.Conv2d(up + bc[4], bc[4], 3, 1, 1), nn.BatchNorm2d(bc[4]), nn.ReLU(inplace=True),
             nn.Conv2d(bc[4], bc[4], 3, 1, 1), nn.BatchNorm2d(bc[4]), nn.ReLU(inplace=True),
             nn.ConvTranspose2d(bc[4], num_classes, 4, 2, 1), nn.ELU(inplace=True))
+
+    # the encoder family of this model's backbone; the is_* flags are read by callers, nothing in the package branches on them
+    family = property(lambda self: family_of(self.backbone_name))
+    is_shuffle = property(lambda self: self.family is _shf.FAMILY)
+    is_squeeze = property(lambda self: self.family is _sqz.FAMILY)
+    is_regnet = property(lambda self: self.family is _rgn.FAMILY)
+    is_effnet = property(lambda self: self.family is _eff.FAMILY)
+    mbconv_fused_se = True      # the MBConv middle effnet.encode runs: slu_dwconv3x3_se_fwd + slu_se_gate_psum
 
     def _build_encoder(self, backbone, input_channels, meta_channel_dim):
         """The torchvision-shaped ResNet with the reference's surgery (semanticFCN.py:146-153): conv1 replaced by a 3x3 / stride-1 conv
@@ -217,51 +213,6 @@ class SemanticNetworkWithFPN(nn.Module):
         self.layer3, self.layer4 = self.backbone.layer3, self.backbone.layer4
         top = 512 * block.expansion                      # semanticFCN.py:85-96: 512 (resnet18 / 34), 2048 (resnet50)
         return [top, top // 2, top // 4, top // 8, top // 16]
-
-    def _build_shufflenet(self, backbone, input_channels, meta_channel_dim):
-        """The torchvision-shaped ShuffleNetV2 with the reference's surgery (semanticFCN.py:181-190): conv1[0] replaced by a 3x3 / stride-1 conv
-        over input + meta channels, `stem` = conv1 (no maxpool), layer1..3 = stage2..4, layer4 = conv5.  Returns the channel ladder."""
-        self.meta_channel_dim = meta_channel_dim
-        self.backbone = _shf.ShuffleNetV2Container(backbone)
-        self.backbone.conv1[0] = nn.Conv2d(input_channels + meta_channel_dim, self.backbone.conv1[0].out_channels, kernel_size=3, stride=1, padding=1,
-                                           bias=False)
-        self.stem = self.backbone.conv1
-        self.layer1, self.layer2, self.layer3, self.layer4 = self.backbone.stage2, self.backbone.stage3, self.backbone.stage4, self.backbone.conv5
-        return list(_shf.BASE_CHANNELS[backbone])
-
-    def _build_squeezenet(self, backbone, input_channels, meta_channel_dim):
-        """The torchvision-shaped SqueezeNet 1.0 with the reference's surgery (semanticFCN.py:155-169): features[0] replaced by a 3x3 / stride-1
-        conv over 2 + meta channels (the reference hard-codes the 2), `stem` = features[0:4], layer1..4 = features[4:6] / [6:8] / [8:10] / [10:].
-        Returns the channel ladder."""
-        self.meta_channel_dim = meta_channel_dim
-        self.backbone = _sqz.SqueezeNetContainer(backbone)
-        f = self.backbone.features
-        f[0] = nn.Conv2d(2 + meta_channel_dim, 96, kernel_size=3, stride=1, padding=1, bias=False)
-        self.stem, self.layer1, self.layer2, self.layer3, self.layer4 = f[0:4], f[4:6], f[6:8], f[8:10], f[10:]
-        return list(_sqz.BASE_CHANNELS[backbone])
-
-    def _build_regnet(self, backbone, input_channels, meta_channel_dim):
-        """The torchvision-shaped RegNetY with the reference's surgery (semanticFCN.py:171-179): stem[0] replaced by a 3x3 / stride-1 conv over
-        input + meta channels, `stem` = stem (conv + BN + ReLU), layer1..4 = trunk_output[0..3].  Returns the channel ladder."""
-        self.meta_channel_dim = meta_channel_dim
-        self.backbone = _rgn.RegNetYContainer(backbone)
-        self.backbone.stem[0] = nn.Conv2d(input_channels + meta_channel_dim, self.backbone.stem[0].out_channels, kernel_size=3, stride=1, padding=1,
-                                          bias=False)
-        self.stem = self.backbone.stem
-        t = self.backbone.trunk_output
-        self.layer1, self.layer2, self.layer3, self.layer4 = t[0], t[1], t[2], t[3]
-        return list(_rgn.BASE_CHANNELS[backbone])
-
-    def _build_effnet(self, backbone, input_channels, meta_channel_dim):
-        """The torchvision-shaped efficientnet_v2_{s,m,l} with the reference's surgery (semanticFCN.py:192-201): features[0][0] replaced by a 3x3 /
-        stride-1 conv over input + meta channels, `stem` = features[0], layer1..3 = features[2..4], layer4 = features[6:] (a slice, which keeps the
-        children's names: built, aliased in the state_dict as layer4.6.* / layer4.7.* as in the reference, never called by forward).  Returns the channel ladder."""
-        self.meta_channel_dim = meta_channel_dim
-        self.backbone = _eff.EfficientNetContainer(backbone)
-        f = self.backbone.features
-        f[0][0] = nn.Conv2d(input_channels + meta_channel_dim, f[0][0].out_channels, kernel_size=3, stride=1, padding=1, bias=False)
-        self.stem, self.layer1, self.layer2, self.layer3, self.layer4 = f[0], f[2], f[3], f[4], f[6:]
-        return list(_eff.BASE_CHANNELS[backbone])
 
     def _check_inputs(self, x, meta_channel):
         if not (isinstance(x, torch.Tensor) and isinstance(meta_channel, torch.Tensor)) or x.dim() != 4 or meta_channel.dim() != 4:
@@ -292,182 +243,13 @@ class SemanticNetworkWithFPN(nn.Module):
         x4 = self._stage("layer4", self.layer4, x3, m3)
         return x1, x2, x3, x4
 
-    # ---------------- ShuffleNetV2 encoder (semanticFCN.py:181-190, :306-314; shufflenet.py) ----------------
-    def _shf_tail(self, name, dw: nn.Conv2d, dw_bn, pw: nn.Conv2d, pw_bn):
-        """(wdw [C, 9], bdw [C], wpack, bpw [Co]) of a unit's depthwise 3x3 -> BN -> 1x1 -> BN -> ReLU tail with both BatchNorms folded in, cached per
-        parameter version and conv precision like `_prep` (the pointwise product is the exact-fp32 MFMA under 'fp32' and 'f16x3' alike)."""
-        cache = self.__dict__.setdefault("_shf_cache", {})
-        k = _key(dw.weight, dw_bn.weight, dw_bn.bias, dw_bn.running_mean, dw_bn.running_var,
-                 pw.weight, pw_bn.weight, pw_bn.bias, pw_bn.running_mean, pw_bn.running_var)
-        hit = cache.get(name)
-        if hit is None or hit[0] != k:
-            w9, b9 = self._fold(dw.weight, None, dw_bn)
-            w1, b1 = self._fold(pw.weight, None, pw_bn)
-            co, c = w1.shape[0], w1.shape[1]
-            hit = cache[name] = (k, w9.detach().float().reshape(c, 9).contiguous(), b9.detach().float().contiguous(),
-                                 ops.pack_shuffle_tail_weight(w1.detach().float().reshape(co, c).contiguous()), b1.detach().float().contiguous())
-        return hit[1:]
-
-    def _shf_unit(self, n: str, blk, x, meta_k):
-        """One InvertedResidual: the fused conv for branch2's first 1x1 (+ BN + ReLU), slu_shuffle_tail_fwd for the rest -- two launches for a
-        stride-1 unit, three for a stride-2 one.  meta_k: the meta channels that replace the last m input channels (first unit of a stage)."""
-        b2 = blk.branch2
-        cx = x.shape[1]
-        bf = b2[5].out_channels
-        if blk.stride == 1:
-            if meta_k is not None:
-                raise NotImplementedError("meta injection into a stride-1 ShuffleNetV2 unit does not occur (every stage opens with a stride-2 unit)")
-            h = self._conv(n + ".branch2.0", b2[0], b2[1], [ConvSource(x, None, False, 0, bf, cx - bf)])                  # x[:, C/2:]
-            return ops.shuffle_tail(h, *self._shf_tail(n + ".branch2.3", b2[3], b2[4], b2[5], b2[6]), bf, 1, passthrough=x)
-        m = 0 if meta_k is None else meta_k.shape[1]
-        b1 = blk.branch1
-        out = torch.empty((x.shape[0], 2 * bf, (x.shape[2] + 1) // 2, (x.shape[3] + 1) // 2), dtype=torch.float32, device=x.device)
-        ops.shuffle_tail(x, *self._shf_tail(n + ".branch1.0", b1[0], b1[1], b1[2], b1[3]), bf, 2, out=out, parity=0, cuse=cx - m, src2=meta_k)
-        src = [ConvSource(x)] if meta_k is None else [ConvSource(meta_k), ConvSource(x, None, False, 0, cx - m)]             # (meta, x[:, :-m])
-        h = self._conv(n + ".branch2.0", b2[0], b2[1], src, tail_first=m)
-        return ops.shuffle_tail(h, *self._shf_tail(n + ".branch2.3", b2[3], b2[4], b2[5], b2[6]), bf, 2, out=out, parity=1)
-
-    def _encode_shufflenet(self, x, meta):
-        """(x1, x2, x3, x4) at 1/2, 1/4, 1/8, 1/8 resolution: stem (conv + BN + ReLU, stride 1), stage2..4, conv5, with the multi-scale meta
-        injection on the way into stage3 / stage4 / conv5 (semanticFCN.py:306-314)."""
-        m1 = m2 = m3 = None
-        if self.multi_scale_meta:
-            m1, m2, m3 = ops.nearest_down(meta, 2), ops.nearest_down(meta, 4), ops.nearest_down(meta, 8)
-        h = self._conv("stem", self.stem[0], self.stem[1], [ConvSource(x), ConvSource(meta)])
-        outs = []
-        for lname, stage, mk in (("layer1", self.layer1, None), ("layer2", self.layer2, m1), ("layer3", self.layer3, m2)):
-            for bi, blk in enumerate(stage):
-                h = self._shf_unit(f"{lname}.{bi}", blk, h, mk if bi == 0 else None)
-            outs.append(h)
-        x3 = outs[2]
-        m = 0 if m3 is None else m3.shape[1]
-        src = [ConvSource(x3)] if m3 is None else [ConvSource(m3), ConvSource(x3, None, False, 0, x3.shape[1] - m)]
-        x4 = self._conv("layer4", self.layer4[0], self.layer4[1], src, tail_first=m)
-        return outs[0], outs[1], x3, x4
-
-    def _shufflenet_guard(self, x, meta, cls: str):
-        """What a ShuffleNetV2 encoder does not run: training / gradients (no stride-2 depthwise backward) and the half-precision storage path."""
-        if self._wants_autograd(x, meta):
-            raise NotImplementedError(f"{cls} with the {self.backbone_name} backbone is inference only on the HIP path: call model.eval() and run "
-                                      "under torch.no_grad() (the ShuffleNetV2 units have no backward kernels)")
-        if _sn.get_conv_precision() == "f16":
-            raise RuntimeError(f"{cls} with the {self.backbone_name} backbone does not run with conv precision 'f16': the half-precision "
-                               "storage path covers the BasicBlock backbones (resnet18 / resnet34) only; use set_conv_precision('fp32')")
-
-    # ---------------- SqueezeNet 1.0 encoder (semanticFCN.py:155-169, :287-295; squeezenet.py) ----------------
-    def _fire_params(self, name, fire):
-        """(wpack, bsq, b1, b3) of a Fire module, cached per parameter version like `_shf_tail` (every product is the exact-fp32 MFMA under
-        'fp32' and 'f16x3' alike)."""
-        cache = self.__dict__.setdefault("_fire_cache", {})
-        sq, e1, e3 = fire.squeeze, fire.expand1x1, fire.expand3x3
-        k = _key(sq.weight, sq.bias, e1.weight, e1.bias, e3.weight, e3.bias)
-        hit = cache.get(name)
-        if hit is None or hit[0] != k:
-            def f(t):
-                return t.detach().float().contiguous()
-            wpack = ops.pack_fire_weight(f(sq.weight).reshape(sq.out_channels, sq.in_channels), f(e1.weight).reshape(e1.out_channels, e1.in_channels),
-                                         f(e3.weight))
-            hit = cache[name] = (k, wpack, f(sq.bias), f(e1.bias), f(e3.bias))
-        return hit[1:]
-
-    def _sqz_modules(self, lname, modules, x, meta_k):
-        """A run of `features`: Fire = one slu_fire_fwd, MaxPool = slu_maxpool3s2_ceil_fwd.  meta_k: the meta channels that replace the last m
-        channels of x on the way into the first module (read in place as a second source)."""
-        for i, mod in enumerate(modules):
-            kw = {}
-            if i == 0 and meta_k is not None:
-                kw = dict(cuse=x.shape[1] - meta_k.shape[1], src2=meta_k)
-            if isinstance(mod, _sqz.Fire):
-                x = ops.fire(x, *self._fire_params(f"{lname}.{i}", mod), **kw)
-            elif isinstance(mod, nn.MaxPool2d):
-                x = ops.maxpool3s2_ceil(x, **kw)
-            else:
-                raise NotImplementedError(f"{type(mod).__name__} inside a SqueezeNet stage is not on the HIP path")
-        return x
-
-    def _encode_squeezenet(self, x, meta):
-        """(x1, x2, x3, x4) with 256 / 256 / 384 / 512 channels at 1/2, 1/4, 1/4, 1/8 resolution; the meta channels go into layer2 (ahead of its
-        pool) and layer3 only, meta3 is unused (semanticFCN.py:287-295)."""
-        m1 = m2 = None
-        if self.multi_scale_meta:
-            m1, m2 = ops.nearest_down(meta, 2), ops.nearest_down(meta, 4)
-        h = self._conv("stem", self.stem[0], None, [ConvSource(x), ConvSource(meta)])
-        xs = self._sqz_modules("stem", list(self.stem)[2:], h, None)
-        x1 = self._sqz_modules("layer1", self.layer1, xs, None)
-        x2 = self._sqz_modules("layer2", self.layer2, x1, m1)
-        x3 = self._sqz_modules("layer3", self.layer3, x2, m2)
-        x4 = self._sqz_modules("layer4", self.layer4, x3, None)
-        return x1, x2, x3, x4
-
-    def _squeezenet_guard(self, x, meta, cls: str):
-        """What the SqueezeNet encoder does not run: training / gradients (the Fire kernel and the ceil pool have no backward) and the
+    def _inference_guard(self, x, meta, cls: str):
+        """What an inference-only encoder family does not run: training / gradients (the family's kernels have no backward) and the
         half-precision storage path."""
-        if self._wants_autograd(x, meta) or self.training:
+        fam = self.family
+        if self._wants_autograd(x, meta) or (fam.training_refuses and self.training):
             raise NotImplementedError(f"{cls} with the {self.backbone_name} backbone is inference only on the HIP path: call model.eval() and run "
-                                      "under torch.no_grad() (the Fire module kernel has no backward)")
-        if _sn.get_conv_precision() == "f16":
-            raise RuntimeError(f"{cls} with the {self.backbone_name} backbone does not run with conv precision 'f16': the half-precision "
-                               "storage path covers the BasicBlock backbones (resnet18 / resnet34) only; use set_conv_precision('fp32')")
-
-    # ---------------- RegNetY encoder (semanticFCN.py:171-179, :305-314; regnet.py) ----------------
-    def _regnet_fb(self, name, conv: nn.Conv2d, bn):
-        """(wg, bias) of a Y block's grouped 3x3 conv with its BatchNorm folded in, in the order slu_regnet_gconv_fwd reads, cached per parameter
-        version like `_shf_tail` (the products are exact fp32 under 'fp32' and 'f16x3' alike)."""
-        cache = self.__dict__.setdefault("_regnet_cache", {})
-        k = _key(conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var)
-        hit = cache.get(name)
-        if hit is None or hit[0] != k:
-            w, b = self._fold(conv.weight, None, bn)
-            hit = cache[name] = (k, ops.pack_regnet_gconv_weight(w.detach().float().contiguous(), conv.in_channels // conv.groups),
-                                 b.detach().float().contiguous())
-        return hit[1:]
-
-    def _encode_regnet(self, x, meta):
-        """(x1, x2, x3, x4) at 1/2, 1/4, 1/8, 1/16 resolution: stem (conv + BN + ReLU, stride 1), the four stages of Y blocks
-        (regnet.y_block_forward), with the multi-scale meta injection on the way into layer2 / layer3 / layer4 (semanticFCN.py:305-314)."""
-        m1 = m2 = m3 = None
-        if self.multi_scale_meta:
-            m1, m2, m3 = ops.nearest_down(meta, 2), ops.nearest_down(meta, 4), ops.nearest_down(meta, 8)
-        h = self._conv("stem", self.stem[0], self.stem[1], [ConvSource(x), ConvSource(meta)])
-        outs = []
-        for lname, stage, mk in (("layer1", self.layer1, None), ("layer2", self.layer2, m1), ("layer3", self.layer3, m2), ("layer4", self.layer4, m3)):
-            for bi, blk in enumerate(stage):
-                h = _rgn.y_block_forward(self, f"{lname}.{bi}", blk, h, mk if bi == 0 else None)
-            outs.append(h)
-        return tuple(outs)
-
-    def _regnet_guard(self, x, meta, cls: str):
-        """What a RegNetY encoder does not run: training / gradients (the grouped conv and the gate have no backward) and the half-precision
-        storage path."""
-        if self._wants_autograd(x, meta) or self.training:
-            raise NotImplementedError(f"{cls} with the {self.backbone_name} backbone is inference only on the HIP path: call model.eval() and run "
-                                      "under torch.no_grad() (the grouped conv kernel of the Y block has no backward)")
-        if _sn.get_conv_precision() == "f16":
-            raise RuntimeError(f"{cls} with the {self.backbone_name} backbone does not run with conv precision 'f16': the half-precision "
-                               "storage path covers the BasicBlock backbones (resnet18 / resnet34) only; use set_conv_precision('fp32')")
-
-    # ---------------- EfficientNetV2 encoder (semanticFCN.py:124-135,192-201, :296-304; effnet.py) ----------------
-    def _encode_effnet(self, x, meta):
-        """(x1, x2, x3, x4) at 1/2, 1/4, 1/8, 1/8 resolution: stem (conv + BN + SiLU, stride 1), features[2..4] (effnet.block_forward), the meta
-        channels injected on the way into layer2 and layer3; x4 = cat(x3[:, :-m], meta3) -- layer4 is never applied (semanticFCN.py:296-304)."""
-        if not self.multi_scale_meta:
-            raise NotImplementedError("efficientnet backbones run with multi_scale_meta=True only (the reference's other branch feeds layer4 = "
-                                      "features[6:] a tensor of the wrong channel count)")
-        m1, m2, m3 = ops.nearest_down(meta, 2), ops.nearest_down(meta, 4), ops.nearest_down(meta, 8)
-        h = self._conv("stem", self.stem[0], self.stem[1], [ConvSource(x), ConvSource(meta)], act="silu")
-        outs = []
-        for lname, stage, mk in (("layer1", self.layer1, None), ("layer2", self.layer2, m1), ("layer3", self.layer3, m2)):
-            for bi, blk in enumerate(stage):
-                h = _eff.block_forward(self, f"{lname}.{bi}", blk, h, mk if bi == 0 else None)
-            outs.append(h)
-        return outs[0], outs[1], outs[2], ops.replace_tail(outs[2], m3)
-
-    def _effnet_guard(self, x, meta, cls: str):
-        """What an EfficientNetV2 encoder does not run in this class: training / gradients (the fused depthwise kernel and the gate have no
-        backward here) and the half-precision storage path."""
-        if self._wants_autograd(x, meta) or self.training:
-            raise NotImplementedError(f"{cls} with the {self.backbone_name} backbone is inference only on the HIP path: call model.eval() and run "
-                                      "under torch.no_grad() (the fused depthwise + SE kernels of the MBConv block have no backward)")
+                                      f"under torch.no_grad() ({fam.inference_clause})")
         if _sn.get_conv_precision() == "f16":
             raise RuntimeError(f"{cls} with the {self.backbone_name} backbone does not run with conv precision 'f16': the half-precision "
                                "storage path covers the BasicBlock backbones (resnet18 / resnet34) only; use set_conv_precision('fp32')")
@@ -477,6 +259,17 @@ class SemanticNetworkWithFPN(nn.Module):
         return nn.Sequential(nn.Conv2d(cin, cout, 3, 1, 1), nn.BatchNorm2d(cout), nn.ReLU(inplace=True))
 
     # ---------------- weight preparation (cached per parameter version and conv precision) ----------------
+    def _cached(self, cache_attr: str, name: str, deps, make):
+        """The tuple `make()` returns, kept in the dict `self.<cache_attr>` under `name` and rebuilt when a tensor of `deps` was replaced or
+        written to, or the conv precision changed: the folded / packed parameters of the family kernels (shufflenet.py, squeezenet.py,
+        regnet.py, effnet.py)."""
+        cache = self.__dict__.setdefault(cache_attr, {})
+        k = _key(*deps)
+        hit = cache.get(name)
+        if hit is None or hit[0] != k:
+            hit = cache[name] = (k,) + tuple(make())
+        return hit[1:]
+
     def _prep(self, name: str, maker, *deps) -> _Packed:
         cache: Dict[str, _Packed] = self.__dict__.setdefault("_packed", {})
         p = cache.get(name)
@@ -819,14 +612,9 @@ class SemanticNetworkWithFPN(nn.Module):
 
     def forward(self, x, meta_channel):
         x, meta = self._check_inputs(x, meta_channel)
-        if self.is_shuffle:
-            self._shufflenet_guard(x, meta, "models/semanticFCN")
-        if self.is_squeeze:
-            self._squeezenet_guard(x, meta, "models/semanticFCN")
-        if self.is_regnet:
-            self._regnet_guard(x, meta, "models/semanticFCN")
-        if self.is_effnet:
-            self._effnet_guard(x, meta, "models/semanticFCN")
+        fam = self.family
+        if fam.inference_clause is not None:
+            self._inference_guard(x, meta, "models/semanticFCN")
         if self._wants_autograd(x, meta):
             return self._forward_train(x, meta)
         if self.backbone_name == "resnet50" and _sn.get_conv_precision() == "f16x3":
@@ -837,16 +625,7 @@ class SemanticNetworkWithFPN(nn.Module):
                 raise RuntimeError("models/semanticFCN with the resnet50 backbone does not run with conv precision 'f16': the half-precision "
                                    "storage path covers the BasicBlock backbones (resnet18 / resnet34) only; use set_conv_precision('fp32')")
             return self._forward_h8(x, meta)
-        if self.is_shuffle:
-            x1, x2, x3, x4 = self._encode_shufflenet(x, meta)
-        elif self.is_squeeze:
-            x1, x2, x3, x4 = self._encode_squeezenet(x, meta)
-        elif self.is_regnet:
-            x1, x2, x3, x4 = self._encode_regnet(x, meta)
-        elif self.is_effnet:
-            x1, x2, x3, x4 = self._encode_effnet(x, meta)
-        else:
-            x1, x2, x3, x4 = self._encode(x, meta)
+        x1, x2, x3, x4 = fam.encode(self, x, meta)
         f4 = self._conv("fpn4", self.fpn_block4[0], self.fpn_block4[1], [ConvSource(x4)])
         f3 = self._conv("fpn3", self.fpn_block3[0], self.fpn_block3[1], [ConvSource(x3)])
         f2 = self._conv("fpn2", self.fpn_block2[0], self.fpn_block2[1], [ConvSource(x2)])
@@ -864,3 +643,18 @@ class SemanticNetworkWithFPN(nn.Module):
         y = self._conv("dec0", d[0], d[1], [ConvSource(f1), ConvSource(ups)])
         y = self._conv("dec1", d[3], d[4], [ConvSource(y)])
         return self._convT_k4s2p1("dec_out", d[6], y, elu_plus_one=True)
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# the encoder families (encoder_family.py): the ResNets here, the others next to their containers
+RESNET_FAMILY = EncoderFamily(backbones=tuple(_RESNETS), build=SemanticNetworkWithFPN._build_encoder, encode=SemanticNetworkWithFPN._encode,
+                              head_scales=(8, 4, 2), inference_clause=None, training_refuses=False, trains_in_opt=True, mc_shared_prefix=True)
+FAMILIES = (RESNET_FAMILY, _shf.FAMILY, _sqz.FAMILY, _rgn.FAMILY, _eff.FAMILY)
+
+
+def family_of(backbone) -> Optional[EncoderFamily]:
+    """The family whose `backbones` holds the name (None: no family does, the constructors refuse it)."""
+    for fam in FAMILIES:
+        if backbone in fam.backbones:
+            return fam
+    return None

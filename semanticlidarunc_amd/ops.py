@@ -1845,10 +1845,9 @@ def dwconv3x3_se(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, stride: i
 SE_GATE_MAX_C, SE_GATE_MAX_S = 1536, 96
 
 
-def se_gate_psum(psum: torch.Tensor, count: int, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor) -> torch.Tensor:
-    """SqueezeExcitation's multiplier [N, C] = sigmoid(fc2(SiLU(fc1(mean)))) with mean = psum.sum(-1) / count (summed in tile order on the device);
-    psum [N, C, T] from dwconv3x3_se with count = Ho Wo, or a plain mean as [N, C, 1] (or [N, C]) with count = 1.  w1 [S, C], b1 [S], w2 [C, S],
-    b2 [C]; C <= 1536 and S <= 96, the range of se_scale."""
+def _se_gate_from_psum(fn: str, entry: str, psum, count, w1, b1, w2, b2, limit, mean_arg: bool, want_mean: bool = False):
+    """se_gate_psum / regnet_se_gate: validation, allocation and the call of `entry` (csrc/se_gate.hip).  limit(c, s): the entry point's range as
+    an error text or None; mean_arg: the entry point takes the nullable mean output after the gate."""
     _req(psum, "psum")
     if psum.dim() == 2:
         psum = psum.unsqueeze(2)
@@ -1856,7 +1855,7 @@ def se_gate_psum(psum: torch.Tensor, count: int, w1: torch.Tensor, b1: torch.Ten
         raise RuntimeError(f"psum: expected [N, C, T], got {tuple(psum.shape)}")
     n, c, t = psum.shape
     if int(count) < 1:
-        raise RuntimeError("se_gate_psum: count must be positive")
+        raise RuntimeError(f"{fn}: count must be positive")
     _req(w1, "w1")
     if w1.dim() != 2 or w1.shape[1] != c or w1.shape[0] == 0:
         raise RuntimeError(f"w1: expected [S, {c}], got {tuple(w1.shape)}")
@@ -1865,12 +1864,25 @@ def se_gate_psum(psum: torch.Tensor, count: int, w1: torch.Tensor, b1: torch.Ten
         _req(tns, nme)
         if tuple(tns.shape) != shp:
             raise RuntimeError(f"{nme}: expected {shp}, got {tuple(tns.shape)}")
-    if c > SE_GATE_MAX_C or s > SE_GATE_MAX_S:
-        raise RuntimeError(f"se_gate_psum: C = {c}, S = {s} is outside the kernel's C <= {SE_GATE_MAX_C}, S <= {SE_GATE_MAX_S}")
-    scale = torch.empty((n, c), dtype=torch.float32, device=psum.device)
-    check(_lib.load().slu_se_gate_psum(psum.data_ptr(), t, 1.0 / float(count), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
-                                       scale.data_ptr(), n, c, s, _stream()), "slu_se_gate_psum")
-    return scale
+    refusal = limit(c, s)
+    if refusal:
+        raise RuntimeError(f"{fn}: {refusal}")
+    gate = torch.empty((n, c), dtype=torch.float32, device=psum.device)
+    mean = torch.empty((n, c), dtype=torch.float32, device=psum.device) if want_mean else None
+    outs = (gate.data_ptr(), _ptr(mean)) if mean_arg else (gate.data_ptr(),)
+    check(getattr(_lib.load(), entry)(psum.data_ptr(), t, 1.0 / float(count), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), *outs,
+                                      n, c, s, _stream()), entry)
+    return (gate, mean) if want_mean else gate
+
+
+def se_gate_psum(psum: torch.Tensor, count: int, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor) -> torch.Tensor:
+    """SqueezeExcitation's multiplier [N, C] = sigmoid(fc2(SiLU(fc1(mean)))) with mean = psum.sum(-1) / count (summed in tile order on the device);
+    psum [N, C, T] from dwconv3x3_se with count = Ho Wo, or a plain mean as [N, C, 1] (or [N, C]) with count = 1.  w1 [S, C], b1 [S], w2 [C, S],
+    b2 [C]; C <= 1536 and S <= 96, the range of se_scale."""
+    def limit(c, s):
+        if c > SE_GATE_MAX_C or s > SE_GATE_MAX_S:
+            return f"C = {c}, S = {s} is outside the kernel's C <= {SE_GATE_MAX_C}, S <= {SE_GATE_MAX_S}"
+    return _se_gate_from_psum("se_gate_psum", "slu_se_gate_psum", psum, count, w1, b1, w2, b2, limit, False)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -2107,29 +2119,10 @@ def regnet_se_gate(psum: torch.Tensor, count: int, w1: torch.Tensor, b1: torch.T
     """RegNet's SqueezeExcitation multiplier [N, C] = sigmoid(fc2(relu(fc1(mean)))) with mean = psum.sum(-1) / count (summed in tile order on the
     device); psum [N, C, T] from regnet_gconv with count = Ho Wo, or a plain mean as [N, C, 1] (or [N, C]) with count = 1.  w1 [S, C], b1 [S],
     w2 [C, S], b2 [C].  want_mean: returns (gate, mean)."""
-    _req(psum, "psum")
-    if psum.dim() == 2:
-        psum = psum.unsqueeze(2)
-    if psum.dim() != 3 or psum.numel() == 0:
-        raise RuntimeError(f"psum: expected [N, C, T], got {tuple(psum.shape)}")
-    n, c, t = psum.shape
-    if int(count) < 1:
-        raise RuntimeError("regnet_se_gate: count must be positive")
-    _req(w1, "w1")
-    if w1.dim() != 2 or w1.shape[1] != c or w1.shape[0] == 0:
-        raise RuntimeError(f"w1: expected [S, {c}], got {tuple(w1.shape)}")
-    s = w1.shape[0]
-    for tns, nme, shp in ((b1, "b1", (s,)), (w2, "w2", (c, s)), (b2, "b2", (c,))):
-        _req(tns, nme)
-        if tuple(tns.shape) != shp:
-            raise RuntimeError(f"{nme}: expected {shp}, got {tuple(tns.shape)}")
-    if (c + s) * 4 > 64 * 1024:
-        raise RuntimeError(f"regnet_se_gate: C + S = {c + s} does not fit the kernel's 64 KiB of LDS")
-    gate = torch.empty((n, c), dtype=torch.float32, device=psum.device)
-    mean = torch.empty((n, c), dtype=torch.float32, device=psum.device) if want_mean else None
-    check(_lib.load().slu_regnet_se_gate(psum.data_ptr(), t, 1.0 / float(count), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
-                                         gate.data_ptr(), _ptr(mean), n, c, s, _stream()), "slu_regnet_se_gate")
-    return (gate, mean) if want_mean else gate
+    def limit(c, s):
+        if (c + s) * 4 > 64 * 1024:
+            return f"C + S = {c + s} does not fit the kernel's 64 KiB of LDS"
+    return _se_gate_from_psum("regnet_se_gate", "slu_regnet_se_gate", psum, count, w1, b1, w2, b2, limit, True, want_mean)
 
 
 def regnet_sample2(src: torch.Tensor, coff: int = 0, cuse: int = 0, src2: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -14,7 +14,7 @@ a checkpoint.
   avgpool, fc   never called by the segmenters
 Convs other than the SE's are bias-free, BatchNorm eps is 1e-5.
 
-`y_block_forward` is the one forward of a block; both FPN classes call it (fpn.py `_encode_regnet`)."""
+`y_block_forward` is the one forward of a block; both FPN classes reach it through `encode` below."""
 from __future__ import annotations
 
 import math
@@ -23,6 +23,7 @@ from collections import OrderedDict
 import torch.nn as nn
 
 from . import ops
+from .encoder_family import EncoderFamily, run_stages
 from .ops import ConvSource
 
 # (depth, w_0, w_a, w_m, group width) -- torchvision's regnet_y_* constructors; se_ratio 0.25, bottleneck multiplier 1
@@ -134,9 +135,31 @@ class RegNetYContainer(nn.Module):
 
 
 # ----------------------------------------------------------------------------------------------------------------
+def build(host, backbone, input_channels, meta_channel_dim):
+    """The torchvision-shaped RegNetY with the reference's surgery (semanticFCN.py:171-179): stem[0] replaced by a 3x3 / stride-1 conv over
+    input + meta channels, `stem` = stem (conv + BN + ReLU), layer1..4 = trunk_output[0..3].  Returns the channel ladder."""
+    host.meta_channel_dim = meta_channel_dim
+    host.backbone = RegNetYContainer(backbone)
+    host.backbone.stem[0] = nn.Conv2d(input_channels + meta_channel_dim, host.backbone.stem[0].out_channels, kernel_size=3, stride=1, padding=1,
+                                      bias=False)
+    host.stem = host.backbone.stem
+    t = host.backbone.trunk_output
+    host.layer1, host.layer2, host.layer3, host.layer4 = t[0], t[1], t[2], t[3]
+    return list(BASE_CHANNELS[backbone])
+
+
+def folded_gconv(host, name, conv: nn.Conv2d, bn):
+    """(wg, bias) of a Y block's grouped 3x3 conv with its BatchNorm folded in, in the order slu_regnet_gconv_fwd reads, cached on `host` per
+    parameter version and conv precision (the products are exact fp32 under 'fp32' and 'f16x3' alike)."""
+    def make():
+        w, b = host._fold(conv.weight, None, bn)
+        return ops.pack_regnet_gconv_weight(w.detach().float().contiguous(), conv.in_channels // conv.groups), b.detach().float().contiguous()
+    return host._cached("_regnet_cache", name, (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var), make)
+
+
 def y_block_forward(host, name: str, blk: YBlock, x, meta_k=None):
     """One Y block, eval mode, on the HIP kernels.  `host` is the FPN model: its `_conv` runs the fused 1x1 convs with their folded BatchNorm
-    from its packed-weight cache, its `_regnet_fb` holds the folded, re-ordered f.b weights.  meta_k: the meta channels, at the block's input
+    from its packed-weight cache, `folded_gconv` keeps the folded, re-ordered f.b weights on it.  meta_k: the meta channels, at the block's input
     resolution, that replace the last m channels of x on the way in (first block of layer2..4).
 
       f.a     fused 1x1 conv (+ BN + ReLU); with meta_k it reads (meta_k, x[:, :-m]) in place, the weight's input channels rotated
@@ -151,7 +174,7 @@ def y_block_forward(host, name: str, blk: YBlock, x, meta_k=None):
     src = [ConvSource(x)] if meta_k is None else [ConvSource(meta_k), ConvSource(x, None, False, 0, cx - m)]      # (meta, x[:, :-m])
     a = host._conv(name + ".f.a", f.a[0], f.a[1], src, tail_first=m)
     stride = f.b[0].stride[0]
-    wg, bg = host._regnet_fb(name + ".f.b", f.b[0], f.b[1])
+    wg, bg = folded_gconv(host, name + ".f.b", f.b[0], f.b[1])
     h, psum = ops.regnet_gconv(a, wg, bg, stride)
     se = f.se
     c, s = se.fc1.in_channels, se.fc1.out_channels
@@ -167,3 +190,20 @@ def y_block_forward(host, name: str, blk: YBlock, x, meta_k=None):
     else:
         idn = host._conv(name + ".proj", blk.proj[0], blk.proj[1], src, act="none", tail_first=m)
     return host._conv(name + ".f.c", f.c[0], f.c[1], [ConvSource(h, gate)], act="relu", resid=idn, late=True)
+
+
+def encode(host, x, meta):
+    """(x1, x2, x3, x4) at 1/2, 1/4, 1/8, 1/16 resolution: stem (conv + BN + ReLU, stride 1), the four stages of Y blocks, with the multi-scale
+    meta injection on the way into layer2 / layer3 / layer4 (semanticFCN.py:305-314)."""
+    m1 = m2 = m3 = None
+    if host.multi_scale_meta:
+        m1, m2, m3 = ops.nearest_down(meta, 2), ops.nearest_down(meta, 4), ops.nearest_down(meta, 8)
+    h = host._conv("stem", host.stem[0], host.stem[1], [ConvSource(x), ConvSource(meta)])
+    return tuple(run_stages(host, y_block_forward, h, (("layer1", host.layer1, None), ("layer2", host.layer2, m1), ("layer3", host.layer3, m2),
+                                                       ("layer4", host.layer4, m3))))
+
+
+# the grouped conv and the gate have no backward, so no training; the default head
+FAMILY = EncoderFamily(backbones=ENABLED, build=build, encode=encode, head_scales=(8, 4, 2),
+                       inference_clause="the grouped conv kernel of the Y block has no backward", training_refuses=True, trains_in_opt=False,
+                       mc_shared_prefix=False)

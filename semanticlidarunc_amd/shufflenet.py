@@ -3,8 +3,8 @@ baselines/Reichert/semanticFCN_opt.py:155-166,227-236 build torchvision's `shuff
 stride-1 conv over input + meta channels and wire `stem = conv1` (no maxpool), `layer1..3 = stage2..4`, `layer4 = conv5`).
 
 torchvision is not needed: the classes below re-create the public architecture of torchvision's `shufflenetv2.py` -- module names, parameter
-shapes and therefore `state_dict` keys, default initialisation -- without a forward (the arithmetic lives in fpn.py on the HIP kernels);
-`pretrained` weights are not downloaded, load a checkpoint.
+shapes and therefore `state_dict` keys, default initialisation -- without a module forward (the arithmetic lives in `unit_forward` / `encode`
+below, on the HIP kernels); `pretrained` weights are not downloaded, load a checkpoint.
 
 The unit (`InvertedResidual`):
   stride 1   out = shuffle(cat(x[:, :C/2], branch2(x[:, C/2:])))
@@ -17,7 +17,12 @@ from __future__ import annotations
 
 from typing import List
 
+import torch
 import torch.nn as nn
+
+from . import ops
+from .encoder_family import EncoderFamily, run_stages
+from .ops import ConvSource
 
 # (stage repeats, [conv1, stage2, stage3, stage4, conv5] output channels) -- torchvision's shufflenet_v2_x* constructors
 _CONFIGS = {
@@ -74,3 +79,69 @@ class ShuffleNetV2Container(nn.Module):
         cout = chans[-1]
         self.conv5 = nn.Sequential(nn.Conv2d(cin, cout, 1, 1, 0, bias=False), nn.BatchNorm2d(cout), nn.ReLU(inplace=True))
         self.fc = nn.Linear(cout, num_classes)
+
+
+# ----------------------------------------------------------------------------------------------------------------
+def build(host, backbone, input_channels, meta_channel_dim):
+    """The torchvision-shaped ShuffleNetV2 with the reference's surgery (semanticFCN.py:181-190): conv1[0] replaced by a 3x3 / stride-1 conv
+    over input + meta channels, `stem` = conv1 (no maxpool), layer1..3 = stage2..4, layer4 = conv5.  Returns the channel ladder."""
+    host.meta_channel_dim = meta_channel_dim
+    host.backbone = ShuffleNetV2Container(backbone)
+    host.backbone.conv1[0] = nn.Conv2d(input_channels + meta_channel_dim, host.backbone.conv1[0].out_channels, kernel_size=3, stride=1, padding=1,
+                                       bias=False)
+    host.stem = host.backbone.conv1
+    host.layer1, host.layer2, host.layer3, host.layer4 = host.backbone.stage2, host.backbone.stage3, host.backbone.stage4, host.backbone.conv5
+    return list(BASE_CHANNELS[backbone])
+
+
+def folded_tail(host, name, dw: nn.Conv2d, dw_bn, pw: nn.Conv2d, pw_bn):
+    """(wdw [C, 9], bdw [C], wpack, bpw [Co]) of a unit's depthwise 3x3 -> BN -> 1x1 -> BN -> ReLU tail with both BatchNorms folded in, cached on
+    `host` per parameter version and conv precision (the pointwise product is the exact-fp32 MFMA under 'fp32' and 'f16x3' alike)."""
+    def make():
+        w9, b9 = host._fold(dw.weight, None, dw_bn)
+        w1, b1 = host._fold(pw.weight, None, pw_bn)
+        co, c = w1.shape[0], w1.shape[1]
+        return (w9.detach().float().reshape(c, 9).contiguous(), b9.detach().float().contiguous(),
+                ops.pack_shuffle_tail_weight(w1.detach().float().reshape(co, c).contiguous()), b1.detach().float().contiguous())
+    return host._cached("_shf_cache", name, (dw.weight, dw_bn.weight, dw_bn.bias, dw_bn.running_mean, dw_bn.running_var,
+                                             pw.weight, pw_bn.weight, pw_bn.bias, pw_bn.running_mean, pw_bn.running_var), make)
+
+
+def unit_forward(host, n: str, blk, x, meta_k=None):
+    """One InvertedResidual: the fused conv for branch2's first 1x1 (+ BN + ReLU), slu_shuffle_tail_fwd for the rest -- two launches for a
+    stride-1 unit, three for a stride-2 one.  meta_k: the meta channels that replace the last m input channels (first unit of a stage)."""
+    b2 = blk.branch2
+    cx = x.shape[1]
+    bf = b2[5].out_channels
+    if blk.stride == 1:
+        if meta_k is not None:
+            raise NotImplementedError("meta injection into a stride-1 ShuffleNetV2 unit does not occur (every stage opens with a stride-2 unit)")
+        h = host._conv(n + ".branch2.0", b2[0], b2[1], [ConvSource(x, None, False, 0, bf, cx - bf)])                  # x[:, C/2:]
+        return ops.shuffle_tail(h, *folded_tail(host, n + ".branch2.3", b2[3], b2[4], b2[5], b2[6]), bf, 1, passthrough=x)
+    m = 0 if meta_k is None else meta_k.shape[1]
+    b1 = blk.branch1
+    out = torch.empty((x.shape[0], 2 * bf, (x.shape[2] + 1) // 2, (x.shape[3] + 1) // 2), dtype=torch.float32, device=x.device)
+    ops.shuffle_tail(x, *folded_tail(host, n + ".branch1.0", b1[0], b1[1], b1[2], b1[3]), bf, 2, out=out, parity=0, cuse=cx - m, src2=meta_k)
+    src = [ConvSource(x)] if meta_k is None else [ConvSource(meta_k), ConvSource(x, None, False, 0, cx - m)]             # (meta, x[:, :-m])
+    h = host._conv(n + ".branch2.0", b2[0], b2[1], src, tail_first=m)
+    return ops.shuffle_tail(h, *folded_tail(host, n + ".branch2.3", b2[3], b2[4], b2[5], b2[6]), bf, 2, out=out, parity=1)
+
+
+def encode(host, x, meta):
+    """(x1, x2, x3, x4) at 1/2, 1/4, 1/8, 1/8 resolution: stem (conv + BN + ReLU, stride 1), stage2..4, conv5, with the multi-scale meta
+    injection on the way into stage3 / stage4 / conv5 (semanticFCN.py:306-314)."""
+    m1 = m2 = m3 = None
+    if host.multi_scale_meta:
+        m1, m2, m3 = ops.nearest_down(meta, 2), ops.nearest_down(meta, 4), ops.nearest_down(meta, 8)
+    h = host._conv("stem", host.stem[0], host.stem[1], [ConvSource(x), ConvSource(meta)])
+    x1, x2, x3 = run_stages(host, unit_forward, h, (("layer1", host.layer1, None), ("layer2", host.layer2, m1), ("layer3", host.layer3, m2)))
+    m = 0 if m3 is None else m3.shape[1]
+    src = [ConvSource(x3)] if m3 is None else [ConvSource(m3), ConvSource(x3, None, False, 0, x3.shape[1] - m)]
+    x4 = host._conv("layer4", host.layer4[0], host.layer4[1], src, tail_first=m)
+    return x1, x2, x3, x4
+
+
+# no stride-2 depthwise backward, so no training; model.train() with every BatchNorm in eval mode is not refused (it never was)
+FAMILY = EncoderFamily(backbones=tuple(BASE_CHANNELS), build=build, encode=encode, head_scales=(4, 4, 2),
+                       inference_clause="the ShuffleNetV2 units have no backward kernels", training_refuses=False, trains_in_opt=False,
+                       mc_shared_prefix=False)

@@ -123,7 +123,7 @@ def test_gate_kernel(cuda, s, c, t):
     if t == 1:                                                                         # [N, C] is taken as [N, C, 1]; the composed gate agrees
         assert torch.equal(ops.se_gate_psum(mean.to(cuda), 1, *d), got)
         composed = ops.se_scale(mean.view(n, c, 1, 1).to(cuda).contiguous(), *d)
-        assert float((composed - got).abs().max()) <= 1e-5
+        assert torch.equal(composed, got)                                              # one kernel behind both entry points (csrc/se_gate.hip)
 
 
 # ---------------- one MBConv block end to end ----------------
