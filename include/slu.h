@@ -88,8 +88,10 @@ typedef struct slu_conv_desc {   /* HOST struct */
 /* precision of the multiply-accumulate inside slu_conv2d_fwd (inputs, outputs and accumulation are fp32 either way):
  *   SLU_CONV_FP32  : v_mfma_f32_32x32x2_f32, bit-for-bit a k-ordered fmaf chain; wpack from slu_pack_conv_weight, ck = slu_conv_ck
  *   SLU_CONV_F16X3 : every fp32 operand x is split x = hi + lo (two fp16), products hi*hi + hi*lo + lo*hi on
- *                    v_mfma_f32_32x32x16_f16 (fp32 accumulate): ~2^-22 relative error per product, 5.3x fewer MFMA
- *                    cycles; |x| must stay below 65504; wpack from slu_pack_conv_weight_f16x3, ck = 16 */
+ *                    v_mfma_f32_32x32x16_f16 (fp32 accumulate): ~2^-22 relative error per product while lo is a normal
+ *                    fp16 (|x| >= 2^-3), an absolute operand error of 2^-24 below that (2e-5 of the output scale holds while
+ *                    both operands have rms >= 2^-8), hi saturates above 65504 and lo carries the rest up to 131008
+ *                    (DESIGN 3.1b); 5.3x fewer MFMA cycles; wpack from slu_pack_conv_weight_f16x3, ck = 16 */
 #define SLU_CONV_FP32  0
 #define SLU_CONV_F16X3 1
 

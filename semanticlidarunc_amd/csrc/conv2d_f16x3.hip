@@ -5,6 +5,13 @@
 // with the exact-fp32 kernel to fp32-level accuracy while the matrix-core time drops 5.3x (3 x 32 cycles per 16 channels x 32 x 32 instead of 8 x 64), which moves the
 // 3x3 / 2x2 convs of the range-image stack from MFMA-bound towards HBM-bound.
 //
+// Accuracy (measured; tests/f16x3_restatement.py restates this arithmetic on the CPU and tests/test_gpu_f16x3_split.py holds the
+// kernels to it): |result - exact| <= (2^-21 + 2^-24 / rms|x| + 2^-24 / rms|w|) of the output scale.  Full accuracy (~1e-6) holds while lo is
+// a NORMAL fp16, |x| >= 2^-3; below that lo is a subnormal with an absolute step of 2^-24, so the operand's relative error is 2^-24 / |x|:
+// 2e-5 of the output scale holds while both operands have rms >= 2^-8 (4e-3) -- BatchNorm-folded weights (fpn.py) are subject to it.
+// Above 65504 hi saturates and lo carries the rest up to 131008.  The matrix core keeps subnormal operands; its block alignment by
+// exponent field only matters once hi itself is a few steps of 2^-24.
+//
 // LDS images (channel-innermost so one ds_read_b128 is one MFMA operand):
 //   B: [2 groups of 8 channels][rows][cols][8 x fp16]  hi and lo  -- lane (pixel r, half h) reads record
 //      (group h, pixel r + tap offset): consecutive lanes = consecutive 16-byte records, conflict-free
@@ -23,7 +30,8 @@ namespace {
 constexpr int CK16 = 16;
 
 // x = hi + lo with hi = fp16(x) rounded toward zero (v_cvt_pkrtz_f16_f32 converts two values per instruction)
-// and lo = fp16(x - hi): 3 VALU per element; hi carries 11 bits, lo at least 10 more.
+// and lo = fp16(x - hi), also toward zero: 3 VALU per element; hi carries 11 bits and lo 11 more while lo is a normal fp16 (|x| >= 2^-3);
+// below that lo is a subnormal, a multiple of 2^-24.  A finite |x| > 65504 gives hi = +-65504 and lo the rest, up to 131008 in all.
 __device__ __forceinline__ void split8(const float (&x)[8], uint4& hi, uint4& lo) {
   unsigned h[4], l[4];
 #pragma unroll

@@ -118,7 +118,10 @@ class WeightPackPlan:
 
 
 def pack_conv_weight_f16x3(weight: torch.Tensor) -> torch.Tensor:
-    """OIHW fp32 weight -> split-fp16 (hi, lo) MFMA A-fragment image for precision='f16x3'."""
+    """OIHW fp32 weight -> split-fp16 (hi, lo) MFMA A-fragment image for precision='f16x3'.
+    Each weight is stored as hi = fp16(w) toward zero and lo = fp16(w - hi): 22 bits while lo is a normal fp16 (|w| >= 2^-3), an absolute
+    error of 2^-24 below that.  The conv stays within 2e-5 of its output scale while the weights (and the inputs) have rms >= 2^-8 (4e-3);
+    smaller weights -- BatchNorm-folded ones can be -- lose accuracy as 2^-24 / rms|w|."""
     _req(weight, "weight")
     if weight.dim() != 4 or weight.shape[2] != weight.shape[3]:
         raise RuntimeError(f"weight: expected [Cout,Cin,k,k], got {tuple(weight.shape)}")
@@ -157,6 +160,8 @@ def conv2d_fused(srcs: Sequence[ConvSource], wpack: torch.Tensor, cout: int, ksi
                  stats: Optional[torch.Tensor] = None, n_out: Optional[int] = None) -> torch.Tensor:
     """out = resid + bn_a * leaky(conv(cat(srcs)) + bias) + bn_b   (see slu_conv2d_fwd).
     precision 'fp32' (exact, wpack from pack_conv_weight) or 'f16x3' (split-fp16, wpack from pack_conv_weight_f16x3).
+    'f16x3' is within (2^-21 + 2^-24 / rms|x| + 2^-24 / rms|w|) of the output scale of the exact result: ~1e-6 for O(1) operands, 2e-5 while
+    both operands have rms >= 2^-8, worse below; |x| above 65504 is carried by the lo part up to 131008.
     n_out: the output batch, for a conv whose sources are all batch-broadcast (`ConvSource.nbatch`); otherwise it is the first source's."""
     if precision not in PRECISIONS:
         raise ValueError(f"unknown conv precision {precision!r}")

@@ -1,5 +1,9 @@
 """GPU: the split-fp16 conv path (three f16 MFMAs per K-step, fp32 accumulate) against the fp32 oracle and the
-exact-fp32 kernel.  Same bars as the exact path: single convs 1e-4 abs on O(1) outputs, whole network 1e-3."""
+exact-fp32 kernel.  Same bars as the exact path: single convs 1e-4 abs on O(1) outputs, whole network 1e-3.
+
+These bars are about 100 x wider than the kernel's arithmetic.  The sharp checks are test_gpu_conv_lattice.py (bit equality on inputs
+whose answer is exact in any order, both conv paths, every instantiation) and test_gpu_f16x3_split.py (ordinary values against a CPU
+restatement of the three-term sum, at 4 x the fp32 CPU conv's own error, and the sweep over operand magnitude)."""
 import numpy as np
 import pytest
 import torch
