@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SLU_ABI_VERSION 42
+#define SLU_ABI_VERSION 43
 
 #define SLU_OK            0
 #define SLU_EINVAL       -1   /* null pointer / non-positive size / inconsistent descriptor   */
@@ -564,6 +564,38 @@ int slu_binned_stats(const float* u, const uint8_t* correct, long long n, const 
 size_t slu_group_by_class_workspace_bytes(long long n);
 int slu_group_by_class(const int64_t* labels, const float* values, long long n, int C, float* out_values, int64_t* counts, void* workspace,
                        size_t workspace_bytes, slu_stream_t stream);
+
+/* ---- temperature scaling (models/temp_scaling.py:26-33,78,88-104 the cache; :142-154,158-170 the objective; DESIGN "Temperature
+ * scaling on the device") ---------------------------------------------------------------------------------------------------------
+ * slu_calib_rows: the calibration cache of one batch.  out [B,C,HW] fp32 of `kind` 0 logits / 1 probs / 2 log-probs; per pixel
+ *     kind 0: m = max_c x_c, e_c = exp(x_c - m), p_c = e_c / sum_c e_c (the softmax form, sum in class order), row_c = logf(max(p_c, 1e-12f))
+ *     kind 1: row_c = logf(max(x_c, 1e-12f))              kind 2: p_c = exp(x_c), row_c = logf(max(p_c, 1e-12f))
+ *   p_c is an fp32 value, but e_c, their sum and the quotient are evaluated in fp64 and rounded once (log p near 0 magnifies every
+ *   ulp of p), and so are exp and logf: a row is the correctly rounded logarithm of the correctly rounded probability.
+ *   The pixels with label != ignore_index (every pixel when !has_ignore) are appended in (b, h, w) order -- what the reference's
+ *   boolean mask returns -- at row count[0]: rows [cap, C] fp32 row-major, row_labels [cap] int64, then count[0] += their number
+ *   (count: DEVICE int64, zero it before the first batch).  A row at or past `cap` is dropped, never written: count[0] > cap afterwards
+ *   tells.  Plain launches (valid pixels per 256-pixel block, their scan by one workgroup, the scatter; rows leave through LDS in
+ *   256-byte segments); no workgroup waits on another.  C <= 32 (SLU_EUNSUPPORTED above), B HW < 2^31.
+ * slu_temp_nll: the objective of the fit and its derivative for the rows i = idx[j], j < M (idx DEVICE int64; NULL: i = j < N, M ignored).
+ *   With x = rows[i], y = row_labels[i]:
+ *     T = max(expf(log_T[0]), 1e-3f), an fp32 value (the exponential correctly rounded),  s_c = x_c / T,  m = max_c s_c,
+ *     S = sum_c exp(s_c - m) in class order,  p_c = exp(s_c - m) / S
+ *     loss = m + log(S) - s_y
+ *     g    = (x_y - sum_c p_c x_c) / T = d loss / d log_T, evaluated as sum_c p_c (x_y - x_c) / T;   g = 0 where expf(log_T[0]) < 1e-3f
+ *            (the sub-gradient of clamp_min)
+ *   Everything after T is fp64 on the fp32 rows: an fp32 row is about as far from the exact value as the reference's own fp32
+ *   evaluation, and the sum over the rows of either can cancel to a tenth of that (DESIGN).
+ *   loss_sum[0] = sum loss, g_sum[0] = sum g (fp64: per-thread, then the wave's butterfly, the workgroup's four waves in order, one
+ *   partial per workgroup, and one workgroup that adds the partials in index order: no floating-point atomics, the same bits run to
+ *   run); bad[0] = rows with y outside [0, C) or i outside [0, N): they contribute nothing.  log_T is read on the DEVICE.  All three
+ *   outputs are overwritten.  C <= 32. */
+size_t slu_calib_rows_workspace_bytes(int B, int HW);
+int slu_calib_rows(const float* out, int kind, const int64_t* labels, int B, int C, int HW, int has_ignore, int64_t ignore_index, float* rows,
+                   int64_t* row_labels, long long cap, int64_t* count, void* workspace, size_t workspace_bytes, slu_stream_t stream);
+size_t slu_temp_nll_workspace_bytes(long long n);
+int slu_temp_nll(const float* rows, const int64_t* row_labels, long long N, int C, const int64_t* idx, long long M, const float* log_T,
+                 double* loss_sum, double* g_sum, int64_t* bad, void* workspace, size_t workspace_bytes, slu_stream_t stream);
 
 /* ---- Tversky loss (models/losses.py:74-128, the 'Tversky' loss branch trainer.py:497-503) -----------------------
  * valid = 0 <= y < C and (no ignore or y != ignore_index); p by model_act (0 logits: softmax, 1 probs, 2 log_probs: exp);

@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-ABI_VERSION = 42
+ABI_VERSION = 43
 MAX_SRC = 3
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libslu_hip.so")
@@ -243,6 +243,12 @@ SIGNATURES = {
     "slu_build_normals": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_float, c_f32p, c_stream]),
     "slu_group_by_class_workspace_bytes": (C.c_size_t, [C.c_longlong]),
     "slu_group_by_class": (C.c_int, [c_i64p, c_f32p, C.c_longlong, C.c_int, c_f32p, c_i64p, C.c_void_p, C.c_size_t, c_stream]),
+    "slu_calib_rows_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "slu_calib_rows": (C.c_int, [c_f32p, C.c_int, c_i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, c_f32p, c_i64p, C.c_longlong, c_i64p,
+                                 C.c_void_p, C.c_size_t, c_stream]),
+    "slu_temp_nll_workspace_bytes": (C.c_size_t, [C.c_longlong]),
+    "slu_temp_nll": (C.c_int, [c_f32p, c_i64p, C.c_longlong, C.c_int, c_i64p, C.c_longlong, c_f32p, c_f64p, c_f64p, c_i64p, C.c_void_p, C.c_size_t,
+                               c_stream]),
     "slu_dirichlet_loss_fwd_ex": (C.c_int, [c_f32p, c_i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_float, C.c_int, C.c_int64,
                                             c_f64p, c_i64p, c_stream]),
     "slu_dirichlet_loss_bwd_ex": (C.c_int, [c_f32p, c_i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_float, C.c_int, C.c_int64,

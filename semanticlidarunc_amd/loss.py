@@ -101,3 +101,41 @@ def salsanext_loss(logits, labels, w_nll: float = 1.0, w_ls: float = 1.0, lovasz
     """(loss, nll, lovasz) of the reference's "SalsaNext" loss branch; `loss` is differentiable w.r.t. logits, the two terms are
     values only (marked non-differentiable)."""
     return SalsaNextLossFn.apply(logits, labels, w_nll, w_ls, lovasz_ignore)
+
+
+class TempNllFn(torch.autograd.Function):
+    """(log_T, rows, row_labels, idx, denom, chunk_size) -> (loss_sum / denom, bad): the objective of temperature scaling
+    (models/temp_scaling.py:145-151) with T = max(exp(log_T), 1e-3) read on the device; d / d log_T = g_sum / denom comes out of the
+    same pass (ops.temp_nll), so the backward launches nothing.  At most `chunk_size` rows per launch, the chunks' fp64 sums added in
+    chunk order.  loss is float64; bad (int64 [1], rows whose label is outside [0, C)) is not differentiable."""
+
+    @staticmethod
+    def forward(ctx, log_T, rows, row_labels, idx, denom, chunk_size):
+        lt = log_T.detach().float().contiguous()
+        n = rows.shape[0] if idx is None else idx.numel()
+        step = n if not chunk_size or chunk_size <= 0 else int(chunk_size)
+        loss = g = bad = None
+        for i in range(0, n, step):
+            j = min(i + step, n)
+            if idx is None:
+                part = ops.temp_nll(rows[i:j], row_labels[i:j], lt)
+            else:
+                part = ops.temp_nll(rows, row_labels, lt, idx[i:j])
+            loss, g, bad = part if loss is None else (loss + part[0], g + part[1], bad + part[2])
+        ctx.save_for_backward(g / float(denom))
+        ctx.like = (log_T.shape, log_T.dtype)
+        ctx.mark_non_differentiable(bad)
+        return (loss / float(denom)).reshape(()), bad
+
+    @staticmethod
+    def backward(ctx, gout, _gbad):
+        (g,) = ctx.saved_tensors
+        shape, dtype = ctx.like
+        return (g * gout.to(torch.float64)).to(dtype).reshape(shape), None, None, None, None, None
+
+
+def temp_nll_loss(log_T, rows, row_labels, idx=None, denom=None, chunk_size=None):
+    """(loss, bad) of TempNllFn; denom defaults to the number of rows evaluated."""
+    if denom is None:
+        denom = rows.shape[0] if idx is None else idx.numel()
+    return TempNllFn.apply(log_T, rows, row_labels, idx, denom, chunk_size)

@@ -1447,6 +1447,65 @@ def group_by_class(labels: torch.Tensor, values: torch.Tensor, num_classes: int)
     return out, counts
 
 
+# ------------------------------------------------------------------------------------------------
+# temperature scaling (models/temp_scaling.py): the calibration cache and the fused NLL(T) closure
+# ------------------------------------------------------------------------------------------------
+CALIB_KINDS = {"logits": 0, "probs": 1, "log_probs": 2}
+
+
+def calib_rows(out: torch.Tensor, kind: str, labels: torch.Tensor, ignore_index, rows: torch.Tensor, row_labels: torch.Tensor, count: torch.Tensor):
+    """Append the log-probability rows of the pixels with label != ignore_index (all when None), in (b, h, w) order, to the cache
+    `rows` fp32 [cap, C] / `row_labels` int64 [cap] at row count[0] (int64 [1] on the device, advanced by the launch; rows past cap are
+    dropped and count[0] > cap tells).  out fp32 [B,C,H,W] of `kind` 'logits' | 'probs' | 'log_probs', labels int64 [B,H,W].  No host
+    synchronisation."""
+    _req(out, "out")
+    _req(labels, "labels", torch.int64)
+    _req(rows, "rows")
+    _req(row_labels, "row_labels", torch.int64)
+    _req(count, "count", torch.int64)
+    if kind not in CALIB_KINDS:
+        raise ValueError(f"Unknown output kind: {kind}")
+    if out.dim() != 4 or tuple(labels.shape) != (out.shape[0], out.shape[2], out.shape[3]) or out.numel() == 0:
+        raise RuntimeError(f"calib_rows: out [B,C,H,W] / labels [B,H,W] expected, got {tuple(out.shape)} / {tuple(labels.shape)}")
+    b, c, h, w = out.shape
+    if rows.dim() != 2 or rows.shape[1] != c or rows.shape[0] == 0 or tuple(row_labels.shape) != (rows.shape[0],) or count.numel() != 1:
+        raise RuntimeError(f"calib_rows: rows [cap,{c}] / row_labels [cap] / count [1] expected, got {tuple(rows.shape)} / "
+                           f"{tuple(row_labels.shape)} / {tuple(count.shape)}")
+    lib = _lib.load()
+    ws = torch.empty(lib.slu_calib_rows_workspace_bytes(b, h * w), dtype=torch.uint8, device=out.device)
+    check(lib.slu_calib_rows(out.data_ptr(), CALIB_KINDS[kind], labels.data_ptr(), b, c, h * w, 0 if ignore_index is None else 1,
+                             0 if ignore_index is None else int(ignore_index), rows.data_ptr(), row_labels.data_ptr(), rows.shape[0],
+                             count.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "slu_calib_rows")
+
+
+def temp_nll(rows: torch.Tensor, row_labels: torch.Tensor, log_T: torch.Tensor, idx: Optional[torch.Tensor] = None):
+    """rows fp32 [N,C], row_labels int64 [N], log_T fp32 [1] (all on the device), idx int64 [M] or None -> (loss_sum float64 [1],
+    g_sum float64 [1], bad int64 [1]) on the device: the sums of NLL(rows[i] / T) and of its derivative by log T over i = idx[j] (None: all
+    rows), T = max(exp(log_T), 1e-3); bad = rows skipped because their label is outside [0, C) or their index outside [0, N).  The
+    temperature is read on the device: no host synchronisation."""
+    _req(rows, "rows")
+    _req(row_labels, "row_labels", torch.int64)
+    _req(log_T, "log_T")
+    if rows.dim() != 2 or rows.numel() == 0 or tuple(row_labels.shape) != (rows.shape[0],) or log_T.numel() != 1:
+        raise RuntimeError(f"temp_nll: rows [N,C] / row_labels [N] / log_T [1] expected, got {tuple(rows.shape)} / {tuple(row_labels.shape)} / "
+                           f"{tuple(log_T.shape)}")
+    m = 0
+    if idx is not None:
+        _req(idx, "idx", torch.int64)
+        if idx.dim() != 1 or idx.numel() == 0:
+            raise RuntimeError(f"temp_nll: idx must be a non-empty 1-D tensor, got {tuple(idx.shape)}")
+        m = idx.numel()
+    n, c = rows.shape
+    lib = _lib.load()
+    ws = torch.empty(lib.slu_temp_nll_workspace_bytes(m or n), dtype=torch.uint8, device=rows.device)
+    loss = torch.empty(1, dtype=torch.float64, device=rows.device)
+    g = torch.empty(1, dtype=torch.float64, device=rows.device)
+    bad = torch.empty(1, dtype=torch.int64, device=rows.device)
+    check(lib.slu_temp_nll(rows.data_ptr(), row_labels.data_ptr(), n, c, _ptr(idx), m, log_T.data_ptr(), loss.data_ptr(), g.data_ptr(),
+                           bad.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "slu_temp_nll")
+    return loss, g, bad
+
+
 def _c_params(params):
     import ctypes as C
     vals = [float(v) for v in params]
