@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SLU_ABI_VERSION 43
+#define SLU_ABI_VERSION 44
 
 #define SLU_OK            0
 #define SLU_EINVAL       -1   /* null pointer / non-positive size / inconsistent descriptor   */
@@ -778,6 +778,22 @@ int slu_global_avgpool(const float* x, float* out, int N, int C, int HW, slu_str
 int slu_se_gate(const float* avg, const float* w1, const float* b1, const float* w2, const float* b2, float* scale, int N, int C, int S,
                 slu_stream_t stream);
 
+/* ---- What the encoder unit kernels below share (ShuffleNetV2 tail, SqueezeNet Fire and ceil pool, RegNetY sampling) -------------------------
+ * slu_cat2: the input of a unit, the channel concatenation  src0[:, coff0 : coff0 + c0]  (+)  src1[:, :c1]  of dense NCHW fp32 tensors with
+ * ct0 / ct1 stored channels at one H x W (src1 NULL, c1 = 0: one source); C = c0 + c1.  It is how a stage reads x[:, :-m] (+) meta_k, or half
+ * of a tensor, in place.  c0 >= 1, 0 <= coff0, coff0 + c0 <= ct0, and with src1 1 <= c1 <= ct1: anything else is SLU_EINVAL.  The output of an
+ * entry point that takes one must not overlap either stored tensor (SLU_EINVAL).
+ * Packed weights: the A operand of v_mfma_f32_32x32x2_f32 as the kernels load it.  The image of W [R][K] (or [R][K][taps]) with K-chunk kc is
+ * [ceil(R / 32)][taps][ceil(K / kc) * kc / 2][64] floats: lane l of (32-row block m, tap t, K-step k2) holds W[32 m + (l & 31)][2 k2 + (l >> 5)][t],
+ * 0 outside the matrix.  slu_shuffle_tail_pack: W = wpw [Co][C], kc = 32.  slu_fire_pack: the images of wsq [S][Cin] (kc = 32), w1 [E1][S]
+ * (kc = 16) and w3 [E3][S][9] (kc = 16, taps = 9), one after the other. */
+typedef struct slu_cat2 {
+  const float* src0;
+  const float* src1;
+  int32_t ct0, coff0, c0;
+  int32_t ct1, c1;
+} slu_cat2;                /* 40 bytes */
+
 /* ---- ShuffleNetV2 unit tail (models/semanticFCN.py:181-190 and baselines/Reichert/semanticFCN_opt.py:227-236 build torchvision's
  * shufflenet_v2_x{0_5,1_0,1_5,2_0}; the unit is torchvision's InvertedResidual) ---------------------------------------------------------
  * slu_shuffle_tail_fwd: depthwise 3x3 (pad 1, stride 1 or 2) -> pointwise 1x1 -> ReLU with both eval BatchNorms folded in, stored through the
@@ -787,17 +803,14 @@ int slu_se_gate(const float* avg, const float* w1, const float* b1, const float*
  *   out[n, 2j + parity]  = y[n,j]
  *   out[n, 2j]           = pass[n,j]       when pass != NULL (parity must then be 1)
  *
- * src is the channel concatenation  src0[:, coff0 : coff0 + c0]  (+)  src1[:, :c1]  of dense NCHW fp32 tensors with ct0 / ct1 stored channels at
- * H x W (src1 NULL, c1 = 0: one source); C = c0 + c1.  out is [N][2 Co][Ho][Wo], Ho = ceil(H / stride), Wo likewise; the channels of the other
+ * src is the slu_cat2 `in` at H x W, C = c0 + c1 channels.  out is [N][2 Co][Ho][Wo], Ho = ceil(H / stride), Wo likewise; the channels of the other
  * parity are left untouched when pass is NULL.  pass is [N][pass_ct][Ho][Wo] and its first Co channels are copied.  The depthwise result stays
  * on chip.  The pointwise product is exact fp32 (v_mfma_f32_32x32x2_f32) whatever the conv precision of the surrounding model; no atomics, so
  * results are bit-identical run to run.  wpack = slu_shuffle_tail_pack of wpw [Co][C] (slu_shuffle_tail_packed_floats(Co, C) floats; 0 =
- * unsupported).  Co <= 512, stride 1 / 2, N <= 65535, H W < 2^31; anything else is SLU_EUNSUPPORTED.  out must not overlap an input. */
+ * unsupported).  Co <= 512, stride 1 / 2, N <= 65535, H W < 2^31; anything else is SLU_EUNSUPPORTED.  out must not overlap `in` or pass
+ * (SLU_EINVAL). */
 typedef struct slu_shuffle_tail_desc {   /* HOST struct */
-  const float* src0;
-  const float* src1;
-  int32_t ct0, coff0, c0;
-  int32_t ct1, c1;
+  slu_cat2 in;
   int32_t N, H, W, stride;
   int32_t Co, parity;
   int32_t pass_ct;
@@ -820,22 +833,17 @@ int slu_shuffle_tail_fwd(const slu_shuffle_tail_desc* d, slu_stream_t stream);
  *   out[n,j]      = relu( b1[j] + sum_k w1[j,k] * s[n,k] )                                           j < E1
  *   out[n,E1 + j] = relu( b3[j] + sum_{k,a,b} w3[j,k,a,b] * s[n,k, y-1+a, x-1+b] )                   j < E3
  *
- * src is the channel concatenation  src0[:, coff0 : coff0 + c0]  (+)  src1[:, :c1]  of dense NCHW fp32 tensors with ct0 / ct1 stored channels at
- * H x W (src1 NULL, c1 = 0: one source); Cin = c0 + c1.  out is [N][E1 + E3][H][W].  The squeeze map lives in LDS with a one-pixel halo around a
+ * src is the slu_cat2 `in` at H x W, Cin = c0 + c1 channels.  out is [N][E1 + E3][H][W].  The squeeze map lives in LDS with a one-pixel halo around a
  * 4 x 32 output tile and never goes to global memory; outside the image it is 0 (the padding of the 3x3 -- not relu(bsq), not the squeeze of a
  * clamped input), inside the image but outside the tile it is computed from the real input.  Every product is exact fp32
  * (v_mfma_f32_32x32x2_f32) whatever the conv precision of the surrounding model; no atomics, so results are bit-identical run to run.
  * wpack = slu_fire_pack of wsq [S][Cin], w1 [E1][S], w3 [E3][S][3][3] (slu_fire_packed_floats(Cin, S, E1, E3) floats, zero-filled outside the
  * matrices; 0 = unsupported).  Any Cin >= 1, 1 <= S <= 64, 1 <= E1, E3 <= 256, N <= 65535, H W < 2^31; anything else is SLU_EUNSUPPORTED.
- * out must not overlap an input (SLU_EINVAL).
- * slu_maxpool3s2_ceil_fwd: nn.MaxPool2d(3, 2, padding=0, ceil_mode=True) over the same two-source concatenation -> y [N][c0 + c1][Ho][Wo],
+ * slu_maxpool3s2_ceil_fwd: nn.MaxPool2d(3, 2, padding=0, ceil_mode=True) of the slu_cat2 `in` at H x W -> y [N][c0 + c1][Ho][Wo],
  * Ho = ceil((H - 3) / 2) + 1, Wo likewise; windows start at (2 oy, 2 ox) and are clipped at the far edge; H, W >= 3 (SLU_EINVAL below).  Not
  * slu_maxpool3s2_fwd (padding 1): for even H the output size is the same and the windows are shifted by one. */
 typedef struct slu_fire_desc {   /* HOST struct */
-  const float* src0;
-  const float* src1;
-  int32_t ct0, coff0, c0;
-  int32_t ct1, c1;
+  slu_cat2 in;
   int32_t N, H, W;
   int32_t S, E1, E3;
   int32_t reserved;
@@ -848,8 +856,7 @@ typedef struct slu_fire_desc {   /* HOST struct */
 size_t slu_fire_packed_floats(int cin, int s, int e1, int e3);
 int slu_fire_pack(const float* wsq, const float* w1, const float* w3, int cin, int s, int e1, int e3, float* out, slu_stream_t stream);
 int slu_fire_fwd(const slu_fire_desc* d, slu_stream_t stream);
-int slu_maxpool3s2_ceil_fwd(const float* src0, int ct0, int coff0, int c0, const float* src1, int ct1, int c1, float* y, int N, int H, int W,
-                            slu_stream_t stream);
+int slu_maxpool3s2_ceil_fwd(const slu_cat2* in, float* y, int N, int H, int W, slu_stream_t stream);
 
 /* ---- RegNetY block (models/semanticFCN.py:97-108,171-179 and baselines/Reichert/semanticFCN_opt.py:143-154 build torchvision's
  * regnet_y_{400mf,800mf,1_6gf,3_2gf}; the unit is torchvision's ResBottleneckBlock with a ReLU SqueezeExcitation) ---------------------------
@@ -868,15 +875,14 @@ int slu_maxpool3s2_ceil_fwd(const float* src0, int ct0, int coff0, int c0, const
  * relu(b1[s] + sum_c' w1[s, c'] * mean[n, c'])) -- fc1 [S][C], ReLU, fc2 [C][S], sigmoid of torchvision's SqueezeExcitation as RegNet builds
  * it (slu_se_gate is the SiLU form of EfficientNet).  psum [N][C][T]; T = 1 and inv_count = 1 take a plain [N][C] mean.  mean (optional,
  * [N][C]) receives the means.  Any S >= 1 and C >= 1 with (C + S) * 4 <= 64 KiB.  The gate reaches f.c as slu_conv_src.scale.
- * slu_regnet_sample2: y [N][c0 + c1][ceil(H / 2)][ceil(W / 2)] = cat(src0[:, coff0 : coff0 + c0], src1[:, :c1])[:, :, ::2, ::2] -- what the
- * 1x1 / stride-2 projection of a stage's first block reads, with the meta channels in place. */
+ * slu_regnet_sample2: y [N][c0 + c1][ceil(H / 2)][ceil(W / 2)] = in[:, :, ::2, ::2] of the slu_cat2 `in` at H x W -- what the 1x1 / stride-2
+ * projection of a stage's first block reads, with the meta channels in place. */
 int slu_regnet_gconv_tiles(int H, int W, int stride);
 int slu_regnet_gconv_fwd(const float* x, int ct, int coff, const float* wg, const float* bias, float* y, float* psum, int N, int C, int gw, int H, int W,
                          int stride, slu_stream_t stream);
 int slu_regnet_se_gate(const float* psum, int T, float inv_count, const float* w1, const float* b1, const float* w2, const float* b2, float* gate,
                        float* mean, int N, int C, int S, slu_stream_t stream);
-int slu_regnet_sample2(const float* src0, int ct0, int coff0, int c0, const float* src1, int ct1, int c1, float* y, int N, int H, int W,
-                       slu_stream_t stream);
+int slu_regnet_sample2(const slu_cat2* in, float* y, int N, int H, int W, slu_stream_t stream);
 
 /* ---- EfficientNetV2 MBConv middle (models/semanticFCN.py:124-135,192-201 builds torchvision's efficientnet_v2_{s,m,l}; the unit is torchvision's
  * MBConv: depthwise 3x3 + BatchNorm + SiLU, then a SqueezeExcitation with SiLU between its two layers) -----------------------------------------

@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-ABI_VERSION = 43
+ABI_VERSION = 44
 MAX_SRC = 3
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libslu_hip.so")
@@ -96,11 +96,19 @@ class CtxBlockH8Desc(C.Structure):
     ]
 
 
-class ShuffleTailDesc(C.Structure):
+class Cat2(C.Structure):
+    """slu_cat2: cat(src0[:, coff0:coff0 + c0], src1[:, :c1]); 40 bytes."""
     _fields_ = [
         ("src0", C.c_void_p), ("src1", C.c_void_p),
         ("ct0", C.c_int32), ("coff0", C.c_int32), ("c0", C.c_int32),
         ("ct1", C.c_int32), ("c1", C.c_int32),
+    ]
+
+
+class ShuffleTailDesc(C.Structure):
+    _anonymous_ = ("in_",)      # d.src0, d.ct0, ... reach the embedded record
+    _fields_ = [
+        ("in_", Cat2),
         ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("stride", C.c_int32),
         ("Co", C.c_int32), ("parity", C.c_int32),
         ("pass_ct", C.c_int32),
@@ -110,10 +118,9 @@ class ShuffleTailDesc(C.Structure):
 
 
 class FireDesc(C.Structure):
+    _anonymous_ = ("in_",)
     _fields_ = [
-        ("src0", C.c_void_p), ("src1", C.c_void_p),
-        ("ct0", C.c_int32), ("coff0", C.c_int32), ("c0", C.c_int32),
-        ("ct1", C.c_int32), ("c1", C.c_int32),
+        ("in_", Cat2),
         ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
         ("S", C.c_int32), ("E1", C.c_int32), ("E3", C.c_int32),
         ("reserved", C.c_int32),
@@ -294,12 +301,12 @@ SIGNATURES = {
     "slu_fire_packed_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "slu_fire_pack": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_stream]),
     "slu_fire_fwd": (C.c_int, [C.POINTER(FireDesc), c_stream]),
-    "slu_maxpool3s2_ceil_fwd": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, C.c_int, c_f32p, C.c_int, C.c_int, C.c_int, c_stream]),
+    "slu_maxpool3s2_ceil_fwd": (C.c_int, [C.POINTER(Cat2), c_f32p, C.c_int, C.c_int, C.c_int, c_stream]),
     "slu_regnet_gconv_tiles": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "slu_regnet_gconv_fwd": (C.c_int, [c_f32p, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                        c_stream]),
     "slu_regnet_se_gate": (C.c_int, [c_f32p, C.c_int, C.c_float, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, c_stream]),
-    "slu_regnet_sample2": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, C.c_int, c_f32p, C.c_int, C.c_int, C.c_int, c_stream]),
+    "slu_regnet_sample2": (C.c_int, [C.POINTER(Cat2), c_f32p, C.c_int, C.c_int, C.c_int, c_stream]),
     "slu_dwconv3x3_se_tiles": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "slu_dwconv3x3_se_fwd": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_stream]),
     "slu_se_gate_psum": (C.c_int, [c_f32p, C.c_int, C.c_float, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, c_stream]),

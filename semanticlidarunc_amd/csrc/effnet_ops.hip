@@ -7,7 +7,7 @@
 //   (the gate on the pooled vector, fc1 -> SiLU -> fc2 -> sigmoid, is slu_se_gate in se_gate.hip)
 //   dwconv3x3_wgrad_kernel  training: dL/dw[c][tap] = sum over (sample, pixel) of dy * shifted x -- one workgroup per channel, nine fp64 block sums
 //                           (the data gradient of the stride-1 depthwise conv is the forward kernel with the taps reversed)
-#include "pixel_common.h"
+#include "encoder_unit.h"
 
 namespace {
 
@@ -91,7 +91,7 @@ __global__ __launch_bounds__(256) void dwconv3x3_wgrad_kernel(const float* __res
 extern "C" int slu_dwconv3x3_fwd(const float* x, const float* w, const float* bias, float* y, int N, int C, int H, int W, int stride, int act,
                                  slu_stream_t stream) {
   if (!x || !w || !y || N <= 0 || C <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2) || (act != 0 && act != 3)) return SLU_EINVAL;
-  const int OH = (H + stride - 1) / stride, OW = (W + stride - 1) / stride;      // floor((H + 2 - 3) / stride) + 1
+  const int OH = slu_strided_out(H, stride), OW = slu_strided_out(W, stride);
   const size_t total = (size_t)N * C * OH * OW;
   if (stride == 1)
     hipLaunchKernelGGL(dwconv3x3_kernel<1>, dim3(slu_grid_1d(total, 65535)), dim3(256), 0, slu_stream(stream), x, w, bias, y, N * C, C, H, W, OH, OW, act);

@@ -16,12 +16,11 @@
 //                           are dealt to the waves as (row group of NBW tile rows) x (block phase): NBW = 4 -- a wave holds all four rows of a
 //                           block, blocks w, w + 4, ..; NBW = 2 -- two rows, blocks (w >> 1) + 2 i; NBW = 1 -- one row, every block.  A from the
 //                           packed image one chunk (8 K-steps) ahead, B from LDS (lane -> consecutive floats: conflict-free).  Small maps are
-//                           split over blockIdx.z by output blocks (each z recomputes the squeeze) and take the smaller NBW.
-//   fire_pack_kernel        wsq [S][Cin], w1 [E1][S], w3 [E3][S][3][3] -> the A-fragment images: lane l of (block m, K-step k2) holds
-//                           W[32 m + (l & 31)][2 k2 + (l >> 5)], zero outside the matrices; the 3x3 image is ordered (block, tap, K-step).
-//   maxpool3s2_ceil_kernel  nn.MaxPool2d(3, 2, padding=0, ceil_mode=True) over the same two-source channel concatenation.
+//                           split over blockIdx.z by output blocks (slu_cu_fill_split; each z recomputes the squeeze) and take the smaller NBW.
+//   fire_pack_kernel        wsq [S][Cin], w1 [E1][S], w3 [E3][S][3][3] -> their three A-fragment images (encoder_unit.h), one after the other.
+//   maxpool3s2_ceil_kernel  nn.MaxPool2d(3, 2, padding=0, ceil_mode=True) over the same slu_cat2.
 // Products are v_mfma_f32_32x32x2_f32 (exact fp32: a k-ordered fmaf chain); no atomics: results are bit-identical run to run.
-#include "pixel_common.h"
+#include "encoder_unit.h"
 
 namespace {
 
@@ -36,10 +35,10 @@ constexpr int FQ_KC = 2 * FQ_KS;                      //          of the next ch
 constexpr int F_MAX_S = 64, F_MAX_E = 256;
 
 struct FireArgs {
-  const float* src0;      // first channel read of source 0
-  const float* src1;      // source 1 or nullptr
-  long long bs0, bs1;     // floats between two images of each source tensor
-  int c0, C;              // channels taken from source 0, channels in all
+  const float* src0;      // the fields of Cat2Args (slu_cat2_fill), flat: as a member struct the kernels' argument loads change
+  const float* src1;
+  long long bs0, bs1;
+  int c0, C;
   int H, W, tx;           // tx = tiles per row of tiles
   int S, SP, E1, E3;      // SP = S rounded up to F_KC
   int nb1, nb3, mps1, mps3;   // 32-channel output blocks of the two expand convs; blocks per blockIdx.z
@@ -59,7 +58,7 @@ __device__ __forceinline__ void fire_load_b(const FireArgs& a, const float* s0, 
 #pragma unroll
   for (int kk = 0; kk < FQ_KS; ++kk) {
     const int c = q * FQ_KC + 2 * kk + hh;
-    const float* p = c < a.c0 ? s0 + (size_t)c * HW : s1 + (size_t)(c - a.c0) * HW;
+    const float* p = CAT2_PLANE(c, a.c0, s0, s1, HW);
 #pragma unroll
     for (int u = 0; u < 2; ++u) bv[u][kk] = *(c < a.C ? p + off[u] : zero);
   }
@@ -244,33 +243,10 @@ __global__ __launch_bounds__(256) void fire_kernel(const FireArgs a) {
 // out = [wsq image | w1 image | w3 image]; see the head of the file
 __global__ __launch_bounds__(256) void fire_pack_kernel(const float* __restrict__ wsq, const float* __restrict__ w1, const float* __restrict__ w3, int cin,
                                                         int s, int e1, int e3, size_t nq, size_t n1, size_t total, float* __restrict__ out) {
-  const int kq2 = (cin + FQ_KC - 1) / FQ_KC * FQ_KS, ks2 = (s + F_KC - 1) / F_KC * F_KS;
-  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-    float v = 0.0f;
-    if (e < nq) {
-      const int l = (int)(e & 63);
-      const size_t r = e >> 6;
-      const int k2 = (int)(r % kq2), m = (int)(r / kq2);
-      const int row = m * 32 + (l & 31), k = 2 * k2 + (l >> 5);
-      if (row < s && k < cin) v = wsq[(size_t)row * cin + k];
-    } else if (e < nq + n1) {
-      const size_t f = e - nq;
-      const int l = (int)(f & 63);
-      const size_t r = f >> 6;
-      const int k2 = (int)(r % ks2), m = (int)(r / ks2);
-      const int row = m * 32 + (l & 31), k = 2 * k2 + (l >> 5);
-      if (row < e1 && k < s) v = w1[(size_t)row * s + k];
-    } else {
-      const size_t f = e - nq - n1;
-      const int l = (int)(f & 63);
-      size_t r = f >> 6;
-      const int k2 = (int)(r % ks2);
-      r /= ks2;
-      const int tap = (int)(r % 9), m = (int)(r / 9);
-      const int row = m * 32 + (l & 31), k = 2 * k2 + (l >> 5);
-      if (row < e3 && k < s) v = w3[((size_t)row * s + k) * 9 + tap];
-    }
-    out[e] = v;
+  PIX_GRID_STRIDE(e, total) {
+    out[e] = e < nq        ? afrag_element(wsq, e, s, cin, FQ_KC, 1)
+             : e < nq + n1 ? afrag_element(w1, e - nq, e1, s, F_KC, 1)
+                           : afrag_element(w3, e - nq - n1, e3, s, F_KC, 9);
   }
 }
 
@@ -280,7 +256,7 @@ __global__ __launch_bounds__(256) void maxpool3s2_ceil_kernel(const float* __res
   const size_t total = (size_t)N * C * OH * OW;
   PIX_GRID_STRIDE(e, total) {
     const PixXYCN o = pix_xycn(e, OW, OH, C);
-    const float* p = o.c < c0 ? s0 + o.n * (size_t)bs0 + (size_t)o.c * H * W : s1 + o.n * (size_t)bs1 + (size_t)(o.c - c0) * H * W;
+    const float* p = CAT2_PLANE(o.c, c0, s0 + o.n * (size_t)bs0, s1 + o.n * (size_t)bs1, H * W);
     float m = -INFINITY;
 #pragma unroll
     for (int i = 0; i < 3; ++i)
@@ -298,10 +274,9 @@ struct FireSizes {
 };
 bool fire_sizes(int cin, int s, int e1, int e3, FireSizes& z) {
   if (cin <= 0 || s <= 0 || e1 <= 0 || e3 <= 0 || s > F_MAX_S || e1 > F_MAX_E || e3 > F_MAX_E) return false;
-  const size_t kq2 = (size_t)((cin + FQ_KC - 1) / FQ_KC) * FQ_KS, ks2 = (size_t)((s + F_KC - 1) / F_KC) * F_KS;
-  z.nq = (size_t)((s + 31) / 32) * kq2 * 64;
-  z.n1 = (size_t)((e1 + 31) / 32) * ks2 * 64;
-  z.n3 = (size_t)((e3 + 31) / 32) * 9 * ks2 * 64;
+  z.nq = afrag_floats(s, cin, FQ_KC, 1);
+  z.n1 = afrag_floats(e1, s, F_KC, 1);
+  z.n3 = afrag_floats(e3, s, F_KC, 9);
   return true;
 }
 
@@ -312,8 +287,6 @@ int launch_fire(const FireArgs& a, dim3 grid, size_t lds, int nbw, hipStream_t s
   else hipLaunchKernelGGL((fire_kernel<MS, 1>), grid, dim3(256), lds, st, a);
   SLU_CHECK_LAUNCH();
 }
-
-bool overlaps(const float* a, size_t na, const float* b, size_t nb) { return a < b + nb && b < a + na; }
 
 }  // namespace
 
@@ -333,23 +306,14 @@ extern "C" int slu_fire_pack(const float* wsq, const float* w1, const float* w3,
 }
 
 extern "C" int slu_fire_fwd(const slu_fire_desc* d, slu_stream_t stream) {
-  if (!d || !d->src0 || !d->wpack || !d->bsq || !d->b1 || !d->b3 || !d->out) return SLU_EINVAL;
-  if (d->N <= 0 || d->H <= 0 || d->W <= 0 || d->S <= 0 || d->E1 <= 0 || d->E3 <= 0) return SLU_EINVAL;
-  if (d->c0 <= 0 || d->ct0 <= 0 || d->coff0 < 0 || d->coff0 + d->c0 > d->ct0) return SLU_EINVAL;
-  if (d->src1 ? (d->c1 <= 0 || d->ct1 < d->c1) : d->c1 != 0) return SLU_EINVAL;
+  if (!d || !d->wpack || !d->bsq || !d->b1 || !d->b3 || !d->out || slu_cat2_check(d->in, d->N, d->H, d->W)) return SLU_EINVAL;
+  if (d->S <= 0 || d->E1 <= 0 || d->E3 <= 0) return SLU_EINVAL;
   FireSizes z;
-  if (!fire_sizes(d->c0 + d->c1, d->S, d->E1, d->E3, z)) return SLU_EUNSUPPORTED;
-  if (d->N > 65535 || (long long)d->H * d->W >= 0x7fffffffLL) return SLU_EUNSUPPORTED;
-  const size_t HW = (size_t)d->H * d->W, nout = (size_t)d->N * (d->E1 + d->E3) * HW;
-  if (overlaps(d->out, nout, d->src0, (size_t)d->N * d->ct0 * HW) || (d->src1 && overlaps(d->out, nout, d->src1, (size_t)d->N * d->ct1 * HW)))
-    return SLU_EINVAL;
+  if (!fire_sizes(d->in.c0 + d->in.c1, d->S, d->E1, d->E3, z) || slu_unit_grid_check(d->N, d->H, d->W)) return SLU_EUNSUPPORTED;
+  const size_t HW = (size_t)d->H * d->W;
+  if (slu_cat2_overlaps(d->in, d->N, HW, d->out, (size_t)d->N * (d->E1 + d->E3) * HW)) return SLU_EINVAL;
   FireArgs a;
-  a.src0 = d->src0 + (size_t)d->coff0 * HW;
-  a.src1 = d->src1;
-  a.bs0 = (long long)d->ct0 * HW;
-  a.bs1 = (long long)d->ct1 * HW;
-  a.c0 = d->c0;
-  a.C = d->c0 + d->c1;
+  slu_cat2_fill(a, d->in, HW);
   a.H = d->H; a.W = d->W;
   a.tx = (d->W + FT_W - 1) / FT_W;
   a.S = d->S;
@@ -361,12 +325,9 @@ extern "C" int slu_fire_fwd(const slu_fire_desc* d, slu_stream_t stream) {
   a.wsq = d->wpack; a.w1 = d->wpack + z.nq; a.w3 = d->wpack + z.nq + z.n1;
   a.bsq = d->bsq; a.b1 = d->b1; a.b3 = d->b3;
   a.out = d->out;
-  // Small maps leave most of the 256 CUs idle with one workgroup per tile: split the output blocks over up to 4 workgroups per tile (each
-  // recomputes the squeeze map) until there are about as many workgroups as CUs.
   const long long tiles = (long long)a.tx * ((d->H + FT_H - 1) / FT_H) * d->N;
   if (tiles > 0x7fffffffLL) return SLU_EUNSUPPORTED;
-  int split = 1;
-  while (split < 4 && tiles * split < 256 && a.nb3 >= 2 * split) split *= 2;
+  const int split = slu_cu_fill_split(tiles, a.nb3);
   a.mps3 = (a.nb3 + split - 1) / split;
   a.mps1 = (a.nb1 + split - 1) / split;
   const int nbw = a.mps3 >= 4 ? 4 : a.mps3 >= 2 ? 2 : 1;
@@ -375,14 +336,7 @@ extern "C" int slu_fire_fwd(const slu_fire_desc* d, slu_stream_t stream) {
   return d->S > 32 ? launch_fire<2>(a, grid, lds, nbw, slu_stream(stream)) : launch_fire<1>(a, grid, lds, nbw, slu_stream(stream));
 }
 
-extern "C" int slu_maxpool3s2_ceil_fwd(const float* src0, int ct0, int coff0, int c0, const float* src1, int ct1, int c1, float* y, int N, int H, int W,
-                                       slu_stream_t stream) {
-  if (!src0 || !y || N <= 0 || c0 <= 0 || ct0 <= 0 || coff0 < 0 || coff0 + c0 > ct0) return SLU_EINVAL;
-  if (src1 ? (c1 <= 0 || ct1 < c1) : c1 != 0) return SLU_EINVAL;
-  if (H < 3 || W < 3) return SLU_EINVAL;
-  const int OH = (H - 2) / 2 + 1, OW = (W - 2) / 2 + 1;      // ceil((H - 3) / 2) + 1
-  const size_t HW = (size_t)H * W, total = (size_t)N * (c0 + c1) * OH * OW;
-  hipLaunchKernelGGL(maxpool3s2_ceil_kernel, dim3(slu_grid_1d(total, 16384)), dim3(256), 0, slu_stream(stream), src0 + (size_t)coff0 * HW, src1,
-                     (long long)ct0 * HW, (long long)ct1 * HW, c0, c0 + c1, N, H, W, OH, OW, y);
-  SLU_CHECK_LAUNCH();
+extern "C" int slu_maxpool3s2_ceil_fwd(const slu_cat2* in, float* y, int N, int H, int W, slu_stream_t stream) {
+  if (!in || !y || slu_cat2_check(*in, N, H, W) || H < 3 || W < 3) return SLU_EINVAL;
+  return slu_cat2_resample(maxpool3s2_ceil_kernel, in, y, N, H, W, slu_ceil_pool3s2_out(H), slu_ceil_pool3s2_out(W), slu_stream(stream));
 }

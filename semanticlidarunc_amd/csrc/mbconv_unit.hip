@@ -15,7 +15,7 @@
 //     fmaf chain of dwconv3x3_kernel in the same (a, b) order (a padding tap adds w * 0), the same silu().
 //     The sum: every lane adds what it stores in a fixed order, wave_sum, one LDS slot per wave, the four slots added in wave order by one
 //     lane, one float per tile -- no atomics and no order between workgroups, so y and psum are bit-identical run to run.
-#include "pixel_common.h"
+#include "encoder_unit.h"
 
 namespace {
 
@@ -149,7 +149,7 @@ int launch_dwse(const float* x, const float* w, const float* bias, float* y, flo
 
 extern "C" int slu_dwconv3x3_se_tiles(int H, int W, int stride) {
   if (H <= 0 || W <= 0 || (stride != 1 && stride != 2)) return 0;
-  const int OH = (H + stride - 1) / stride, OW = (W + stride - 1) / stride;
+  const int OH = slu_strided_out(H, stride), OW = slu_strided_out(W, stride);
   const int rows = dwse_rows(W, OH, OW, stride);
   return rows <= 0 ? 0 : (OH + rows - 1) / rows;
 }
@@ -158,7 +158,7 @@ extern "C" int slu_dwconv3x3_se_fwd(const float* x, const float* w, const float*
                                     slu_stream_t stream) {
   if (!x || !w || !bias || !y || !psum || N <= 0 || C <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2)) return SLU_EINVAL;
   if (N > 65535 || C > 65535 || (long long)H * W >= 0x7fffffffLL) return SLU_EUNSUPPORTED;
-  const int OH = (H + stride - 1) / stride, OW = (W + stride - 1) / stride;      // floor((H + 2 - 3) / stride) + 1
+  const int OH = slu_strided_out(H, stride), OW = slu_strided_out(W, stride);
   const int rows = dwse_rows(W, OH, OW, stride);
   if (rows <= 0) return SLU_EUNSUPPORTED;      // three input rows do not fit the LDS budget
   const int T = (OH + rows - 1) / rows;

@@ -13,9 +13,9 @@
 //     output, in (c, tap) order).
 //     The mean: wave_sum per output channel, one LDS slot per wave, the four slots added in wave order, one float per (image, channel, tile) --
 //     no atomics, so two runs give the same bits; the gate (slu_regnet_se_gate, se_gate.hip) adds the tiles in tile order.
-//   regnet_sample2_kernel                y = cat(src0[:, coff0 : coff0 + c0], src1)[:, :, ::2, ::2]: the input of a stride-2 block's 1x1 / stride-2
-//                                        projection, with the meta injection, in one pass that reads a quarter of the input.
-#include "pixel_common.h"
+//   regnet_sample2_kernel                y = in[:, :, ::2, ::2] of a slu_cat2: the input of a stride-2 block's 1x1 / stride-2 projection, with the
+//                                        meta injection, in one pass that reads a quarter of the input.
+#include "encoder_unit.h"
 
 namespace {
 
@@ -91,7 +91,7 @@ __global__ __launch_bounds__(256) void regnet_sample2_kernel(const float* __rest
   const size_t total = (size_t)N * C * OH * OW;
   PIX_GRID_STRIDE(e, total) {
     const PixXYCN o = pix_xycn(e, OW, OH, C);
-    const float* p = o.c < c0 ? s0 + o.n * (size_t)bs0 + (size_t)o.c * H * W : s1 + o.n * (size_t)bs1 + (size_t)(o.c - c0) * H * W;
+    const float* p = CAT2_PLANE(o.c, c0, s0 + o.n * (size_t)bs0, s1 + o.n * (size_t)bs1, H * W);
     y[e] = p[(size_t)(2 * o.y) * W + 2 * o.x];
   }
 }
@@ -130,16 +130,16 @@ int launch_gconv_s(int stride, const float* x, const float* wg, const float* bia
 extern "C" int slu_regnet_gconv_tiles(int H, int W, int stride) {
   if (H <= 0 || W <= 0 || (stride != 1 && stride != 2)) return 0;
   int tx;
-  return rg_tiles((H + stride - 1) / stride, (W + stride - 1) / stride, tx);
+  return rg_tiles(slu_strided_out(H, stride), slu_strided_out(W, stride), tx);
 }
 
 extern "C" int slu_regnet_gconv_fwd(const float* x, int ct, int coff, const float* wg, const float* bias, float* y, float* psum, int N, int C, int gw,
                                     int H, int W, int stride, slu_stream_t stream) {
-  if (!x || !wg || !bias || !y || !psum || N <= 0 || C <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2)) return SLU_EINVAL;
-  if (coff < 0 || ct <= 0 || coff + C > ct) return SLU_EINVAL;
+  const slu_cat2 in = {x, nullptr, ct, coff, C, 0, 0};      // one source: the kernel reads x alone
+  if (!wg || !bias || !y || !psum || (stride != 1 && stride != 2) || slu_cat2_check(in, N, H, W)) return SLU_EINVAL;
   if ((gw != 8 && gw != 16 && gw != 24) || C % gw) return SLU_EUNSUPPORTED;
-  if (N > 65535 || C / gw > 65535 || (long long)H * W >= 0x7fffffffLL) return SLU_EUNSUPPORTED;
-  const int OH = (H + stride - 1) / stride, OW = (W + stride - 1) / stride;      // floor((H + 2 - 3) / stride) + 1
+  if (C / gw > 65535 || slu_unit_grid_check(N, H, W)) return SLU_EUNSUPPORTED;
+  const int OH = slu_strided_out(H, stride), OW = slu_strided_out(W, stride);
   int tx;
   if (rg_tiles(OH, OW, tx) <= 0) return SLU_EUNSUPPORTED;
   const size_t HW = (size_t)H * W;
@@ -151,13 +151,7 @@ extern "C" int slu_regnet_gconv_fwd(const float* x, int ct, int coff, const floa
   return launch_gconv_s<24>(stride, xs, wg, bias, y, psum, bsx, N, C, H, W, OH, OW, st);
 }
 
-extern "C" int slu_regnet_sample2(const float* src0, int ct0, int coff0, int c0, const float* src1, int ct1, int c1, float* y, int N, int H, int W,
-                                  slu_stream_t stream) {
-  if (!src0 || !y || N <= 0 || H <= 0 || W <= 0 || c0 <= 0 || ct0 <= 0 || coff0 < 0 || coff0 + c0 > ct0) return SLU_EINVAL;
-  if (src1 ? (c1 <= 0 || ct1 < c1) : c1 != 0) return SLU_EINVAL;
-  const int OH = (H + 1) / 2, OW = (W + 1) / 2;
-  const size_t HW = (size_t)H * W, total = (size_t)N * (c0 + c1) * OH * OW;
-  hipLaunchKernelGGL(regnet_sample2_kernel, dim3(slu_grid_1d(total, 16384)), dim3(256), 0, slu_stream(stream), src0 + (size_t)coff0 * HW, src1,
-                     (long long)ct0 * HW, (long long)ct1 * HW, c0, c0 + c1, N, H, W, OH, OW, y);
-  SLU_CHECK_LAUNCH();
+extern "C" int slu_regnet_sample2(const slu_cat2* in, float* y, int N, int H, int W, slu_stream_t stream) {
+  if (!in || !y || slu_cat2_check(*in, N, H, W)) return SLU_EINVAL;
+  return slu_cat2_resample(regnet_sample2_kernel, in, y, N, H, W, slu_strided_out(H, 2), slu_strided_out(W, 2), slu_stream(stream));
 }

@@ -13,11 +13,10 @@
 //                                      v_mfma_f32_32x32x2_f32 (exact fp32: a k-ordered fmaf chain) with A from the packed weight image (L2) and B
 //                                      from LDS.  A chunk's A operands are loaded in one batch ahead of its barriers and the next chunk's depthwise
 //                                      loads are issued before the current chunk's MFMAs, so a chunk pays about one memory round trip.  On small
-//                                      maps the output blocks are split over up to 4 workgroups per pixel tile (blockIdx.z) to fill the CUs.
-//   shuffle_tail_pack_kernel           [Co][C] fp32 -> [ceil(Co/32)][16 ceil(C/32)][64]: the A operand of (block m, K-step k2) for lane l is
-//                                      W[32 m + (l & 31)][2 k2 + (l >> 5)], zero outside the matrix.
+//                                      maps the output blocks are split over workgroups (blockIdx.z, slu_cu_fill_split) to fill the CUs.
+//   shuffle_tail_pack_kernel           [Co][C] fp32 -> the A-fragment image (encoder_unit.h) with K-chunk TAIL_KC.
 // The weight is streamed from L2 in K-chunks (the 488 x 488 one is 952 KB).  No atomics: results are bit-identical run to run.
-#include "slu_common.h"
+#include "encoder_unit.h"
 
 namespace {
 
@@ -27,10 +26,10 @@ constexpr int TAIL_LDW = 96;      // LDS row stride in floats: rows k and k + 1 
 constexpr int TAIL_MAX_CO = 512;  // 16 output blocks: UPW <= 8
 
 struct TailArgs {
-  const float* src0;      // first channel read of source 0
-  const float* src1;      // source 1 or nullptr
-  long long bs0, bs1;     // floats between two images of each source tensor
-  int c0, C;              // channels taken from source 0, channels in all
+  const float* src0;      // the fields of Cat2Args (slu_cat2_fill), flat: as a member struct the kernels' argument loads change
+  const float* src1;
+  long long bs0, bs1;
+  int c0, C;
   int H, W, Ho, Wo;
   int Co, parity, nmblk, nchunks;
   int mps;                // 32-channel output blocks per workgroup: blockIdx.z owns blocks [z mps, (z + 1) mps)
@@ -48,7 +47,7 @@ __device__ __forceinline__ void tail_depthwise(const TailArgs& a, int n, int q, 
     const int c = q * TAIL_KC + w + 4 * i;      // wave-uniform
     float v = 0.0f;
     if (c < a.C) {
-      const float* sp = c < a.c0 ? a.src0 + (size_t)n * a.bs0 + (size_t)c * HW : a.src1 + (size_t)n * a.bs1 + (size_t)(c - a.c0) * HW;
+      const float* sp = CAT2_PLANE(c, a.c0, a.src0 + (size_t)n * a.bs0, a.src1 + (size_t)n * a.bs1, HW);
       const float* wc = a.wdw + (size_t)c * 9;
       v = a.bdw[c];
 #pragma unroll
@@ -159,24 +158,13 @@ __global__ __launch_bounds__(256) void shuffle_tail_kernel(const TailArgs a) {
   });
 }
 
-__global__ __launch_bounds__(256) void shuffle_tail_pack_kernel(const float* __restrict__ w, int co, int c, int kp2, size_t total, float* __restrict__ out) {
-  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-    const int l = (int)(e & 63);
-    const size_t r = e >> 6;
-    const int k2 = (int)(r % kp2);
-    const int m = (int)(r / kp2);
-    const int row = m * 32 + (l & 31), k = 2 * k2 + (l >> 5);
-    out[e] = (row < co && k < c) ? w[(size_t)row * c + k] : 0.0f;
-  }
+__global__ __launch_bounds__(256) void shuffle_tail_pack_kernel(const float* __restrict__ w, int co, int c, size_t total, float* __restrict__ out) {
+  PIX_GRID_STRIDE(e, total) out[e] = afrag_element(w, e, co, c, TAIL_KC, 1);
 }
 
 template <int STRIDE>
 int launch_tail(TailArgs& a, int N, hipStream_t st) {
-  // Small maps leave most of the 256 CUs idle with one workgroup per 64 pixels: split the output blocks over up to 4 workgroups per pixel tile
-  // (each recomputes the depthwise chunk, which is cheap next to an idle CU) until there are about as many workgroups as CUs.
-  const long long tiles = (long long)((a.Ho * a.Wo + TAIL_PIX - 1) / TAIL_PIX) * N;
-  int split = 1;
-  while (split < 4 && tiles * split < 256 && a.nmblk >= 2 * split) split *= 2;
+  const int split = slu_cu_fill_split((long long)((a.Ho * a.Wo + TAIL_PIX - 1) / TAIL_PIX) * N, a.nmblk);      // each z recomputes the depthwise chunk
   a.mps = (a.nmblk + split - 1) / split;
   const dim3 grid((unsigned)((a.Ho * a.Wo + TAIL_PIX - 1) / TAIL_PIX), (unsigned)N, (unsigned)((a.nmblk + a.mps - 1) / a.mps)), block(256);
   const int units = (a.mps + 1) / 2;
@@ -191,35 +179,30 @@ int launch_tail(TailArgs& a, int N, hipStream_t st) {
 
 extern "C" size_t slu_shuffle_tail_packed_floats(int co, int c) {
   if (co <= 0 || c <= 0 || co > TAIL_MAX_CO) return 0;
-  return (size_t)((co + 31) / 32) * ((c + TAIL_KC - 1) / TAIL_KC) * (TAIL_KC / 2) * 64;
+  return afrag_floats(co, c, TAIL_KC, 1);
 }
 
 extern "C" int slu_shuffle_tail_pack(const float* w, int co, int c, float* out, slu_stream_t stream) {
   if (!w || !out || co <= 0 || c <= 0) return SLU_EINVAL;
   const size_t total = slu_shuffle_tail_packed_floats(co, c);
   if (total == 0) return SLU_EUNSUPPORTED;
-  const int kp2 = (c + TAIL_KC - 1) / TAIL_KC * (TAIL_KC / 2);
-  hipLaunchKernelGGL(shuffle_tail_pack_kernel, dim3(slu_grid_1d(total, 4096)), dim3(256), 0, slu_stream(stream), w, co, c, kp2, total, out);
+  hipLaunchKernelGGL(shuffle_tail_pack_kernel, dim3(slu_grid_1d(total, 4096)), dim3(256), 0, slu_stream(stream), w, co, c, total, out);
   SLU_CHECK_LAUNCH();
 }
 
 extern "C" int slu_shuffle_tail_fwd(const slu_shuffle_tail_desc* d, slu_stream_t stream) {
-  if (!d || !d->src0 || !d->wdw || !d->bdw || !d->wpack || !d->bpw || !d->out) return SLU_EINVAL;
-  if (d->N <= 0 || d->H <= 0 || d->W <= 0 || d->Co <= 0 || d->c0 <= 0 || d->ct0 <= 0 || d->coff0 < 0 || d->coff0 + d->c0 > d->ct0) return SLU_EINVAL;
-  if ((d->parity != 0 && d->parity != 1) || (d->src1 ? (d->c1 <= 0 || d->ct1 < d->c1) : d->c1 != 0)) return SLU_EINVAL;
-  if (d->pass && (d->pass_ct < d->Co || d->parity != 1)) return SLU_EINVAL;
+  if (!d || !d->wdw || !d->bdw || !d->wpack || !d->bpw || !d->out || d->Co <= 0 || slu_cat2_check(d->in, d->N, d->H, d->W)) return SLU_EINVAL;
+  if ((d->parity != 0 && d->parity != 1) || (d->pass && (d->pass_ct < d->Co || d->parity != 1))) return SLU_EINVAL;
   if (d->stride != 1 && d->stride != 2) return SLU_EUNSUPPORTED;
-  if (d->Co > TAIL_MAX_CO || d->N > 65535 || (long long)d->H * d->W >= 0x7fffffffLL) return SLU_EUNSUPPORTED;
+  if (d->Co > TAIL_MAX_CO || slu_unit_grid_check(d->N, d->H, d->W)) return SLU_EUNSUPPORTED;
   TailArgs a;
-  const long long HW = (long long)d->H * d->W;
-  a.Ho = (d->H + d->stride - 1) / d->stride;
-  a.Wo = (d->W + d->stride - 1) / d->stride;
-  a.src0 = d->src0 + (size_t)d->coff0 * HW;
-  a.src1 = d->src1;
-  a.bs0 = (long long)d->ct0 * HW;
-  a.bs1 = (long long)d->ct1 * HW;
-  a.c0 = d->c0;
-  a.C = d->c0 + d->c1;
+  const size_t HW = (size_t)d->H * d->W;
+  a.Ho = slu_strided_out(d->H, d->stride);
+  a.Wo = slu_strided_out(d->W, d->stride);
+  const size_t HWo = (size_t)a.Ho * a.Wo, nout = (size_t)d->N * 2 * d->Co * HWo;
+  if (slu_cat2_overlaps(d->in, d->N, HW, d->out, nout) || (d->pass && slu_overlaps(d->out, nout, d->pass, (size_t)d->N * d->pass_ct * HWo)))
+    return SLU_EINVAL;
+  slu_cat2_fill(a, d->in, HW);
   a.H = d->H; a.W = d->W;
   a.Co = d->Co; a.parity = d->parity;
   a.nmblk = (d->Co + 31) / 32;

@@ -46,6 +46,30 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
+def _req_shapes(*items) -> None:
+    """(tensor, name, shape) ...: _req, and the shape."""
+    for t, nme, shp in items:
+        _req(t, nme)
+        if tuple(t.shape) != shp:
+            raise RuntimeError(f"{nme}: expected {shp}, got {tuple(t.shape)}")
+
+
+def _overlaps(a: torch.Tensor, b: torch.Tensor) -> bool:
+    return a.data_ptr() < b.data_ptr() + b.numel() * b.element_size() and b.data_ptr() < a.data_ptr() + a.numel() * a.element_size()
+
+
+def _out_or_new(fn: str, out: Optional[torch.Tensor], shape, inputs) -> torch.Tensor:
+    """A new float32 tensor next to inputs[0], or the caller's `out`: checked, of this shape, overlapping none of `inputs` (None entries skipped)."""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=inputs[0].device)
+    _req(out, "out")
+    if tuple(out.shape) != tuple(shape):
+        raise RuntimeError(f"out: expected {tuple(shape)}, got {tuple(out.shape)}")
+    if any(t is not None and _overlaps(out, t) for t in inputs):
+        raise RuntimeError(f"{fn}: out must not overlap an input")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # convolution
 # ------------------------------------------------------------------------------------------------
@@ -1868,10 +1892,7 @@ def se_scale(x: torch.Tensor, w1: torch.Tensor, b1: Optional[torch.Tensor], w2: 
     _req(x, "x")
     n, c, h, w = x.shape
     s = w1.shape[0]
-    for t, nme, shp in ((w1, "w1", (s, c)), (w2, "w2", (c, s))):
-        _req(t, nme)
-        if tuple(t.shape) != shp:
-            raise RuntimeError(f"se_scale: {nme} expected {shp}, got {tuple(t.shape)}")
+    _req_shapes((w1, "w1", (s, c)), (w2, "w2", (c, s)))
     lib = _lib.load()
     avg = torch.empty((n, c), dtype=torch.float32, device=x.device)
     check(lib.slu_global_avgpool(x.data_ptr(), avg.data_ptr(), n, c, h * w, _stream()), "slu_global_avgpool")
@@ -1924,10 +1945,7 @@ def _se_gate_from_psum(fn: str, entry: str, psum, count, w1, b1, w2, b2, limit, 
     if w1.dim() != 2 or w1.shape[1] != c or w1.shape[0] == 0:
         raise RuntimeError(f"w1: expected [S, {c}], got {tuple(w1.shape)}")
     s = w1.shape[0]
-    for tns, nme, shp in ((b1, "b1", (s,)), (w2, "w2", (c, s)), (b2, "b2", (c,))):
-        _req(tns, nme)
-        if tuple(tns.shape) != shp:
-            raise RuntimeError(f"{nme}: expected {shp}, got {tuple(tns.shape)}")
+    _req_shapes((b1, "b1", (s,)), (w2, "w2", (c, s)), (b2, "b2", (c,)))
     refusal = limit(c, s)
     if refusal:
         raise RuntimeError(f"{fn}: {refusal}")
@@ -1947,6 +1965,35 @@ def se_gate_psum(psum: torch.Tensor, count: int, w1: torch.Tensor, b1: torch.Ten
         if c > SE_GATE_MAX_C or s > SE_GATE_MAX_S:
             return f"C = {c}, S = {s} is outside the kernel's C <= {SE_GATE_MAX_C}, S <= {SE_GATE_MAX_S}"
     return _se_gate_from_psum("se_gate_psum", "slu_se_gate_psum", psum, count, w1, b1, w2, b2, limit, False)
+
+
+# ------------------------------------------------------------------------------------------------
+# The two-source input of the encoder unit kernels (slu_cat2, csrc/encoder_unit.h)
+# ------------------------------------------------------------------------------------------------
+def _channel_range(t: torch.Tensor, name: str, coff: int, cuse: int):
+    """(coff, c) of t[:, coff:coff + cuse] of an NCHW tensor (cuse = 0: every channel from coff on), checked."""
+    _req(t, name)
+    if t.dim() != 4:
+        raise RuntimeError(f"{name}: expected NCHW, got {tuple(t.shape)}")
+    ct = t.shape[1]
+    coff, cuse = int(coff), int(cuse)
+    c = cuse if cuse else ct - coff
+    if coff < 0 or c <= 0 or coff + c > ct:
+        raise RuntimeError(f"{name}: channel range [{coff}, {coff + c}) is outside the tensor's {ct} channels")
+    return coff, c
+
+
+def _two_sources(src: torch.Tensor, coff: int, cuse: int, src2: Optional[torch.Tensor]):
+    """cat(src[:, coff:coff + cuse], src2) (cuse = 0: every channel from coff on), checked: (its _lib.Cat2, (n, h, w, c))."""
+    coff, c0 = _channel_range(src, "src", coff, cuse)
+    n, ct0, h, w = src.shape
+    ct1 = 0
+    if src2 is not None:
+        _req(src2, "src2")
+        if src2.dim() != 4 or (src2.shape[0], src2.shape[2], src2.shape[3]) != (n, h, w) or src2.shape[1] == 0:
+            raise RuntimeError(f"src2: expected [{n}, > 0, {h}, {w}], got {tuple(src2.shape)}")
+        ct1 = src2.shape[1]
+    return _lib.Cat2(src.data_ptr(), _ptr(src2), ct0, coff, c0, ct1, ct1), (n, h, w, c0 + ct1)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1976,39 +2023,16 @@ def shuffle_tail(src: torch.Tensor, wdw: torch.Tensor, bdw: torch.Tensor, wpack:
     src2 optional), wdw [C, 9], bdw [C], wpack = pack_shuffle_tail_weight(W_pw [co, C]), bpw [co].  out [N, 2 co, Ho, Wo] is allocated when not
     given; without `passthrough` its channels of the other parity are left as they were.  The depthwise result stays on chip.  The pointwise
     product is the exact-fp32 MFMA under every conv precision ('fp32' and 'f16x3' alike): the kernel is bandwidth-bound, split products buy nothing."""
-    _req(src, "src")
-    if src.dim() != 4:
-        raise RuntimeError(f"src: expected NCHW, got {tuple(src.shape)}")
-    n, ct0, h, w = src.shape
-    coff, cuse = int(coff), int(cuse)
-    c0 = cuse if cuse else ct0 - coff
-    if coff < 0 or c0 <= 0 or coff + c0 > ct0:
-        raise RuntimeError(f"src: channel range [{coff}, {coff + c0}) is outside the tensor's {ct0} channels")
-    ct1 = c1 = 0
-    if src2 is not None:
-        _req(src2, "src2")
-        if src2.dim() != 4 or (src2.shape[0], src2.shape[2], src2.shape[3]) != (n, h, w):
-            raise RuntimeError(f"src2: expected [{n}, *, {h}, {w}], got {tuple(src2.shape)}")
-        ct1 = c1 = src2.shape[1]
-    c = c0 + c1
+    cat, (n, h, w, c) = _two_sources(src, coff, cuse, src2)
     if stride not in (1, 2) or parity not in (0, 1) or co <= 0:
         raise RuntimeError("shuffle_tail: stride must be 1 or 2, parity 0 or 1, co positive")
     lib = _lib.load()
-    for t, nme, shp in ((wdw, "wdw", (c, 9)), (bdw, "bdw", (c,)), (bpw, "bpw", (co,))):
-        _req(t, nme)
-        if tuple(t.shape) != shp:
-            raise RuntimeError(f"{nme}: expected {shp}, got {tuple(t.shape)}")
+    _req_shapes((wdw, "wdw", (c, 9)), (bdw, "bdw", (c,)), (bpw, "bpw", (co,)))
     _req(wpack, "wpack")
     want = lib.slu_shuffle_tail_packed_floats(co, c)
     if want and wpack.numel() != want:
         raise RuntimeError(f"wpack: {wpack.numel()} floats does not match Co={co} C={c}")
     ho, wo = (h + stride - 1) // stride, (w + stride - 1) // stride
-    if out is None:
-        out = torch.empty((n, 2 * co, ho, wo), dtype=torch.float32, device=src.device)
-    else:
-        _req(out, "out")
-        if tuple(out.shape) != (n, 2 * co, ho, wo):
-            raise RuntimeError(f"out: expected {(n, 2 * co, ho, wo)}, got {tuple(out.shape)}")
     d = _lib.ShuffleTailDesc()
     if passthrough is not None:
         _req(passthrough, "passthrough")
@@ -2017,8 +2041,8 @@ def shuffle_tail(src: torch.Tensor, wdw: torch.Tensor, bdw: torch.Tensor, wpack:
         if parity != 1:
             raise RuntimeError("shuffle_tail: the pass-through half takes the even channels, so parity must be 1")
         d.pass_, d.pass_ct = passthrough.data_ptr(), passthrough.shape[1]
-    d.src0, d.src1 = src.data_ptr(), _ptr(src2)
-    d.ct0, d.coff0, d.c0, d.ct1, d.c1 = ct0, coff, c0, ct1, c1
+    out = _out_or_new("shuffle_tail", out, (n, 2 * co, ho, wo), (src, src2, passthrough))
+    d.in_ = cat
     d.N, d.H, d.W, d.stride, d.Co, d.parity = n, h, w, int(stride), int(co), int(parity)
     d.wdw, d.bdw, d.wpack, d.bpw, d.out = wdw.data_ptr(), bdw.data_ptr(), wpack.data_ptr(), bpw.data_ptr(), out.data_ptr()
     check(lib.slu_shuffle_tail_fwd(C.byref(d), _stream()), "slu_shuffle_tail_fwd")
@@ -2028,29 +2052,6 @@ def shuffle_tail(src: torch.Tensor, wdw: torch.Tensor, bdw: torch.Tensor, wpack:
 # ------------------------------------------------------------------------------------------------
 # SqueezeNet Fire module and ceil-mode max-pool (csrc/fire_unit.hip)
 # ------------------------------------------------------------------------------------------------
-def _two_sources(src: torch.Tensor, coff: int, cuse: int, src2: Optional[torch.Tensor]):
-    """(n, h, w, ct0, coff, c0, ct1, c1) of cat(src[:, coff:coff + cuse], src2) (cuse = 0: every channel from coff on), checked."""
-    _req(src, "src")
-    if src.dim() != 4:
-        raise RuntimeError(f"src: expected NCHW, got {tuple(src.shape)}")
-    n, ct0, h, w = src.shape
-    coff, cuse = int(coff), int(cuse)
-    c0 = cuse if cuse else ct0 - coff
-    if coff < 0 or c0 <= 0 or coff + c0 > ct0:
-        raise RuntimeError(f"src: channel range [{coff}, {coff + c0}) is outside the tensor's {ct0} channels")
-    ct1 = c1 = 0
-    if src2 is not None:
-        _req(src2, "src2")
-        if src2.dim() != 4 or (src2.shape[0], src2.shape[2], src2.shape[3]) != (n, h, w) or src2.shape[1] == 0:
-            raise RuntimeError(f"src2: expected [{n}, > 0, {h}, {w}], got {tuple(src2.shape)}")
-        ct1 = c1 = src2.shape[1]
-    return n, h, w, ct0, coff, c0, ct1, c1
-
-
-def _overlaps(a: torch.Tensor, b: torch.Tensor) -> bool:
-    return a.data_ptr() < b.data_ptr() + b.numel() * b.element_size() and b.data_ptr() < a.data_ptr() + a.numel() * a.element_size()
-
-
 def pack_fire_weight(wsq: torch.Tensor, w1: torch.Tensor, w3: torch.Tensor) -> torch.Tensor:
     """wsq [S, Cin], w1 [E1, S], w3 [E3, S, 3, 3] fp32 -> the MFMA A-fragment images slu_fire_fwd streams (re-run after every weight update)."""
     for t, nme in ((wsq, "wsq"), (w1, "w1"), (w3, "w3")):
@@ -2076,7 +2077,7 @@ def fire(src: torch.Tensor, wpack: torch.Tensor, bsq: torch.Tensor, b1: torch.Te
     the squeeze map stays in LDS.  src is cat(src[:, coff:coff + cuse], src2) (cuse = 0: every channel from coff on; src2 optional),
     wpack = pack_fire_weight(wsq, w1, w3), bsq [S], b1 [E1], b3 [E3].  out [N, E1 + E3, H, W] is allocated when not given and must not overlap an
     input.  Every product is the exact-fp32 MFMA under every conv precision ('fp32' and 'f16x3' alike)."""
-    n, h, w, ct0, coff, c0, ct1, c1 = _two_sources(src, coff, cuse, src2)
+    cat, (n, h, w, cin) = _two_sources(src, coff, cuse, src2)
     for t, nme in ((bsq, "bsq"), (b1, "b1"), (b3, "b3")):
         _req(t, nme)
         if t.dim() != 1 or t.numel() == 0:
@@ -2084,22 +2085,14 @@ def fire(src: torch.Tensor, wpack: torch.Tensor, bsq: torch.Tensor, b1: torch.Te
     s, e1, e3 = bsq.numel(), b1.numel(), b3.numel()
     lib = _lib.load()
     _req(wpack, "wpack")
-    want = lib.slu_fire_packed_floats(c0 + c1, s, e1, e3)
+    want = lib.slu_fire_packed_floats(cin, s, e1, e3)
     if want == 0:
-        raise RuntimeError(f"fire: Cin={c0 + c1} S={s} E1={e1} E3={e3} is outside what slu_fire_fwd takes (S <= 64, E1 and E3 <= 256)")
+        raise RuntimeError(f"fire: Cin={cin} S={s} E1={e1} E3={e3} is outside what slu_fire_fwd takes (S <= 64, E1 and E3 <= 256)")
     if wpack.numel() != want:
-        raise RuntimeError(f"wpack: {wpack.numel()} floats does not match Cin={c0 + c1} S={s} E1={e1} E3={e3}")
-    if out is None:
-        out = torch.empty((n, e1 + e3, h, w), dtype=torch.float32, device=src.device)
-    else:
-        _req(out, "out")
-        if tuple(out.shape) != (n, e1 + e3, h, w):
-            raise RuntimeError(f"out: expected {(n, e1 + e3, h, w)}, got {tuple(out.shape)}")
-        if _overlaps(out, src) or (src2 is not None and _overlaps(out, src2)):
-            raise RuntimeError("fire: out must not overlap an input")
+        raise RuntimeError(f"wpack: {wpack.numel()} floats does not match Cin={cin} S={s} E1={e1} E3={e3}")
+    out = _out_or_new("fire", out, (n, e1 + e3, h, w), (src, src2))
     d = _lib.FireDesc()
-    d.src0, d.src1 = src.data_ptr(), _ptr(src2)
-    d.ct0, d.coff0, d.c0, d.ct1, d.c1 = ct0, coff, c0, ct1, c1
+    d.in_ = cat
     d.N, d.H, d.W, d.S, d.E1, d.E3 = n, h, w, s, e1, e3
     d.wpack, d.bsq, d.b1, d.b3, d.out = wpack.data_ptr(), bsq.data_ptr(), b1.data_ptr(), b3.data_ptr(), out.data_ptr()
     check(lib.slu_fire_fwd(C.byref(d), _stream()), "slu_fire_fwd")
@@ -2108,12 +2101,11 @@ def fire(src: torch.Tensor, wpack: torch.Tensor, bsq: torch.Tensor, b1: torch.Te
 
 def maxpool3s2_ceil(src: torch.Tensor, coff: int = 0, cuse: int = 0, src2: Optional[torch.Tensor] = None) -> torch.Tensor:
     """nn.MaxPool2d(3, 2, padding=0, ceil_mode=True) of cat(src[:, coff:coff + cuse], src2) -> [N, C, ceil((H - 3) / 2) + 1, ceil((W - 3) / 2) + 1]."""
-    n, h, w, ct0, coff, c0, ct1, c1 = _two_sources(src, coff, cuse, src2)
+    cat, (n, h, w, c) = _two_sources(src, coff, cuse, src2)
     if h < 3 or w < 3:
         raise RuntimeError(f"maxpool3s2_ceil: H and W must be at least 3, got {h} x {w}")
-    y = torch.empty((n, c0 + c1, (h - 2) // 2 + 1, (w - 2) // 2 + 1), dtype=torch.float32, device=src.device)
-    check(_lib.load().slu_maxpool3s2_ceil_fwd(src.data_ptr(), ct0, coff, c0, _ptr(src2), ct1, c1, y.data_ptr(), n, h, w, _stream()),
-          "slu_maxpool3s2_ceil_fwd")
+    y = torch.empty((n, c, (h - 2) // 2 + 1, (w - 2) // 2 + 1), dtype=torch.float32, device=src.device)
+    check(_lib.load().slu_maxpool3s2_ceil_fwd(C.byref(cat), y.data_ptr(), n, h, w, _stream()), "slu_maxpool3s2_ceil_fwd")
     return y
 
 
@@ -2141,35 +2133,19 @@ def regnet_gconv(x: torch.Tensor, wg: torch.Tensor, bias: torch.Tensor, stride: 
     wg = pack_regnet_gconv_weight(w, gw) (eval BatchNorm folded in by the caller), cuse = 0: every channel from coff on.  Returns (y [N, C, Ho, Wo],
     psum [N, C, T]): psum holds the per-tile sums of y, which regnet_se_gate turns into the SqueezeExcitation's mean without reading y back.
     Exact fp32 under every conv precision; bit-identical run to run."""
-    _req(x, "x")
-    if x.dim() != 4:
-        raise RuntimeError(f"x: expected NCHW, got {tuple(x.shape)}")
+    coff, c = _channel_range(x, "x", coff, cuse)
     n, ct, h, w = x.shape
-    coff, cuse = int(coff), int(cuse)
-    c = cuse if cuse else ct - coff
-    if coff < 0 or c <= 0 or coff + c > ct:
-        raise RuntimeError(f"x: channel range [{coff}, {coff + c}) is outside the tensor's {ct} channels")
     _req(wg, "wg")
     if wg.dim() != 4 or wg.shape[1] != wg.shape[3] or wg.shape[2] != 9 or wg.shape[1] not in REGNET_GROUP_WIDTHS:
         raise RuntimeError(f"wg: expected [G, gw, 9, gw] with gw in {REGNET_GROUP_WIDTHS}, got {tuple(wg.shape)}")
     gw = wg.shape[1]
     if wg.shape[0] * gw != c:
         raise RuntimeError(f"wg: {wg.shape[0]} groups of {gw} do not make the {c} input channels")
-    _req(bias, "bias")
-    if tuple(bias.shape) != (c,):
-        raise RuntimeError(f"bias: expected ({c},), got {tuple(bias.shape)}")
+    _req_shapes((bias, "bias", (c,)))
     if stride not in (1, 2):
         raise RuntimeError("regnet_gconv: stride must be 1 or 2")
     lib = _lib.load()
-    ho, wo = (h + stride - 1) // stride, (w + stride - 1) // stride
-    if out is None:
-        out = torch.empty((n, c, ho, wo), dtype=torch.float32, device=x.device)
-    else:
-        _req(out, "out")
-        if tuple(out.shape) != (n, c, ho, wo):
-            raise RuntimeError(f"out: expected {(n, c, ho, wo)}, got {tuple(out.shape)}")
-        if _overlaps(out, x):
-            raise RuntimeError("regnet_gconv: out must not overlap the input")
+    out = _out_or_new("regnet_gconv", out, (n, c, (h + stride - 1) // stride, (w + stride - 1) // stride), (x,))
     t = lib.slu_regnet_gconv_tiles(h, w, int(stride))
     if t <= 0:
         raise RuntimeError(f"regnet_gconv: a {h} x {w} map is outside what slu_regnet_gconv_fwd takes")
@@ -2191,7 +2167,7 @@ def regnet_se_gate(psum: torch.Tensor, count: int, w1: torch.Tensor, b1: torch.T
 
 def regnet_sample2(src: torch.Tensor, coff: int = 0, cuse: int = 0, src2: Optional[torch.Tensor] = None) -> torch.Tensor:
     """cat(src[:, coff:coff + cuse], src2)[:, :, ::2, ::2] -> [N, C, ceil(H / 2), ceil(W / 2)]: the input of a 1x1 / stride-2 projection."""
-    n, h, w, ct0, coff, c0, ct1, c1 = _two_sources(src, coff, cuse, src2)
-    y = torch.empty((n, c0 + c1, (h + 1) // 2, (w + 1) // 2), dtype=torch.float32, device=src.device)
-    check(_lib.load().slu_regnet_sample2(src.data_ptr(), ct0, coff, c0, _ptr(src2), ct1, c1, y.data_ptr(), n, h, w, _stream()), "slu_regnet_sample2")
+    cat, (n, h, w, c) = _two_sources(src, coff, cuse, src2)
+    y = torch.empty((n, c, (h + 1) // 2, (w + 1) // 2), dtype=torch.float32, device=src.device)
+    check(_lib.load().slu_regnet_sample2(C.byref(cat), y.data_ptr(), n, h, w, _stream()), "slu_regnet_sample2")
     return y

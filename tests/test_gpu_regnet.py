@@ -6,6 +6,7 @@ F.conv2d(groups=...); gate -- 1e-5 absolute (outputs lie in (0, 1)); one block -
 and at most 1e-3 of the pixels with another argmax, S = max(1, max|want|), under 'fp32' and 'f16x3' (the CPU fp32 run of the restatement is
 within 2e-6 S and flips no pixel on these fixtures: test_regnet_cpu.py::test_fixture_conditions)."""
 import copy
+import ctypes
 
 import numpy as np
 import pytest
@@ -92,7 +93,7 @@ def test_grouped_conv_refusals(cuda):
     assert lib.slu_regnet_gconv_fwd(x.data_ptr(), 48, 0, wg.data_ptr(), b.data_ptr(), out.data_ptr(), None, 1, 48, 24, 4, 8, 1, None) == -1
     assert lib.slu_regnet_gconv_fwd(x.data_ptr(), 48, 8, wg.data_ptr(), b.data_ptr(), out.data_ptr(), psum.data_ptr(), 1, 48, 24, 4, 8, 1, None) == -1
     assert lib.slu_regnet_se_gate(None, 1, 1.0, wg.data_ptr(), b.data_ptr(), wg.data_ptr(), b.data_ptr(), out.data_ptr(), None, 1, 48, 8, None) == -1
-    assert lib.slu_regnet_sample2(None, 48, 0, 48, None, 0, 0, out.data_ptr(), 1, 4, 8, None) == -1
+    assert lib.slu_regnet_sample2(ctypes.byref(_lib.Cat2(None, None, 48, 0, 48, 0, 0)), out.data_ptr(), 1, 4, 8, None) == -1
     torch.cuda.synchronize()
     assert bool((out == 7.0).all())                                                         # nothing was launched
     with pytest.raises(RuntimeError):

@@ -171,7 +171,7 @@ def test_ceil_pool_two_sources_and_refusals(cuda):
     with pytest.raises(RuntimeError):
         ops.maxpool3s2_ceil(torch.zeros(1, 2, 2, 8, device=cuda))                            # H = 2
     xd = x.to(cuda)
-    assert _lib.load().slu_maxpool3s2_ceil_fwd(xd.data_ptr(), 5, 0, 5, None, 0, 0, xd.data_ptr(), 2, 2, 48, None) == -1
+    assert _lib.load().slu_maxpool3s2_ceil_fwd(ctypes.byref(_lib.Cat2(xd.data_ptr(), None, 5, 0, 5, 0, 0)), xd.data_ptr(), 2, 2, 48, None) == -1
 
 
 # ---------------- 3. the models ----------------
