@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SLU_ABI_VERSION 44
+#define SLU_ABI_VERSION 45
 
 #define SLU_OK            0
 #define SLU_EINVAL       -1   /* null pointer / non-positive size / inconsistent descriptor   */
@@ -906,6 +906,26 @@ int slu_dwconv3x3_se_fwd(const float* x, const float* w, const float* bias, floa
                          slu_stream_t stream);
 int slu_se_gate_psum(const float* psum, int T, float inv_count, const float* w1, const float* b1, const float* w2, const float* b2, float* scale,
                      int N, int C, int S, slu_stream_t stream);
+
+/* ---- CENet ResNet-34 decoder (baselines/CENet/CENet_ResNet34.py:165-184) ------------------------------------------------------------------
+ * Both use F.interpolate(mode = 'bilinear', align_corners = True): source coordinate = destination * (in - 1) / (out - 1), and 0 where
+ * out == 1 or in == 1; the taps are found from the integer ratio exactly, so in == out returns the input bit for bit.
+ * slu_bilinear_ac_cat: 1 .. 3 sources [N][C_k][h_k][w_k], each interpolated to H x W and written into channels [c_off_k, c_off_k + C_k) of the
+ * dense [N][C_tot][H][W] buffer `out` in ONE launch (the three interpolations of :165-167 and their part of the torch.cat of :170); channels
+ * outside the slices are left as they are.  `srcs` is a HOST array.  Slices that overlap or leave C_tot are SLU_EINVAL.  16-byte stores where
+ * W % 4 == 0 and out is 16-byte aligned, scalar ones otherwise.  N * sum C_k <= 65535, H <= 1048560, sizes below 2^22 with
+ * (out - 1) * (in - 1) < 2^31 per axis: anything else is SLU_EUNSUPPORTED.
+ * slu_bilinear_ac_softmax: y [N][C][H][W] = softmax over C of the interpolation of the logits x [N][C][h][w] to H x W (h == H and w == W: plain
+ * softmax); 1 <= C <= 32 (SLU_EINVAL above), N, H <= 65535.  The model's aux heads run their 1x1 conv on the low-resolution map and
+ * interpolate the logits here: a 1x1 conv commutes with the interpolation because the four weights sum to 1, so the result equals the
+ * reference's order (interpolate, conv, softmax) up to rounding, not bit for bit. */
+typedef struct slu_bilinear_src {   /* HOST struct, 24 bytes */
+  const float* ptr;   /* [N][C][h][w] */
+  int32_t C, h, w;
+  int32_t c_off;      /* first channel of `out` this source is written to */
+} slu_bilinear_src;
+int slu_bilinear_ac_cat(const slu_bilinear_src* srcs, int nsrc, float* out, int N, int C_tot, int H, int W, slu_stream_t stream);
+int slu_bilinear_ac_softmax(const float* x, float* y, int N, int C, int h, int w, int H, int W, slu_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-ABI_VERSION = 44
+ABI_VERSION = 45
 MAX_SRC = 3
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libslu_hip.so")
@@ -127,6 +127,11 @@ class FireDesc(C.Structure):
         ("wpack", C.c_void_p), ("bsq", C.c_void_p), ("b1", C.c_void_p), ("b3", C.c_void_p),
         ("out", C.c_void_p),
     ]
+
+
+class BilinearSrc(C.Structure):
+    """One source of slu_bilinear_ac_cat; 24 bytes."""
+    _fields_ = [("ptr", C.c_void_p), ("C", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("c_off", C.c_int32)]
 
 
 # name -> (restype, argtypes); every symbol include/slu.h declares
@@ -314,6 +319,8 @@ SIGNATURES = {
     "slu_lovasz_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "slu_lovasz_fwd": (C.c_int, [c_f32p, c_i64p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_uint, C.c_void_p, C.c_size_t, c_f32p,
                                  c_f32p, c_f32p, c_stream]),
+    "slu_bilinear_ac_cat": (C.c_int, [C.POINTER(BilinearSrc), C.c_int, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_stream]),
+    "slu_bilinear_ac_softmax": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_stream]),
 }
 
 _lib = None

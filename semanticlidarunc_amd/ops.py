@@ -2171,3 +2171,65 @@ def regnet_sample2(src: torch.Tensor, coff: int = 0, cuse: int = 0, src2: Option
     y = torch.empty((n, c, (h + 1) // 2, (w + 1) // 2), dtype=torch.float32, device=src.device)
     check(_lib.load().slu_regnet_sample2(C.byref(cat), y.data_ptr(), n, h, w, _stream()), "slu_regnet_sample2")
     return y
+
+
+# ------------------------------------------------------------------------------------------------
+# CENet decoder (baselines/CENet/CENet_ResNet34.py:165-184)
+def bilinear_ac_cat(srcs: Sequence[torch.Tensor], size, out: Optional[torch.Tensor] = None, c_offs: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """cat([F.interpolate(s, size=size, mode='bilinear', align_corners=True) for s in srcs], 1) in one launch; 1..3 sources [N, C_k, h_k, w_k].
+    With `out` [N, C_tot, H, W] source k goes to channels [c_offs[k], c_offs[k] + C_k) (default: one after the other from 0) and every other
+    channel keeps its content."""
+    if not 1 <= len(srcs) <= 3:
+        raise RuntimeError(f"bilinear_ac_cat: 1..3 sources supported, got {len(srcs)}")
+    hh, ww = (int(v) for v in size)
+    if hh < 1 or ww < 1:
+        raise RuntimeError("bilinear_ac_cat: size must be positive")
+    n = None
+    for i, s in enumerate(srcs):
+        _req(s, f"srcs[{i}]")
+        if s.dim() != 4 or s.numel() == 0 or (n is not None and s.shape[0] != n):
+            raise RuntimeError(f"srcs[{i}]: expected a non-empty [N, C, h, w] tensor with the batch of srcs[0], got {tuple(s.shape)}")
+        n = s.shape[0]
+    if c_offs is None:
+        c_offs, at = [], 0
+        for s in srcs:
+            c_offs.append(at)
+            at += s.shape[1]
+    c_offs = [int(v) for v in c_offs]
+    if len(c_offs) != len(srcs):
+        raise RuntimeError("bilinear_ac_cat: one channel offset per source expected")
+    if out is None:
+        out = torch.empty((n, max(o + s.shape[1] for o, s in zip(c_offs, srcs)), hh, ww), dtype=torch.float32, device=srcs[0].device)
+    else:
+        _req(out, "out")
+        if out.dim() != 4 or out.shape[0] != n or tuple(out.shape[2:]) != (hh, ww):
+            raise RuntimeError(f"out: expected [{n}, C_tot, {hh}, {ww}], got {tuple(out.shape)}")
+        if any(_overlaps(out, s) for s in srcs):
+            raise RuntimeError("bilinear_ac_cat: out must not overlap a source")
+    ctot = out.shape[1]
+    arr = (_lib.BilinearSrc * 3)()
+    for k, (s, o) in enumerate(zip(srcs, c_offs)):
+        if o < 0 or o + s.shape[1] > ctot:
+            raise RuntimeError(f"bilinear_ac_cat: channels [{o}, {o + s.shape[1]}) of source {k} leave the {ctot} channels of out")
+        if any(o < c_offs[j] + srcs[j].shape[1] and c_offs[j] < o + s.shape[1] for j in range(k)):
+            raise RuntimeError(f"bilinear_ac_cat: the channel slice of source {k} overlaps an earlier one")
+        arr[k].ptr, arr[k].C, arr[k].h, arr[k].w, arr[k].c_off = s.data_ptr(), s.shape[1], s.shape[2], s.shape[3], o
+    check(_lib.load().slu_bilinear_ac_cat(arr, len(srcs), out.data_ptr(), n, ctot, hh, ww, _stream()), "slu_bilinear_ac_cat")
+    return out
+
+
+def bilinear_ac_softmax(logits: torch.Tensor, size=None) -> torch.Tensor:
+    """softmax(F.interpolate(logits, size=size, mode='bilinear', align_corners=True), dim=1) in one launch; logits [N, C <= 32, h, w].
+    size None (or the logits' own): the plain class softmax."""
+    _req(logits, "logits")
+    if logits.dim() != 4 or logits.numel() == 0:
+        raise RuntimeError(f"logits: expected a non-empty [N, C, h, w] tensor, got {tuple(logits.shape)}")
+    n, c, h, w = logits.shape
+    if c > 32:
+        raise RuntimeError(f"bilinear_ac_softmax: at most 32 classes supported, got {c}")
+    hh, ww = (h, w) if size is None else (int(v) for v in size)
+    if hh < 1 or ww < 1:
+        raise RuntimeError("bilinear_ac_softmax: size must be positive")
+    y = torch.empty((n, c, hh, ww), dtype=torch.float32, device=logits.device)
+    check(_lib.load().slu_bilinear_ac_softmax(logits.data_ptr(), y.data_ptr(), n, c, h, w, hh, ww, _stream()), "slu_bilinear_ac_softmax")
+    return y
