@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define SLU_ABI_VERSION 45
+#define SLU_ABI_VERSION 46
 
 #define SLU_OK            0
 #define SLU_EINVAL       -1   /* null pointer / non-positive size / inconsistent descriptor   */
@@ -926,6 +926,28 @@ typedef struct slu_bilinear_src {   /* HOST struct, 24 bytes */
 } slu_bilinear_src;
 int slu_bilinear_ac_cat(const slu_bilinear_src* srcs, int nsrc, float* out, int N, int C_tot, int H, int W, slu_stream_t stream);
 int slu_bilinear_ac_softmax(const float* x, float* y, int N, int C, int h, int w, int H, int W, slu_stream_t stream);
+
+/* ---- FIDNet ResNet34_point (baselines/FIDNet/ResNet.py:451-593, 145-170) ---------------------------------------------------------------------
+ * slu_point_mlp: a chain of 1 .. 4 per-pixel 1x1 convs, each with bias and LeakyReLU, in ONE launch (the point-MLP stem of :469-502, 563-576 with
+ * eval BatchNorm folded into the convs):
+ *
+ *   y = act( W_L . ... act( W_1 . x + b_1 ) ... + b_L )    per pixel;  act(v) = v > 0 ? v : slope * v, on the last layer only where act_last != 0
+ *
+ * x [N][C0][HW] -> out [N][widths[L - 1]][HW], HW the flattened pixel count of an image (there is no spatial structure).  `widths` is a HOST array
+ * of the L layer widths; bias holds b_1 .. b_L one after the other (sum of the widths floats).  wpack holds, one after the other, the Packed-weights
+ * images (above) of W_l [widths[l]][K_l] with K-chunk 16, each written by one slu_point_mlp_pack(w, cout, cin, out) call:
+ * (cout / 32) * ceil(cin / 16) * 8 * 64 floats.  The intermediate maps stay in LDS as the next layer's B operand; the input and the last
+ * layer's output are the only activations that touch global memory.  Every product is exact fp32 (v_mfma_f32_32x32x2_f32, a k-ordered fmaf
+ * chain) whatever the conv precision of the surrounding model; no atomics, so results are bit-identical run to run.
+ * 1 <= C0 <= 32, every width a multiple of 32 and at most 512, N <= 65535, HW < 2^31 - 1: anything else is SLU_EUNSUPPORTED (more than 4 layers:
+ * SLU_EINVAL).
+ * slu_bilinear_ac_sum: out [N][C][H][W] = sum over k of the align_corners = True interpolation of src_k [N][C][h_k][w_k] to H x W, 1 .. 3 sources
+ * of the same C (c_off must be 0), the terms added in source order; the coordinates and the limits are slu_bilinear_ac_cat's, and one source at
+ * the output size returns the input bit for bit.  `srcs` is a HOST array. */
+int slu_point_mlp_pack(const float* w, int cout, int cin, float* out, slu_stream_t stream);
+int slu_point_mlp(const float* x, const float* wpack, const float* bias, const int* widths, int nlayers, int N, int C0, long long HW, float slope,
+                  int act_last, float* out, slu_stream_t stream);
+int slu_bilinear_ac_sum(const slu_bilinear_src* srcs, int nsrc, float* out, int N, int C, int H, int W, slu_stream_t stream);
 
 #ifdef __cplusplus
 }

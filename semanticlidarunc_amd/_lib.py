@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-ABI_VERSION = 45
+ABI_VERSION = 46
 MAX_SRC = 3
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libslu_hip.so")
@@ -321,6 +321,10 @@ SIGNATURES = {
                                  c_f32p, c_f32p, c_stream]),
     "slu_bilinear_ac_cat": (C.c_int, [C.POINTER(BilinearSrc), C.c_int, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_stream]),
     "slu_bilinear_ac_softmax": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_stream]),
+    "slu_point_mlp_pack": (C.c_int, [c_f32p, C.c_int, C.c_int, c_f32p, c_stream]),
+    "slu_point_mlp": (C.c_int, [c_f32p, c_f32p, c_f32p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_float, C.c_int, c_f32p,
+                                c_stream]),
+    "slu_bilinear_ac_sum": (C.c_int, [C.POINTER(BilinearSrc), C.c_int, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_stream]),
 }
 
 _lib = None

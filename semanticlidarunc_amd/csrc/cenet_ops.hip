@@ -2,6 +2,7 @@
 //   bilinear_ac_cat_kernel       F.interpolate(x_k, size = (H, W), mode = 'bilinear', align_corners = True) of up to three maps, each written
 //                                into its channel slice of ONE [N, C_tot, H, W] buffer (:165-170: three interpolations + their part of torch.cat)
 //   bilinear_ac_softmax_kernel   the same interpolation of a logit map with C <= 32 classes, then softmax over the classes (:173-184)
+//   bilinear_ac_sum_kernel       the sum of the same interpolation of up to three maps of equal channel count (FIDNet's commuted head)
 //
 // The coordinate map (ATen's area_pixel_compute_source_index with align_corners = True): src = dst * (in - 1) / (out - 1), and 0 where out == 1
 // or in == 1; i0 = floor(src), i1 = min(i0 + 1, in - 1), weights l1 = src - i0, l0 = 1 - l1;
@@ -123,6 +124,75 @@ __global__ __launch_bounds__(256) void bilinear_ac_cat_kernel(AcCatArgs a, float
   }
 }
 
+// out[n, c] = sum over k of the interpolation of src_k[n, c]: the walk of bilinear_ac_cat_kernel per source -- the same taps, the same two
+// nested lerps -- with the terms added in source order in registers.  grid (column tiles of 256, row tiles of 16,
+// N * C planes); every source has the C channels of `out`.  FIDNet's head (fidnet.py) runs its 1x1 conv over the three interpolated pyramid maps
+// at their own low resolutions and sums the interpolated results here: the conv commutes with the interpolation (head of this file).
+__global__ __launch_bounds__(256) void bilinear_ac_sum_kernel(AcCatArgs a, float* __restrict__ out, int H, int W, int vec) {
+  const size_t plane = blockIdx.z;
+  const int ox = (blockIdx.x * 64 + threadIdx.x) * 4;
+  if (ox >= W) return;
+  const int denx = W - 1, deny = H - 1;
+  const float inv_dx = 1.0f / (float)denx, inv_dy = 1.0f / (float)deny;
+  const int oy0 = (blockIdx.y * 4 + threadIdx.y) * AC_ROWS;
+  float4 acc[AC_ROWS] = {};
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    if (k < a.nsrc) {
+      const int h = a.h[k], w = a.w[k];
+      const float* __restrict__ p = a.ptr[k] + plane * (size_t)h * w;
+      AcTap tx[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) tx[j] = ac_taps<float>(min(ox + j, W - 1), w, denx, inv_dx);
+      int cy0 = -1, cy1 = -1;
+      float4 h0 = {}, h1 = {};
+#pragma unroll
+      for (int j = 0; j < AC_ROWS; ++j) {
+        const int oy = oy0 + j;
+        if (oy < H) {
+          const AcTap ty = ac_taps<float>(oy, h, deny, inv_dy);
+          if (ty.i0 != cy0) {
+            if (ty.i0 == cy1) h0 = h1;
+            else h0 = ac_hrow(p + (size_t)ty.i0 * w, tx);
+            cy0 = ty.i0;
+          }
+          if (ty.i1 != cy1) {
+            if (ty.i1 == cy0) h1 = h0;
+            else h1 = ac_hrow(p + (size_t)ty.i1 * w, tx);
+            cy1 = ty.i1;
+          }
+          float4 v;
+          v.x = ty.l0 * h0.x + ty.l1 * h1.x;
+          v.y = ty.l0 * h0.y + ty.l1 * h1.y;
+          v.z = ty.l0 * h0.z + ty.l1 * h1.z;
+          v.w = ty.l0 * h0.w + ty.l1 * h1.w;
+          if (k == 0) {
+            acc[j] = v;      // not 0 + v: a single source at the output size comes back bit for bit, -0 included
+          } else {
+            acc[j].x += v.x, acc[j].y += v.y, acc[j].z += v.z, acc[j].w += v.w;
+          }
+        }
+      }
+    }
+  }
+  float* __restrict__ q = out + plane * (size_t)H * W;
+#pragma unroll
+  for (int j = 0; j < AC_ROWS; ++j) {
+    const int oy = oy0 + j;
+    if (oy < H) {
+      float* d = q + (size_t)oy * W + ox;
+      if (vec) {
+        *reinterpret_cast<float4*>(d) = acc[j];
+      } else {
+        d[0] = acc[j].x;
+        if (ox + 1 < W) d[1] = acc[j].y;
+        if (ox + 2 < W) d[2] = acc[j].z;
+        if (ox + 3 < W) d[3] = acc[j].w;
+      }
+    }
+  }
+}
+
 // grid (column tiles of 256, H, N); a lane owns one output pixel and its class column (class_column.h), lanes of a wave are azimuth-adjacent.
 // The interpolated logits and their maximum are kept in fp64 up to the subtraction of the maximum: a logit of magnitude 80 carries an fp32
 // rounding of 4e-6, which the softmax turns into up to 1e-6 of a probability wherever two classes are close; v - max is small where the
@@ -192,6 +262,27 @@ extern "C" int slu_bilinear_ac_cat(const slu_bilinear_src* srcs, int nsrc, float
   const int vec = W % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
   const dim3 grid((unsigned)((W + 255) / 256), gy, (unsigned)planes);
   hipLaunchKernelGGL(bilinear_ac_cat_kernel, grid, dim3(64, 4), 0, slu_stream(stream), a, out, C_tot, H, W, vec);
+  SLU_CHECK_LAUNCH();
+}
+
+extern "C" int slu_bilinear_ac_sum(const slu_bilinear_src* srcs, int nsrc, float* out, int N, int C, int H, int W, slu_stream_t stream) {
+  if (!srcs || !out || nsrc < 1 || nsrc > 3 || N <= 0 || C <= 0 || H <= 0 || W <= 0) return SLU_EINVAL;
+  AcCatArgs a = {};
+  a.nsrc = nsrc;
+  a.csum = C;
+  for (int k = 0; k < nsrc; ++k) {
+    const slu_bilinear_src& s = srcs[k];
+    if (!s.ptr || s.C != C || s.h <= 0 || s.w <= 0 || s.c_off != 0) return SLU_EINVAL;
+    if (!ac_axis_ok(s.h, H) || !ac_axis_ok(s.w, W)) return SLU_EUNSUPPORTED;
+    a.ptr[k] = s.ptr;
+    a.C[k] = C, a.h[k] = s.h, a.w[k] = s.w;
+  }
+  const long long planes = (long long)N * C;
+  const unsigned gy = (unsigned)((H + 4 * AC_ROWS - 1) / (4 * AC_ROWS));
+  if (planes > 65535 || gy > 65535) return SLU_EUNSUPPORTED;
+  const int vec = W % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+  const dim3 grid((unsigned)((W + 255) / 256), gy, (unsigned)planes);
+  hipLaunchKernelGGL(bilinear_ac_sum_kernel, grid, dim3(64, 4), 0, slu_stream(stream), a, out, H, W, vec);
   SLU_CHECK_LAUNCH();
 }
 

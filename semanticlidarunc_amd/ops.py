@@ -2233,3 +2233,104 @@ def bilinear_ac_softmax(logits: torch.Tensor, size=None) -> torch.Tensor:
     y = torch.empty((n, c, hh, ww), dtype=torch.float32, device=logits.device)
     check(_lib.load().slu_bilinear_ac_softmax(logits.data_ptr(), y.data_ptr(), n, c, h, w, hh, ww, _stream()), "slu_bilinear_ac_softmax")
     return y
+
+
+def bilinear_ac_sum(srcs: Sequence[torch.Tensor], size) -> torch.Tensor:
+    """sum(F.interpolate(s, size=size, mode='bilinear', align_corners=True) for s in srcs) in one launch, the terms added in source order;
+    1..3 sources [N, C, h_k, w_k] of one N and C.  One source at the output size comes back bit for bit."""
+    if not 1 <= len(srcs) <= 3:
+        raise RuntimeError(f"bilinear_ac_sum: 1..3 sources supported, got {len(srcs)}")
+    hh, ww = (int(v) for v in size)
+    if hh < 1 or ww < 1:
+        raise RuntimeError("bilinear_ac_sum: size must be positive")
+    n = c = None
+    for i, s in enumerate(srcs):
+        _req(s, f"srcs[{i}]")
+        if s.dim() != 4 or s.numel() == 0 or (n is not None and s.shape[0] != n):
+            raise RuntimeError(f"srcs[{i}]: expected a non-empty [N, C, h, w] tensor with the batch of srcs[0], got {tuple(s.shape)}")
+        if c is not None and s.shape[1] != c:
+            raise RuntimeError(f"srcs[{i}]: expected the {c} channels of srcs[0], got {s.shape[1]}")
+        n, c = s.shape[0], s.shape[1]
+    out = torch.empty((n, c, hh, ww), dtype=torch.float32, device=srcs[0].device)
+    arr = (_lib.BilinearSrc * 3)()
+    for k, s in enumerate(srcs):
+        arr[k].ptr, arr[k].C, arr[k].h, arr[k].w, arr[k].c_off = s.data_ptr(), c, s.shape[2], s.shape[3], 0
+    check(_lib.load().slu_bilinear_ac_sum(arr, len(srcs), out.data_ptr(), n, c, hh, ww, _stream()), "slu_bilinear_ac_sum")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
+# FIDNet's point-MLP stem (csrc/point_mlp.hip; baselines/FIDNet/ResNet.py:469-502, 563-576)
+POINT_MLP_MAX_LAYERS, POINT_MLP_MAX_C0, POINT_MLP_MAX_WIDTH = 4, 32, 512
+
+
+def point_mlp_packed_floats(cout: int, cin: int) -> int:
+    """Floats of the packed image of one layer's weight [cout, cin] (include/slu.h, slu_point_mlp)."""
+    return (cout // 32) * ((cin + 15) // 16) * 8 * 64
+
+
+def _point_mlp_chain(fn: str, c0: int, widths) -> None:
+    if not 1 <= len(widths) <= POINT_MLP_MAX_LAYERS:
+        raise RuntimeError(f"{fn}: 1..{POINT_MLP_MAX_LAYERS} layers supported, got {len(widths)}")
+    if not 1 <= c0 <= POINT_MLP_MAX_C0:
+        raise RuntimeError(f"{fn}: 1..{POINT_MLP_MAX_C0} input channels supported, got {c0}")
+    if any(w < 32 or w % 32 or w > POINT_MLP_MAX_WIDTH for w in widths):
+        raise RuntimeError(f"{fn}: every layer width must be a multiple of 32 and at most {POINT_MLP_MAX_WIDTH}, got {tuple(widths)}")
+
+
+def pack_point_mlp(weights: Sequence[torch.Tensor]) -> torch.Tensor:
+    """The 1x1 weights [C_l, C_{l-1}] (or [C_l, C_{l-1}, 1, 1]) of a chain of 1..4 layers -> the MFMA A-fragment images slu_point_mlp streams, one
+    after the other (re-run after every weight update)."""
+    ws = []
+    for i, w in enumerate(weights):
+        _req(w, f"weights[{i}]")
+        if w.dim() == 4 and tuple(w.shape[2:]) == (1, 1):
+            w = w.view(w.shape[0], w.shape[1])
+        if w.dim() != 2 or w.numel() == 0:
+            raise RuntimeError(f"weights[{i}]: expected [Cout, Cin] or [Cout, Cin, 1, 1], got {tuple(w.shape)}")
+        if ws and w.shape[1] != ws[-1].shape[0]:
+            raise RuntimeError(f"weights[{i}]: {w.shape[1]} input channels do not follow the {ws[-1].shape[0]} outputs of the layer before")
+        ws.append(w)
+    if not ws:
+        raise RuntimeError("pack_point_mlp: 1..4 layers supported, got 0")
+    _point_mlp_chain("pack_point_mlp", ws[0].shape[1], [w.shape[0] for w in ws])
+    sizes = [point_mlp_packed_floats(w.shape[0], w.shape[1]) for w in ws]
+    out = torch.empty(sum(sizes), dtype=torch.float32, device=ws[0].device)
+    lib, at = _lib.load(), 0
+    for w, sz in zip(ws, sizes):
+        check(lib.slu_point_mlp_pack(w.data_ptr(), w.shape[0], w.shape[1], out.data_ptr() + 4 * at, _stream()), "slu_point_mlp_pack")
+        at += sz
+    return out
+
+
+def point_mlp(x: torch.Tensor, packed: torch.Tensor, biases, widths: Sequence[int], slope: float, act_last: bool = True) -> torch.Tensor:
+    """y = act(W_L ... act(W_1 x + b_1) ... + b_L) per pixel in one launch (slu_point_mlp): x [N, C0 <= 32, H, W] -> [N, widths[-1], H, W],
+    packed = pack_point_mlp(weights), biases the L bias vectors (a sequence, or one tensor holding them one after the other),
+    act(v) = v > 0 ? v : slope v, on the last layer only with act_last.  The intermediate maps stay on chip.  Every product is the exact-fp32 MFMA
+    under every conv precision; bit-identical run to run."""
+    _req(x, "x")
+    if x.dim() != 4 or x.numel() == 0:
+        raise RuntimeError(f"x: expected a non-empty [N, C0, H, W] tensor, got {tuple(x.shape)}")
+    widths = [int(w) for w in widths]
+    n, c0, h, w = x.shape
+    _point_mlp_chain("point_mlp", c0, widths)
+    if not isinstance(biases, torch.Tensor):
+        for i, b in enumerate(biases):
+            _req(b, f"biases[{i}]")
+        if [b.numel() for b in biases] != widths:
+            raise RuntimeError(f"biases: expected vectors of {widths} elements, got {[b.numel() for b in biases]}")
+        biases = torch.cat([b.reshape(-1) for b in biases])
+    _req(biases, "biases")
+    if biases.numel() != sum(widths):
+        raise RuntimeError(f"biases: expected {sum(widths)} elements (the widths {widths}), got {biases.numel()}")
+    _req(packed, "packed")
+    want = sum(point_mlp_packed_floats(co, ci) for co, ci in zip(widths, [c0] + widths[:-1]))
+    if packed.numel() != want:
+        raise RuntimeError(f"packed: {packed.numel()} floats does not match C0={c0} widths={widths} ({want})")
+    if n > 65535 or h * w >= 2 ** 31 - 1:
+        raise _lib.SluError(f"slu_point_mlp: {_lib.load().slu_strerror(-2).decode()} (code -2): N={n} H*W={h * w}")
+    out = torch.empty((n, widths[-1], h, w), dtype=torch.float32, device=x.device)
+    arr = (C.c_int * len(widths))(*widths)
+    check(_lib.load().slu_point_mlp(x.data_ptr(), packed.data_ptr(), biases.data_ptr(), arr, len(widths), n, c0, h * w, float(slope),
+                                    1 if act_last else 0, out.data_ptr(), _stream()), "slu_point_mlp")
+    return out
